@@ -7,6 +7,7 @@ reference (MU: V,U,Z, pycmf/cmf_solvers.py:248-263; Newton: U,Z,V, :510-522)
 over synthetic X (m x d), Y (d x p) already resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3|c5|tiny] [--option name=value ...]
+                    [--dump-outputs DIR] [--full]
 
 Default workload = C4 (the configuration the metric is quoted on; it fits one
 GPU: 34.4 GB).  c2 / c3 / c5 are the other BASELINE configs (parity-test
@@ -20,9 +21,14 @@ fraction of Y's columns / Z's rows; V is replicated and reassembled by one RCCL
 all-reduce per iteration (pycmf_amd/sharded.py).  The per-row Newton workload (c3) shards the rows of all three
 factors instead (two contexts per rank, factor rows exchanged; ShardedNewtonRows).
 
-Prints ONE JSON line on rank 0 with ``roofline`` (dominant kernel class, HIP
-events on the launch stream over the timed region) and ``cpu_baseline`` (CPU
-oracle, bounded sample, rank 0, N=1).
+Prints ONE JSON line on rank 0: ``value`` (it/s) and ``ms_per_step`` over the K
+timed steps, the per-step ``series_ms``, the configuration.  A plain run does
+only that: set up, warm up, time the K steps, write ``--dump-outputs``, print.
+``--full`` adds what takes work of its own: ``roofline`` (dominant kernel class,
+HIP events on the launch stream over the timed region, per-class times of a few
+instrumented iterations after it), ``rel_residual``, ``conditioning``, the
+replica check of N > 1 runs and ``cpu_baseline`` (CPU oracle, bounded sample,
+rank 0, N=1).
 """
 import argparse
 import json
@@ -94,6 +100,7 @@ WORKLOADS["c3z"] = WORKLOADS["c3"]   # rounds 4-5 named the l2 = 0 configuration
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # dense bf16 (v_mfma_f32_32x32x16_bf16)
 HBM_PEAK_GBPS = 8000.0         # MI355X_MICROARCH.md: HBM3E spec
+DUMP_FACTOR_BYTES = 16 << 20   # --dump-outputs: at most this many bytes per factor, its row list included (48 MB for all three)
 
 
 def algorithmic_flops(w):
@@ -205,6 +212,125 @@ def cpu_baseline(w, budget_s=20.0):
                 cpu_count=os.cpu_count() or 1, ratio=ratio, per_row=per_row)
 
 
+def roofline(w, args, world, r0, r1, kp, classes, other, rh_samples, extra, t_extra, bf16x6):
+    """The roofline block of a --full line: the dominant kernel class priced against its bound from the HIP events of the timed
+    region (data-pass classes), the stored PMC traffic of the workload, and the per-class times of the instrumented iterations."""
+    d, k = w["d"], w["k"]
+    # dominant kernel class = most device time on rank 0
+    dom = max(("gemm_nn", "gemm_tn", "gemm_pair", "spmm", "rowhess"), key=lambda c: classes[c][0])
+    dms, dn, dfl = classes[dom]
+    if dom == "spmm":
+        # HBM-bound gather kernel (column-blocked, output-stationary SpMM).  Algorithmic (compulsory) bytes of one A*F
+        # product: the regrouped entry list once (16 B per non-zero) + the gathered operand once + the output once;
+        # the k_pad*4-byte factor-row gather per non-zero is served by the XCD L2s (rows of a 2 MB column block are
+        # shared by the workgroups of an XCD) and reported separately.
+        nnz = float(r1 - r0) * w["nnz_per_row"]
+        comp = nnz * 16.0 + ((r1 - r0) + d) * kp * 4.0
+        achieved = comp / (dms / max(dn, 1) * 1e-3) / 1e9
+        spmm_traffic = None
+        tpath = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.workload)
+        if world == 1 and os.path.exists(tpath):
+            try:
+                spmm_traffic = json.load(open(tpath)).get("spmm")
+            except Exception:
+                spmm_traffic = None
+        roof = {"bound": "hbm", "kernel": "cmfk::spmm_blocked_kernel<%d>  (A F and A^T F of the native CSR input)" % (kp // 64),
+                "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": spmm_traffic,
+                "traffic_unit": "bytes per launch past L2 (rocprofv3 PMC FETCH_SIZE x2 + WRITE_SIZE, profiles/traffic_c5.json): "
+                                "Infinity-Cache hits of the factor-row gathers included",
+                "gathered_GBps": nnz * (kp * 4.0 + 16.0) / (dms / max(dn, 1) * 1e-3) / 1e9,
+                "gather_peak_GBps": 17800.0,
+                "gather_frac": nnz * (kp * 4.0 + 16.0) / (dms / max(dn, 1) * 1e-3) / 1e9 / 17800.0,
+                "note": "achieved = compulsory HBM bytes (entry list + gathered operand + output) / launch time; the bound that "
+                        "matters is the per-nonzero factor-row gather (gathered_GBps) against the measured L2 row-gather rate "
+                        "of the chip, 16.8-18.8 TB/s (MI355X_MICROARCH.md, Indexed rows: gather into LDS)",
+                "avg_launch_ms": dms / max(dn, 1), "launches": dn}
+    else:
+        achieved = dfl / (dms * 1e-3) / 1e12 if dms > 0 else 0.0
+        reference_order = achieved
+        if dom == "rowhess" and rh_samples[0] > 0:
+            # linear sampled sides share partial outer-product sums between rows (option row_classes): the kernel is priced
+            # on the sample rows it actually gathers, the rate in the reference's own count is reported beside it
+            achieved *= rh_samples[1] / rh_samples[0]
+        traffic = None
+        tpath = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.workload)
+        if world == 1 and os.path.exists(tpath):
+            try:
+                traffic = json.load(open(tpath)).get(dom)
+            except Exception:
+                traffic = None
+        if dom == "rowhess":
+            kname = ("cmfk::row_hess_kernel<%d>  (fused per-row gradient + Hessian over the sampled rows; flops "
+                     "credited for the symmetric half of each H_i, k(k+1) per sample row gathered)" % kp)
+        elif dom == "gemm_pair":
+            kname = ("cmfk::gemm_pair_kernel  (k_pad = 128: X^T U with Y Z, X V with Y^T V -- the two data passes of an MU "
+                     "half-iteration as one launch, their K-steps cut into equal quotas per CU)")
+        else:
+            kname = "cmfk::gemm_kernel<%d, %d, 0, 4>  (%s data pass)" % (
+                0 if dom == "gemm_nn" else 1, 256 if k >= 256 else kp,
+                "NN: X V / Y Z / W KR" if dom == "gemm_nn" else "TN: X^T U / Y^T V / W^T KR")
+        peak = FP32_MFMA_PEAK_TFLOPS
+        if bf16x6 and dom in ("gemm_nn", "gemm_tn", "gemm_pair"):
+            # optional arithmetic: 6 bf16 MFMA products per fp32-equivalent product -> the bound is the bf16 matrix peak / 6
+            peak = BF16_MFMA_PEAK_TFLOPS / 6.0
+            kname = ("cmfk::bf16x6_gemm_kernel  (data pass on v_mfma_f32_32x32x16_bf16, three bf16 planes per fp32 operand, "
+                     "six cross products, f32 accumulation; peak = bf16 dense peak / 6)")
+            traffic = None
+        roof = {"bound": "mfma",
+                "kernel": kname,
+                "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                "frac": achieved / peak, "traffic": traffic,
+                "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, profiles/traffic_%s.json)" % args.workload,
+                "algorithmic_flops_per_launch": dfl / max(dn, 1) * (achieved / reference_order if reference_order > 0 else 1.0),
+                "avg_launch_ms": dms / max(dn, 1), "launches": dn}
+        if dom == "rowhess":
+            roof["sample_rows_reference"] = rh_samples[0] / args.steps
+            roof["sample_rows_gathered"] = rh_samples[1] / args.steps
+            roof["reference_order_tflops"] = reference_order
+            roof["note"] = ("sample_rows_reference = outer products the reference runs per iteration (one per row and sampled "
+                            "index); sample_rows_gathered = what the kernel runs: with a linear link the rows of a group of 4 "
+                            "share the sums of the samples they have in common (shared partial sums, DESIGN.md section 4); "
+                            "achieved / frac price the kernel on the gathered rows, reference_order_tflops on the reference's count")
+    if dom == "rowhess" and bf16x6 and kp == 256:
+        roof["kernel"] = ("cmfk::row_hess6_kernel  (fused per-row gradient + Hessian; Hessian on v_mfma_f32_32x32x16_bf16 from three "
+                          "bf16 planes of sqrt(w) o, six products per block; flops credited for the symmetric half, k(k+1) per sample)")
+        roof["peak"] = BF16_MFMA_PEAK_TFLOPS / 6.0
+        roof["frac"] = roof["achieved"] / roof["peak"]
+    elif dom == "rowhess" and kp == 256 and "row_symmetric=0" not in args.option:
+        # the MFMAs cover 28 whole 32x32 blocks above the diagonal and three 16x16 sub-blocks of each of the 8 diagonal ones
+        # (34 block-equivalents; 36 with row_symmetric=1 / 3, which compute the diagonal blocks in full)
+        whole = 36 if any(o in args.option for o in ("row_symmetric=1", "row_symmetric=3")) else 34
+        roof["mfma_executed_tflops"] = achieved * (whole * 2048.0 + 4 * kp) / (kp * (kp + 1.0) + 4 * kp)
+    roof["traffic_provenance"] = (None if roof.get("traffic") is None else
+                                  "stored: profiles/traffic_%s.json, from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                  "command (tools/refresh_r05.sh, gfx950 corrections of MI355X_MICROARCH.md); PMC collection cannot run "
+                                  "inside a timed bench run, so this figure is NOT measured by the run that printed this line" % args.workload)
+    roof["per_class_ms_per_step"] = {c: v[0] / extra for c, v in other.items() if v[1]}
+    roof["per_class_launches_per_step"] = {c: v[1] / extra for c, v in other.items() if v[1]}
+    roof["instrumented_ms_per_step"] = t_extra
+    roof["per_class_note"] = ("%d extra iterations after the timed region with HIP events around every launch (nested scopes record once, "
+                              "under the outermost class): the classes add up to instrumented_ms_per_step, the wall clock of THOSE iterations, "
+                              "which exceeds ms_per_step where the events keep host round trips from overlapping with device work; inside the "
+                              "timed region only the data-pass classes carry events (what achieved / avg_launch_ms are computed from)" % extra)
+    return roof
+
+
+def dump_outputs(ctx, directory):
+    """--dump-outputs: the factors the timed steps left, as a caller of the update step receives them.  A factor larger than
+    DUMP_FACTOR_BYTES is written as a fixed sample of its rows (seeded, sorted; the same rows in every run of the same workload)."""
+    import numpy as np
+    from pycmf_amd import _lib
+    os.makedirs(directory, exist_ok=True)
+    for name, which in (("U", _lib.CMF_U), ("V", _lib.CMF_V), ("Z", _lib.CMF_Z)):
+        F = ctx.get_factor(which)
+        n, k = F.shape
+        keep = max(1, DUMP_FACTOR_BYTES // (4 * k + 8))      # a row: k float32 values + its index as float64
+        rows = np.arange(n) if n <= keep else np.sort(np.random.RandomState(1234 + which).choice(n, size=keep, replace=False))
+        np.save(os.path.join(directory, name + ".npy"), F[rows].astype(np.float32))
+        np.save(os.path.join(directory, name + "_rows.npy"), rows.astype(np.float64))
+
+
 def launch_ranks(n, argv):
     """``python bench.py --gpus N`` without a launcher: start N fresh rank processes (one per GPU) BEFORE anything in
     this process touches the GPU, wait for them, forward rank 0's JSON line.  Never exec: the parent only supervises."""
@@ -255,7 +381,16 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: HIP events around the data passes inside the timed region, a few "
+                         "instrumented iterations after it (roofline, per-class times), rel_residual, conditioning, the replica check of "
+                         "N > 1 runs, the steady-state refusal of per-row Newton lines and the CPU oracle baseline (at N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU oracle baseline out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write rank 0's factors U, V, Z as DIR/<name>.npy (float32) and the indices of the rows "
+                         "written as DIR/<name>_rows.npy (float64): every row, or a fixed seeded sample of rows where a factor would take "
+                         "more than %d MB.  Same arguments, same inputs; per-row Newton workloads warm up until steady, a number of "
+                         "iterations that can differ between runs: --max-warmup 0 fixes it" % (DUMP_FACTOR_BYTES >> 20))
     ap.add_argument("--overlap-chunks", type=int, default=1,
                     help="N > 1 GPUs, MU on dense data: reduce the (d + k) k buffer in this many row blocks on a side stream while the "
                          "next block's partial is computed (default 1: one serial all-reduce)")
@@ -477,9 +612,10 @@ def main():
             if same >= 2 and steady_time and args.warmup + warm_extra >= min(16, args.max_warmup):
                 break
         args.warmup += warm_extra
-    for c_ in ctxs:
-        c_.kernel_timing(2)        # HIP events around the data-pass launches only (the class the roofline prices): an event pair per
-        c_.kernel_timing_reset()   # launch serialises the stream for a few microseconds, 7 % of a C2 iteration when every launch has one
+    if args.full:
+        for c_ in ctxs:
+            c_.kernel_timing(2)        # HIP events around the data-pass launches only (the class the roofline prices): an event pair per
+            c_.kernel_timing_reset()   # launch serialises the stream for a few microseconds, 7 % of a C2 iteration when every launch has one
     if coll:
         ctx.sync()
         coll.reset()
@@ -516,8 +652,10 @@ def main():
             dump[name] = F[mine - lo]
             dump[name + "_absmax"] = np.array([np.abs(F).max() if F.size else 0.0])
         np.savez(args.dump_rows + ".rank%d.npz" % rank, **dump)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, args.dump_outputs)
     replicas = None
-    if coll and not rows_mode:
+    if args.full and coll and not rows_mode:
         # V is replicated: after the timed iterations every rank must hold the same V, bit for bit (a collective that summed
         # the wrong chunks, or ranks that never met, shows up here and not only as a strange residual)
         vsum = float(np.abs(ctx.get_factor(_lib.CMF_V)).sum(dtype=np.float64))
@@ -525,25 +663,26 @@ def main():
         lo = -float(coll.all_reduce_host([-vsum], "max")[0])
         replicas = {"sum_abs_V_max_over_ranks": hi, "sum_abs_V_min_over_ranks": lo, "identical": hi == lo}
 
-    names = ("gemm_nn", "gemm_tn", "gemm_pair", "gemm_small", "gemm_nt", "spmm", "rowhess", "eigen", "elementwise")
-    classes = {c: tuple(sum(v) for v in zip(*(c_.kernel_time(c) for c_ in ctxs))) for c in names}
-    rh_samples = tuple(sum(v) for v in zip(*(c_.rowhess_samples() for c_ in ctxs)))
-    # the other kernel classes: a few more iterations OUTSIDE the timed region with events around every launch
-    extra = min(args.steps, 3)
-    for c_ in ctxs:
-        c_.kernel_timing(1)
-        c_.kernel_timing_reset()
-    t_extra = time.perf_counter()
-    for it in range(extra):
-        do_step(args.warmup + args.steps + it)
-    sync_all()
-    t_extra = (time.perf_counter() - t_extra) / max(extra, 1) * 1e3
-    other = {c: tuple(sum(v) for v in zip(*(c_.kernel_time(c) for c_ in ctxs))) for c in names}
-    for c_ in ctxs:
-        c_.kernel_timing(False)
-    ex2, ey2 = ctx.residual_sq(w.get("x_link", "linear"), w.get("y_link", "linear"))
-    x2, y2 = ctx.data_sq()
-    kp = ctx.geometry()[3]
+    if args.full:
+        names = ("gemm_nn", "gemm_tn", "gemm_pair", "gemm_small", "gemm_nt", "spmm", "rowhess", "eigen", "elementwise")
+        classes = {c: tuple(sum(v) for v in zip(*(c_.kernel_time(c) for c_ in ctxs))) for c in names}
+        rh_samples = tuple(sum(v) for v in zip(*(c_.rowhess_samples() for c_ in ctxs)))
+        # the other kernel classes: a few more iterations OUTSIDE the timed region with events around every launch
+        extra = min(args.steps, 3)
+        for c_ in ctxs:
+            c_.kernel_timing(1)
+            c_.kernel_timing_reset()
+        t_extra = time.perf_counter()
+        for it in range(extra):
+            do_step(args.warmup + args.steps + it)
+        sync_all()
+        t_extra = (time.perf_counter() - t_extra) / max(extra, 1) * 1e3
+        other = {c: tuple(sum(v) for v in zip(*(c_.kernel_time(c) for c_ in ctxs))) for c in names}
+        for c_ in ctxs:
+            c_.kernel_timing(False)
+        ex2, ey2 = ctx.residual_sq(w.get("x_link", "linear"), w.get("y_link", "linear"))
+        x2, y2 = ctx.data_sq()
+        kp = ctx.geometry()[3]
 
     if coll:
         coll.barrier()
@@ -553,103 +692,6 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1e3
     its = args.steps / elapsed
-    # dominant kernel class = most device time on rank 0
-    dom = max(("gemm_nn", "gemm_tn", "gemm_pair", "spmm", "rowhess"), key=lambda c: classes[c][0])
-    dms, dn, dfl = classes[dom]
-    if dom == "spmm":
-        # HBM-bound gather kernel (column-blocked, output-stationary SpMM).  Algorithmic (compulsory) bytes of one A*F
-        # product: the regrouped entry list once (16 B per non-zero) + the gathered operand once + the output once;
-        # the k_pad*4-byte factor-row gather per non-zero is served by the XCD L2s (rows of a 2 MB column block are
-        # shared by the workgroups of an XCD) and reported separately.
-        nnz = float(r1 - r0) * w["nnz_per_row"]
-        comp = nnz * 16.0 + ((r1 - r0) + d) * kp * 4.0
-        achieved = comp / (dms / max(dn, 1) * 1e-3) / 1e9
-        spmm_traffic = None
-        tpath = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.workload)
-        if world == 1 and os.path.exists(tpath):
-            try:
-                spmm_traffic = json.load(open(tpath)).get("spmm")
-            except Exception:
-                spmm_traffic = None
-        roof = {"bound": "hbm", "kernel": "cmfk::spmm_blocked_kernel<%d>  (A F and A^T F of the native CSR input)" % (kp // 64),
-                "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": spmm_traffic,
-                "traffic_unit": "bytes per launch past L2 (rocprofv3 PMC FETCH_SIZE x2 + WRITE_SIZE, profiles/traffic_c5.json): "
-                                "Infinity-Cache hits of the factor-row gathers included",
-                "gathered_GBps": nnz * (kp * 4.0 + 16.0) / (dms / max(dn, 1) * 1e-3) / 1e9,
-                "gather_peak_GBps": 17800.0,
-                "gather_frac": nnz * (kp * 4.0 + 16.0) / (dms / max(dn, 1) * 1e-3) / 1e9 / 17800.0,
-                "note": "achieved = compulsory HBM bytes (entry list + gathered operand + output) / launch time; the bound that "
-                        "matters is the per-nonzero factor-row gather (gathered_GBps) against the measured L2 row-gather rate "
-                        "of the chip, 16.8-18.8 TB/s (MI355X_MICROARCH.md, Indexed rows: gather into LDS)",
-                "avg_launch_ms": dms / max(dn, 1), "launches": dn}
-    else:
-        achieved = dfl / (dms * 1e-3) / 1e12 if dms > 0 else 0.0
-        reference_order = achieved
-        if dom == "rowhess" and rh_samples[0] > 0:
-            # linear sampled sides share partial outer-product sums between rows (option row_classes): the kernel is priced
-            # on the sample rows it actually gathers, the rate in the reference's own count is reported beside it
-            achieved *= rh_samples[1] / rh_samples[0]
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.workload)
-        if world == 1 and os.path.exists(tpath):
-            try:
-                traffic = json.load(open(tpath)).get(dom)
-            except Exception:
-                traffic = None
-        if dom == "rowhess":
-            kname = ("cmfk::row_hess_kernel<%d>  (fused per-row gradient + Hessian over the sampled rows; flops "
-                     "credited for the symmetric half of each H_i, k(k+1) per sample row gathered)" % kp)
-        elif dom == "gemm_pair":
-            kname = ("cmfk::gemm_pair_kernel  (k_pad = 128: X^T U with Y Z, X V with Y^T V -- the two data passes of an MU "
-                     "half-iteration as one launch, their K-steps cut into equal quotas per CU)")
-        else:
-            kname = "cmfk::gemm_kernel<%d, %d, 0, 4>  (%s data pass)" % (
-                0 if dom == "gemm_nn" else 1, 256 if k >= 256 else kp,
-                "NN: X V / Y Z / W KR" if dom == "gemm_nn" else "TN: X^T U / Y^T V / W^T KR")
-        peak = FP32_MFMA_PEAK_TFLOPS
-        if bf16x6 and dom in ("gemm_nn", "gemm_tn", "gemm_pair"):
-            # optional arithmetic: 6 bf16 MFMA products per fp32-equivalent product -> the bound is the bf16 matrix peak / 6
-            peak = BF16_MFMA_PEAK_TFLOPS / 6.0
-            kname = ("cmfk::bf16x6_gemm_kernel  (data pass on v_mfma_f32_32x32x16_bf16, three bf16 planes per fp32 operand, "
-                     "six cross products, f32 accumulation; peak = bf16 dense peak / 6)")
-            traffic = None
-        roof = {"bound": "mfma",
-                "kernel": kname,
-                "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                "frac": achieved / peak, "traffic": traffic,
-                "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, profiles/traffic_%s.json)" % args.workload,
-                "algorithmic_flops_per_launch": dfl / max(dn, 1) * (achieved / reference_order if reference_order > 0 else 1.0),
-                "avg_launch_ms": dms / max(dn, 1), "launches": dn}
-        if dom == "rowhess":
-            roof["sample_rows_reference"] = rh_samples[0] / args.steps
-            roof["sample_rows_gathered"] = rh_samples[1] / args.steps
-            roof["reference_order_tflops"] = reference_order
-            roof["note"] = ("sample_rows_reference = outer products the reference runs per iteration (one per row and sampled "
-                            "index); sample_rows_gathered = what the kernel runs: with a linear link the rows of a group of 4 "
-                            "share the sums of the samples they have in common (shared partial sums, DESIGN.md section 4); "
-                            "achieved / frac price the kernel on the gathered rows, reference_order_tflops on the reference's count")
-    if dom == "rowhess" and bf16x6 and kp == 256:
-        roof["kernel"] = ("cmfk::row_hess6_kernel  (fused per-row gradient + Hessian; Hessian on v_mfma_f32_32x32x16_bf16 from three "
-                          "bf16 planes of sqrt(w) o, six products per block; flops credited for the symmetric half, k(k+1) per sample)")
-        roof["peak"] = BF16_MFMA_PEAK_TFLOPS / 6.0
-        roof["frac"] = roof["achieved"] / roof["peak"]
-    elif dom == "rowhess" and kp == 256 and "row_symmetric=0" not in args.option:
-        # the MFMAs cover 28 whole 32x32 blocks above the diagonal and three 16x16 sub-blocks of each of the 8 diagonal ones
-        # (34 block-equivalents; 36 with row_symmetric=1 / 3, which compute the diagonal blocks in full)
-        whole = 36 if any(o in args.option for o in ("row_symmetric=1", "row_symmetric=3")) else 34
-        roof["mfma_executed_tflops"] = achieved * (whole * 2048.0 + 4 * kp) / (kp * (kp + 1.0) + 4 * kp)
-    roof["traffic_provenance"] = (None if roof.get("traffic") is None else
-                                  "stored: profiles/traffic_%s.json, from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                  "command (tools/refresh_r05.sh, gfx950 corrections of MI355X_MICROARCH.md); PMC collection cannot run "
-                                  "inside a timed bench run, so this figure is NOT measured by the run that printed this line" % args.workload)
-    roof["per_class_ms_per_step"] = {c: v[0] / extra for c, v in other.items() if v[1]}
-    roof["per_class_launches_per_step"] = {c: v[1] / extra for c, v in other.items() if v[1]}
-    roof["instrumented_ms_per_step"] = t_extra
-    roof["per_class_note"] = ("%d extra iterations after the timed region with HIP events around every launch (nested scopes record once, "
-                              "under the outermost class): the classes add up to instrumented_ms_per_step, the wall clock of THOSE iterations, "
-                              "which exceeds ms_per_step where the events keep host round trips from overlapping with device work; inside the "
-                              "timed region only the data-pass classes carry events (what achieved / avg_launch_ms are computed from)" % extra)
     out = {
         "metric": "factor-update iterations/s (%s solver: one full update_step per iteration)" % w["solver"],
         "value": its,
@@ -672,10 +714,11 @@ def main():
                                   ("X/U row-sharded, Y/Z column-sharded x%d, V replicated; the one sum over the ranks per iteration, (d+k)*k f32, "
                                    "as %s" % (world, "reduce-scatter + row-blocked V epilogue + all-gather, the two k^2 Gram all-reduces inside the same two RCCL groups"
                                               if getattr(drv, "mode", None) == "rsag" else "1 RCCL all-reduce"))},
-        "roofline": roof,
-        "rel_residual": {"x": (ex2 / x2) ** 0.5 if x2 > 0 else None, "y": (ey2 / y2) ** 0.5 if y2 > 0 else None,
-                         "note": "rank-0 shard, after warmup+steps iterations"},
     }
+    if args.full:
+        out["roofline"] = roofline(w, args, world, r0, r1, kp, classes, other, rh_samples, extra, t_extra, bf16x6)
+        out["rel_residual"] = {"x": (ex2 / x2) ** 0.5 if x2 > 0 else None, "y": (ey2 / y2) ** 0.5 if y2 > 0 else None,
+                               "note": "rank-0 shard, after warmup+steps iterations"}
     out["series_ms"] = {"per_iteration": [round(v, 4) for v in series_ms],
                         "note": "HIP events on the launch stream of rank 0, one per iteration inside the timed region"}
     if use_dist:
@@ -720,7 +763,7 @@ def main():
         out["note"] = ("fp32 MFMA arithmetic (the default).  Opt-in --option gemm_arith=1 (fp32 operands split exactly into three "
                        "bf16 planes, six products on the bf16 matrix pipe, fp32-equivalent to 4e-7): 23.3-24.0 it/s, "
                        "profiles/r01_c4_n1_bench_bf16x6.json, DESIGN.md section 4")
-    if newton:
+    if args.full and newton:
         st = ctx.newton_clamp_stats(full=True)
         out["conditioning"] = {"clamped_rows_float32": st[0], "max_ratio_left_in_float32": st[1], "rows_refined_in_float64": st[2],
                                "max_condition_estimate_plain_solves": st[3],
@@ -728,7 +771,7 @@ def main():
                                "note": "per-row sweeps since the context was created (cmf_newton_clamp_stats): rows whose float32 Hessian "
                                        "went through the spectral clamp, largest ||H||_F / pert left in float32, rows redone in float64, "
                                        "largest max H_ii / min L_ii^2 over all plain Cholesky solves"}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(w)
         full = w["solver"] == "mu"
         per_row = bool(cb.get("per_row"))
@@ -753,15 +796,16 @@ def main():
                           "reference-order flop" if full else "algorithmic-work", cb["ratio"])),
         }
     if newton:
-        out["steady_state"] = {"extra_warmup_iterations": warm_extra, "instrumented_over_timed": t_extra / ms_per_step if ms_per_step > 0 else None,
+        out["steady_state"] = {"extra_warmup_iterations": warm_extra,
+                               "instrumented_over_timed": t_extra / ms_per_step if args.full and ms_per_step > 0 else None,
                                "warmup_series_ms": [round(x, 1) for x in warm_ms] if warm_extra else [],
                                "note": "warm-up continued until three consecutive iterations recorded the same clamp / refinement counts and took "
                                        "the same time to 3 % (at least 16 iterations in all; warmup_series_ms: their wall clock, host-synchronised); the "
-                                       "iterations after the timed region (instrumented_ms_per_step) must not cost more than 1.25 x the timed "
-                                       "ones, else the line is refused (exit code 3)"}
+                                       "iterations after the timed region (instrumented_ms_per_step, --full only) must not cost more than 1.25 x "
+                                       "the timed ones, else the line is refused (exit code 3)"}
     sys.stdout.flush()
     print(json.dumps(out), flush=True)
-    if newton and ms_per_step > 0 and t_extra > 1.25 * ms_per_step and extra > 0 and not w.get("may_diverge"):
+    if args.full and newton and ms_per_step > 0 and t_extra > 1.25 * ms_per_step and extra > 0 and not w.get("may_diverge"):
         sys.stderr.write("bench.py: NOT a steady-state line: the %d iterations after the timed region took %.1f ms each against %.1f ms "
                          "inside it (a regime change of the solver behind the timed window); raise --warmup / --max-warmup\n"
                          % (extra, t_extra, ms_per_step))

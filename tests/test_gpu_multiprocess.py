@@ -160,7 +160,7 @@ def test_bench_launches_its_own_ranks(workload):
     starts the two rank processes itself (before any GPU call in the parent) and prints rank 0's JSON line.  The test
     box has one GPU, so both ranks share it and the host-staged test double stands in for RCCL (which refuses two ranks on
     one device)."""
-    out = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload, "--no-cpu-baseline", "--mu-collective", "rsag"],
+    out = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload, "--full", "--no-cpu-baseline", "--mu-collective", "rsag"],
                      {"CMF_BENCH_SAME_DEVICE": "1", "CMF_COMM_BACKEND": "host", "CMF_COMM_TIMEOUT": "120"})
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["value"] > 0
     assert len(out["series_ms"]["per_iteration"]) == 3
@@ -178,7 +178,7 @@ def test_bench_launches_its_own_ranks(workload):
         assert coll["replicas"]["identical"], coll["replicas"]     # every rank ends with the same V, bit for bit
     # (--max-warmup 0: the single-GPU per-row Newton line would otherwise warm up to its steady state, and the two runs would no
     # longer be the same iterations)
-    one = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", workload, "--no-cpu-baseline", "--max-warmup", "0"], {})
+    one = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", workload, "--full", "--no-cpu-baseline", "--max-warmup", "0"], {})
     assert one["n_gpus"] == 1 and "collective" not in one
     # same synthetic problem, same iteration count: the sharded run ends at the same residuals (rank 0's shard of X / Y
     # for the sharded run, so compare loosely: both are far from the starting residual and close to each other)
@@ -186,19 +186,35 @@ def test_bench_launches_its_own_ranks(workload):
         assert np.isfinite(one["rel_residual"][key]) and abs(out["rel_residual"][key] - one["rel_residual"][key]) < 0.05 * one["rel_residual"][key]
 
 
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain bench run times exactly --steps steps and prints the headline only (no roofline, residuals or CPU baseline: --full's);
+    --dump-outputs writes the factors the last timed step left, bit-identical between a plain and a --full run of the same arguments."""
+    base = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny"]
+    plain = _run_bench(base + ["--dump-outputs", str(tmp_path / "plain")], {})
+    assert plain["steps"] == 3 and len(plain["series_ms"]["per_iteration"]) == 3 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert not {"roofline", "rel_residual", "cpu_baseline"} & set(plain), sorted(plain)
+    full = _run_bench(base + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")], {})
+    assert "roofline" in full and np.isfinite(full["rel_residual"]["x"])
+    for name, n in (("U", 2048), ("V", 1024), ("Z", 512)):
+        a = np.load(str(tmp_path / "plain" / (name + ".npy")))
+        assert a.dtype == np.float32 and a.shape == (n, 64) and np.isfinite(a).all()
+        np.testing.assert_array_equal(np.load(str(tmp_path / "plain" / (name + "_rows.npy"))), np.arange(n))
+        np.testing.assert_array_equal(a, np.load(str(tmp_path / "full" / (name + ".npy"))))
+
+
 def test_bench_rccl_single_rank():
     """The RCCL branch of bench.py with one rank (all a 1-GPU box can offer RCCL): unique id through the job file,
     ncclCommInitRank inside libcmfhip, the all-reduce of the (d + k) k partial buffer on the context's stream, teardown."""
-    out = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--no-cpu-baseline", "--mu-collective", "allreduce"],
+    out = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--full", "--no-cpu-baseline", "--mu-collective", "allreduce"],
                      {"CMF_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1"})
     assert out["collective"]["backend"] == "rccl" and out["collective"]["calls_per_iteration"] == 1
     assert out["collective"]["ranks_seen"] == 1 and out["collective"]["rank_seen"] == 0     # ncclCommCount / ncclCommUserRank
     assert out["collective"]["payload_bytes_per_iteration"] == (1024 + 64) * 64 * 4
-    ref = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--no-cpu-baseline"], {})
+    ref = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--full", "--no-cpu-baseline"], {})
     assert out["rel_residual"] == ref["rel_residual"]      # a 1-rank all-reduce is the identity: bit-identical iterates
     # the row-blocked protocol: ncclReduceScatter and ncclAllGather in place (one rank: both the identity), each in ONE RCCL group
     # (ncclGroupStart / ncclGroupEnd) with its k^2 all-reduce: four calls, two launch points
-    out = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--no-cpu-baseline", "--mu-collective", "rsag"],
+    out = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--full", "--no-cpu-baseline", "--mu-collective", "rsag"],
                      {"CMF_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1"})
     coll = out["collective"]
     assert coll["protocol"] == "rsag" and coll["calls_per_iteration"] == 4 and coll["replicas"]["identical"]
@@ -209,7 +225,7 @@ def test_bench_rccl_single_rank():
         assert abs(out["rel_residual"][key] - ref["rel_residual"][key]) <= 1e-5 * ref["rel_residual"][key]
     # the default: both protocols timed on the live communicator before the warm-up, the decision and both timings in the line; the
     # trial restores the factors, so the iterates are those of the run without it
-    out = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--no-cpu-baseline"],
+    out = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--full", "--no-cpu-baseline"],
                      {"CMF_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1"})
     coll = out["collective"]
     trial = coll["protocol_trial"]
@@ -221,7 +237,7 @@ def test_bench_rccl_single_rank():
     for key in ("x", "y"):
         assert abs(out["rel_residual"][key] - ref["rel_residual"][key]) <= 1e-5 * ref["rel_residual"][key]
     # linear Newton on native CSR: float64 Gram + float32 partial per iteration
-    out = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "tiny5", "--no-cpu-baseline"],
+    out = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "tiny5", "--full", "--no-cpu-baseline"],
                      {"CMF_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1"})
     assert out["collective"]["backend"] == "rccl" and out["collective"]["calls_per_iteration"] == 2
 
@@ -232,7 +248,7 @@ def test_bench_overlapped_all_reduce_in_row_blocks():
     cmf_comm_allreduce_f32_bg, cmf_comm_join).  Same payload, four calls, the same iterates up to the split-K partition of
     the smaller GEMMs; exposed + hidden time add up to the collectives' duration.  RCCL with one rank, and two ranks on the
     host-staged double."""
-    base = ["--steps", "3", "--warmup", "1", "--workload", "tiny", "--no-cpu-baseline"]
+    base = ["--steps", "3", "--warmup", "1", "--workload", "tiny", "--full", "--no-cpu-baseline"]
     env = {"CMF_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1"}
     serial = _run_bench(["--gpus", "1", "--mu-collective", "allreduce"] + base, env)
     over = _run_bench(["--gpus", "1", "--overlap-chunks", "4"] + base, env)
@@ -311,7 +327,7 @@ def test_dress_rehearsal_eight_ranks_match_one(tmp_path, mode):
     sharing the device, host-staged collectives, workload c4q (k = 256, 16384^3: the shard shapes of C4 / 8 scaled by four -- 2048-row
     blocks of U, Z and of the row-blocked V update, i.e. the column-tiled fused updates).  After two iterations every rank holds the
     same V, and 16 fixed rows of each of U, V, Z equal the single-GPU run's to 1e-5 of the factor's largest entry."""
-    base = ["--steps", "2", "--warmup", "0", "--workload", "c4q", "--no-cpu-baseline"]
+    base = ["--steps", "2", "--warmup", "0", "--workload", "c4q", "--full", "--no-cpu-baseline"]
     one = _run_bench(["--gpus", "1", "--dump-rows", str(tmp_path / "one")] + base, {})
     eight = _run_bench(["--gpus", "8", "--mu-collective", mode, "--dump-rows", str(tmp_path / "eight")] + base,
                        {"CMF_BENCH_SAME_DEVICE": "1", "CMF_COMM_BACKEND": "host", "CMF_COMM_TIMEOUT": "300"})
@@ -330,7 +346,7 @@ def test_dress_rehearsal_two_and_four_ranks_with_the_default_protocol_trial(tmp_
     """the rehearsal at the OTHER rank counts the driver's scaling run takes (N = 2, 4), through the DEFAULT
     protocol selection -- the timed trial on the live ranks, whose cost is in the line (`protocol_trial.seconds`) -- on one GPU with the
     host-staged collectives: replicas identical, 16 rows of each factor equal to the single-GPU run's to 1e-5 of the largest entry."""
-    base = ["--steps", "2", "--warmup", "0", "--workload", "c4q", "--no-cpu-baseline"]
+    base = ["--steps", "2", "--warmup", "0", "--workload", "c4q", "--full", "--no-cpu-baseline"]
     one = _run_bench(["--gpus", "1", "--dump-rows", str(tmp_path / "one")] + base, {})
     many = _run_bench(["--gpus", str(world), "--dump-rows", str(tmp_path / "many")] + base,
                       {"CMF_BENCH_SAME_DEVICE": "1", "CMF_COMM_BACKEND": "host", "CMF_COMM_TIMEOUT": "300"})
@@ -430,7 +446,7 @@ def test_real_rccl_two_gpus(workload, extra):
     from pycmf_amd import _lib
     if _lib.device_count() < 2:
         pytest.skip("needs two GPUs (RCCL refuses two ranks on one device)")
-    base = ["--steps", "3", "--warmup", "1", "--workload", workload, "--no-cpu-baseline"]
+    base = ["--steps", "3", "--warmup", "1", "--workload", workload, "--full", "--no-cpu-baseline"]
     two = _run_bench(["--gpus", "2"] + base + extra, {"MASTER_ADDR": "127.0.0.1"})
     one = _run_bench(["--gpus", "1"] + base, {})
     coll = two["collective"]
@@ -517,7 +533,7 @@ def test_bench_under_torch_distributed_run():
         env.pop(k, None)
     q = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--workload", "tiny", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "--workload", "tiny", "--full", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert q.returncode == 0, q.stderr.decode()[-3000:]
     lines = [ln for ln in q.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line expected from rank 0, got %d" % len(lines)
@@ -540,7 +556,7 @@ def test_bench_under_torch_distributed_run_with_real_rccl_one_rank():
         env.pop(k, None)
     q = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--workload", "tiny", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "--workload", "tiny", "--full", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert q.returncode == 0, q.stderr.decode()[-3000:]
     lines = [ln for ln in q.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1

@@ -647,6 +647,39 @@ def test_product_and_bench_never_import_torch():
         assert not re.search(r"^\s*(import torch|from torch)", src, re.M), f
 
 
+def test_bench_dump_outputs_writes_whole_or_sampled_factors(tmp_path):
+    """bench.py --dump-outputs: float32 factors and float64 row indices; a factor over the byte cap becomes a fixed, sorted sample of
+    its rows (the same rows in every run), and the three factors of the headline shape stay under 64 MB."""
+    import bench
+
+    class Ctx:
+        def __init__(self, shape):
+            self.shape = shape
+
+        def get_factor(self, which):
+            n, k = self.shape[which], self.shape[3]
+            return np.arange(n * k, dtype=np.float64).reshape(n, k)
+
+    small = (300, 200, 100, 8)
+    bench.dump_outputs(Ctx(small), str(tmp_path / "small"))
+    for name, which in (("U", 0), ("V", 1), ("Z", 2)):
+        a, rows = np.load(str(tmp_path / "small" / (name + ".npy"))), np.load(str(tmp_path / "small" / (name + "_rows.npy")))
+        assert a.dtype == np.float32 and rows.dtype == np.float64
+        np.testing.assert_array_equal(rows, np.arange(small[which]))
+        np.testing.assert_array_equal(a, Ctx(small).get_factor(which))
+    c4 = (65536, 65536, 65536, 256)
+    for run in ("a", "b"):
+        bench.dump_outputs(Ctx(c4), str(tmp_path / run))
+    total = 0
+    for name in ("U", "V", "Z"):
+        a, rows = np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "a" / (name + "_rows.npy")))
+        assert 0 < len(rows) < c4[0] and np.all(np.diff(rows) > 0) and a.shape == (len(rows), 256)
+        np.testing.assert_array_equal(a, Ctx(c4).get_factor(0)[rows.astype(np.int64)])
+        np.testing.assert_array_equal(rows, np.load(str(tmp_path / "b" / (name + "_rows.npy"))))
+        total += a.nbytes + rows.nbytes
+    assert total <= 64 << 20
+
+
 def test_partition_routes_linear_newton_to_north_stars_layout():
     """Newton with linear links and no sampling shares MU's partition (nnz-balanced CSR row blocks, V replicated, one large
     all-reduce); any other Newton configuration takes equal blocks of all three factors (three all-gathers)."""

@@ -8,7 +8,7 @@ O=$R/gpurun_out/r06
 mkdir -p "$O"
 cd "$R"
 MODE=${1:-all}
-B="timeout 600 python3 bench.py"
+B="timeout 600 python3 bench.py --full"
 $B --steps 20 --warmup 5 > $O/c4.json 2> $O/c4.err < /dev/null
 $B --steps 40 --warmup 5 --tol 1e-4 --no-cpu-baseline > $O/c4_tol.json 2> $O/c4_tol.err < /dev/null
 $B --steps 40 --warmup 5 --no-cpu-baseline > $O/c4_notol40.json 2> $O/c4_notol40.err < /dev/null
@@ -30,14 +30,14 @@ if [ "$MODE" = "lines" ]; then exit 0; fi
 cd /tmp && export TMPDIR=/tmp
 for W in c4 c2 c3 c3x c5; do
   case $W in c4) A="--steps 10 --warmup 3";; c2) A="--workload c2 --steps 20 --warmup 5";; c3) A="--workload c3 --steps 3 --warmup 3";; c3x) A="--workload c3x --steps 3 --warmup 3";; c5) A="--workload c5 --steps 5 --warmup 2";; esac
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$W -o $W -- python3 $R/bench.py $A --no-cpu-baseline > $O/prof_$W.log 2>&1 < /dev/null
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$W -o $W -- python3 $R/bench.py $A --full --no-cpu-baseline > $O/prof_$W.log 2>&1 < /dev/null
 done
 for W in c4 c3 c3x c5 c5z c5zs; do
   case $W in c4) A="--steps 2 --warmup 1";; c3) A="--workload c3 --steps 1 --warmup 1";; c3x) A="--workload c3x --steps 1 --warmup 1 --max-warmup 0";; c5) A="--workload c5 --steps 2 --warmup 1";; c5z) A="--workload c5z --steps 2 --warmup 1";; c5zs) A="--workload c5zs --steps 2 --warmup 1";; esac
-  timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_${W}_fetch -o f -- python3 $R/bench.py $A --no-cpu-baseline > $O/pmc_${W}f.log 2>&1 < /dev/null
-  timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_${W}_write -o w -- python3 $R/bench.py $A --no-cpu-baseline > $O/pmc_${W}w.log 2>&1 < /dev/null
+  timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_${W}_fetch -o f -- python3 $R/bench.py $A --full --no-cpu-baseline > $O/pmc_${W}f.log 2>&1 < /dev/null
+  timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_${W}_write -o w -- python3 $R/bench.py $A --full --no-cpu-baseline > $O/pmc_${W}w.log 2>&1 < /dev/null
 done
-timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma_c4 -o m -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/pmc_m4.log 2>&1 < /dev/null
+timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma_c4 -o m -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $O/pmc_m4.log 2>&1 < /dev/null
 cd $R
 find $O -name "*_kernel_trace.csv" -delete
 for f in $(find $O -name "*counter_collection.csv"); do

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/r06
 mkdir -p "$O"
 cd "$R"
-B="timeout 600 python3 bench.py"
+B="timeout 600 python3 bench.py --full"
 $B --workload c3 --steps 5 --warmup 3 > $O/c3.json 2> $O/c3.err < /dev/null
 $B --workload c3 --steps 5 --warmup 3 --no-cpu-baseline --option refine_rows=0 > $O/c3_norefine.json 2> $O/c3_norefine.err < /dev/null
 $B --workload c3 --steps 5 --warmup 3 --no-cpu-baseline --option eig_clamp=0 --option refine_rows_tol_ppm=0 > $O/c3_r05_clamp.json 2> $O/c3_r05_clamp.err < /dev/null
@@ -21,17 +21,17 @@ $B --workload c3x --steps 5 --warmup 3 --no-cpu-baseline --option row_symmetric=
 cd /tmp && export TMPDIR=/tmp
 for W in c3 c3x; do
   A="--workload $W --steps 3 --warmup 3"
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$W -o $W -- python3 $R/bench.py $A --no-cpu-baseline > $O/prof_$W.log 2>&1 < /dev/null
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$W -o $W -- python3 $R/bench.py $A --full --no-cpu-baseline > $O/prof_$W.log 2>&1 < /dev/null
 done
 for W in c3 c3x; do
   A="--workload $W --steps 1 --warmup 1"
   if [ $W = c3x ]; then A="$A --max-warmup 0"; fi
-  timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_${W}_fetch -o f -- python3 $R/bench.py $A --no-cpu-baseline > $O/pmc_${W}f.log 2>&1 < /dev/null
-  timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_${W}_write -o w -- python3 $R/bench.py $A --no-cpu-baseline > $O/pmc_${W}w.log 2>&1 < /dev/null
-  timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma_$W -o m -- python3 $R/bench.py $A --no-cpu-baseline > $O/pmc_m_$W.log 2>&1 < /dev/null
+  timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_${W}_fetch -o f -- python3 $R/bench.py $A --full --no-cpu-baseline > $O/pmc_${W}f.log 2>&1 < /dev/null
+  timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_${W}_write -o w -- python3 $R/bench.py $A --full --no-cpu-baseline > $O/pmc_${W}w.log 2>&1 < /dev/null
+  timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma_$W -o m -- python3 $R/bench.py $A --full --no-cpu-baseline > $O/pmc_m_$W.log 2>&1 < /dev/null
 done
-timeout 900 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY --output-format csv -d $O/pmc_lds_c3x -o l -- python3 $R/bench.py --workload c3x --steps 1 --warmup 1 --max-warmup 0 --no-cpu-baseline > $O/pmc_l_c3x.log 2>&1 < /dev/null
-timeout 900 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY --output-format csv -d $O/pmc_lds_c3x_sym3 -o l -- python3 $R/bench.py --workload c3x --steps 1 --warmup 1 --max-warmup 0 --no-cpu-baseline --option row_symmetric=3 > $O/pmc_l_c3x_sym3.log 2>&1 < /dev/null
+timeout 900 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY --output-format csv -d $O/pmc_lds_c3x -o l -- python3 $R/bench.py --workload c3x --steps 1 --warmup 1 --max-warmup 0 --full --no-cpu-baseline > $O/pmc_l_c3x.log 2>&1 < /dev/null
+timeout 900 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY --output-format csv -d $O/pmc_lds_c3x_sym3 -o l -- python3 $R/bench.py --workload c3x --steps 1 --warmup 1 --max-warmup 0 --full --no-cpu-baseline --option row_symmetric=3 > $O/pmc_l_c3x_sym3.log 2>&1 < /dev/null
 cd $R
 find $O -name "*_kernel_trace.csv" -delete
 for f in $(find $O -name "*counter_collection.csv"); do
