@@ -58,7 +58,8 @@ enum {
     CMF_K_SPMM = 6,      /* native CSR: A F, A^T F, sum_nnz a_ij (l_i . r_j)  */
     CMF_K_ROWHESS = 7,   /* fused per-row gradient + Hessian over the sampled rows */
     CMF_K_GEMM_PAIR = 8, /* k_pad = 128: the two data passes of an MU half-iteration as one balanced launch (X^T U with Y Z, X V with Y^T V) */
-    CMF_K_COUNT = 9
+    CMF_K_TOPK = 9,      /* prediction: top-n of f(Q B^T), scores on the fp32 matrix pipe + per-row selection + merge; flops 2 nq C k */
+    CMF_K_COUNT = 10
 };
 
 const char *cmf_last_error(void);
@@ -101,7 +102,9 @@ int cmf_sync(cmf_ctx *ctx);
  * "direct_newton_step" 1 (default) | 0: linear shared-Hessian sweeps with l1 = 0 whose inverse is the plain one (k > 64)
  * update F <- clamp(s (T O) H^-1) in one product | form the gradient and subtract the step,
  * "row_certificates" 1 (default) | 0: half such a group shares one threshold test of _safe_invert (cmf_solvers.py:346-356)
- * through the positive semi-definite part of their Hessians the rows have in common | every row runs its own         */
+ * through the positive semi-definite part of their Hessians the rows have in common | every row runs its own,
+ * "topk_split" n: cmf_topk / cmf_topk_queries cut the candidates into n shares (<= 0, default: as many as fill the chip); the
+ * result does not depend on it                                                                                        */
 int cmf_set_option(cmf_ctx *ctx, const char *name, int64_t value);
 
 /* ---- problem ---------------------------------------------------------- */
@@ -249,6 +252,37 @@ int cmf_newton_v_finish(cmf_ctx *ctx, float *dev_pbuf, double l1, int nn_mask);
  *   *ex2 = ||X - f(U V^T)||^2, *ey2 = ||Y - f(V Z^T)||^2                    */
 int cmf_residual_sq(cmf_ctx *ctx, int x_link, int y_link, double *ex2, double *ey2);
 int cmf_data_sq(cmf_ctx *ctx, double *x2, double *y2);  /* ||X||^2, ||Y||^2 */
+
+/* ---- prediction: the n best entries per row / column of X^ = f(U V^T), Y^ = f(V Z^T) ----------------------------------------
+ * What a user of a fitted model asks next: for this row, which columns does the model score highest?  The reference stops at the
+ * three factor arrays; its only consumer of them is the host argsort of pycmf/analysis.py:3-16 (top terms of a topic), and a user
+ * writes np.argpartition(U @ V.T, ...).  Here the product is never materialised: scores are formed tile by tile on the fp32 matrix
+ * pipe from the float32 factor blocks the context holds, every query keeps its n best in on-chip memory, and nq x n pairs leave
+ * the device (csrc/cmf_topk.hip.h).
+ *   cmf_topk: queries = rows `rows[0 .. nq)` of factor `query` (may repeat; rows == NULL: all its rows, nq ignored), candidates =
+ *   all rows of factor `cand`.  (query, cand) = (U, V): per row of X^ its best columns; (V, U): per column of X^ its best rows;
+ *   (V, Z) / (Z, V): the same of Y^.  Any other pair is CMF_EINVAL.
+ *   cmf_topk_queries: the same with caller-supplied query vectors (host float64, nq x k, element (i, t) at Q[i * rs + t * cs] as in
+ *   cmf_set_factor_f64): rows folded in by a transform, or the k unit vectors (the top rows of a factor's COLUMNS).  Any `cand`.
+ * Result (host, nq x n, row-major): idx[i][t] = the candidate with the t-th largest f(q_i . F[cand]_j), val[i][t] = that value;
+ * link = CMF_LINK_LINEAR | CMF_LINK_LOGIT (f = sigmoid; monotone, so the selection runs on the raw score).  The order is total:
+ * larger raw float32 score first, equal scores: smaller j first (-0 = +0; a NaN score is never selected).  Every score is one
+ * float32 fma chain in a fixed k order, so a query's result is bit-identical when the call is repeated, whichever other queries
+ * are in the call and however the candidates are split over workgroups.
+ * Exclusion (nullable, both or neither): host CSR over the nq queries -- query i skips the candidates
+ * excl_indices[excl_indptr[i] .. excl_indptr[i + 1]), strictly ascending and inside [0, candidates) (checked, CMF_EINVAL).  A query
+ * with fewer than n candidates left gets idx = -1, val = -inf in the remaining places.
+ * 1 <= n <= min(CMF_TOPK_MAX_N, candidates), otherwise CMF_EINVAL (no truncation).  Needs cmf_set_problem and the factors, no data;
+ * modifies no factor, data, option, captured graph or RNG state.  n_components <= 256 (k_pad <= 256).  One GPU: the sharded form
+ * (candidates cut over ranks, lists merged) is not built.
+ * cmf_topk_layout: how such a call is laid out -- out4 = { queries per workgroup, candidate shares S, queries per launch,
+ * device scratch bytes } for nq queries against factor `cand` (excl_nnz < 0: no exclusion lists; own_queries: cmf_topk_queries). */
+#define CMF_TOPK_MAX_N 128
+int cmf_topk(cmf_ctx *ctx, int query, int cand, int link, const int64_t *rows, int64_t nq, int n,
+             const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *idx, float *val);
+int cmf_topk_queries(cmf_ctx *ctx, const double *Q, int64_t rs, int64_t cs, int64_t nq, int cand, int link, int n,
+                     const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *idx, float *val);
+int cmf_topk_layout(cmf_ctx *ctx, int64_t nq, int cand, int n, int64_t excl_nnz, int own_queries, int64_t *out4);
 
 /* ---- batched safe inverse (exposed for tests): _safe_invert :346-356 --- */
 /* H: n symmetric k x k float64 matrices (host), out: Q diag(1/max(|l|,pert)) Q^T */

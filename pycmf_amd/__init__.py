@@ -3,7 +3,7 @@
 The public names are resolved on first use (PEP 562): ``from pycmf_amd import _lib`` -- what bench.py and the sharded
 drivers need -- then imports NumPy only, not scikit-learn / SciPy / pandas behind the estimator."""
 
-__all__ = ["CMF", "collective_matrix_factorization", "HipMUSolver", "HipNewtonSolver"]
+__all__ = ["CMF", "collective_matrix_factorization", "HipMUSolver", "HipNewtonSolver", "top_n_products"]
 
 
 def __getattr__(name):
@@ -13,6 +13,9 @@ def __getattr__(name):
     if name in ("HipMUSolver", "HipNewtonSolver"):
         from . import solver_shell
         return getattr(solver_shell, name)
+    if name == "top_n_products":
+        from . import prediction
+        return prediction.top_n_products
     raise AttributeError("module 'pycmf_amd' has no attribute %r" % name)
 
 

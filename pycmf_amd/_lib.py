@@ -17,7 +17,7 @@ CMF_NN_U, CMF_NN_V, CMF_NN_Z = 1, 2, 4      # nn_mask bits
 LINKS = {"linear": 0, "logit": 1}
 UPD_U, UPD_V, UPD_Z = 1, 2, 4
 K_GEMM_NN, K_GEMM_TN, K_GEMM_NT, K_ELEMWISE, K_EIGEN = 0, 1, 2, 3, 4
-KERNEL_CLASSES = {"gemm_nn": 0, "gemm_tn": 1, "gemm_nt": 2, "elementwise": 3, "eigen": 4, "gemm_small": 5, "spmm": 6, "rowhess": 7, "gemm_pair": 8}
+KERNEL_CLASSES = {"gemm_nn": 0, "gemm_tn": 1, "gemm_nt": 2, "elementwise": 3, "eigen": 4, "gemm_small": 5, "spmm": 6, "rowhess": 7, "gemm_pair": 8, "topk": 9}
 
 _ERR = {1: ValueError, 2: RuntimeError, 3: MemoryError, 4: RuntimeError, 5: NotImplementedError}
 
@@ -77,6 +77,9 @@ PROTOTYPES = {
     "cmf_newton_v_finish": [_vp, _vp, _dbl, _i32],
     "cmf_residual_sq": [_vp, _i32, _i32, _pd, _pd],
     "cmf_data_sq": [_vp, _pd, _pd],
+    "cmf_topk": [_vp, _i32, _i32, _i32, _pi64, _i64, _i32, _pi64, _pi32, _pi32, _pf],
+    "cmf_topk_queries": [_vp, _pd, _i64, _i64, _i64, _i32, _i32, _i32, _pi64, _pi32, _pi32, _pf],
+    "cmf_topk_layout": [_vp, _i64, _i32, _i32, _i64, _i32, _pi64],
     "cmf_safe_invert_batch": [_vp, _pd, _pd, _i32, _i32, _dbl],
     "cmf_safe_invert_f64": [_vp, _pd, _pd, _i32, _dbl],
     "cmf_safe_solve_batch": [_vp, _pd, _pd, _pd, _pd, _i32, _i32, _dbl, _i32],
@@ -536,6 +539,52 @@ class Context:
         ex, ey = C.c_double(0), C.c_double(0)
         check(self._lib.cmf_residual_sq(self._h, LINKS[x_link], LINKS[y_link], C.byref(ex), C.byref(ey)))
         return ex.value, ey.value
+
+    # ---- prediction
+    def topk(self, query, cand, n, link="linear", rows=None, exclude=None, queries=None):
+        """The n best candidates (rows of factor ``cand``) per query, by f(q . b_j): ``(idx int32[nq, n], val float32[nq, n])``,
+        best first, ties by smaller index; ``-1 / -inf`` where a query has fewer than n candidates left.  Queries: the rows
+        ``rows`` (index array; None = all) of factor ``query``, or the (nq x k) array ``queries`` (then ``query`` is ignored).
+        ``exclude``: ``(indptr int64[nq + 1], indices int32)`` -- per query a strictly ascending list of candidates to skip."""
+        xp = xi = None
+        if exclude is not None:
+            xp = np.ascontiguousarray(exclude[0], dtype=np.int64)
+            xi = np.ascontiguousarray(exclude[1], dtype=np.int32)
+        if queries is not None:
+            if rows is not None:
+                raise ValueError("rows and queries exclude each other")
+            Q = np.asarray(queries, dtype=np.float64)
+            if Q.ndim != 2 or Q.shape[1] != self.shape[3]:
+                raise ValueError("queries must be (nq, %d), got %r" % (self.shape[3], Q.shape))
+            nq = Q.shape[0]
+        elif rows is not None:
+            r = np.ascontiguousarray(rows, dtype=np.int64).ravel()
+            nq = r.size
+        else:
+            nq = self.shape[query] if query in (0, 1, 2) else 0
+        if xp is not None and xp.size != nq + 1:
+            raise ValueError("exclude: indptr must have nq + 1 = %d entries, got %d" % (nq + 1, xp.size))
+        if xp is not None and nq and (xp[-1] > xi.size):
+            raise ValueError("exclude: indptr points beyond indices")
+        idx = np.empty((nq, int(n)), dtype=np.int32)
+        val = np.empty((nq, int(n)), dtype=np.float32)
+        xpp = xp.ctypes.data_as(_pi64) if xp is not None else None
+        xip = xi.ctypes.data_as(_pi32) if xi is not None else None
+        lk = LINKS.get(link, link)
+        if queries is not None:
+            rs, cs = _strides(Q) if nq else (Q.shape[1], 1)
+            check(self._lib.cmf_topk_queries(self._h, Q.ctypes.data_as(_pd), rs, cs, nq, cand, lk, int(n), xpp, xip,
+                                             idx.ctypes.data_as(_pi32), val.ctypes.data_as(_pf)))
+        else:
+            check(self._lib.cmf_topk(self._h, query, cand, lk, r.ctypes.data_as(_pi64) if rows is not None else None, nq, int(n),
+                                     xpp, xip, idx.ctypes.data_as(_pi32), val.ctypes.data_as(_pf)))
+        return idx, val
+
+    def topk_layout(self, nq, cand, n, excl_nnz=-1, own_queries=False):
+        """(queries per workgroup, candidate shares, queries per launch, device scratch bytes) of such a call."""
+        out = (C.c_int64 * 4)()
+        check(self._lib.cmf_topk_layout(self._h, int(nq), cand, int(n), int(excl_nnz), int(bool(own_queries)), out))
+        return tuple(out)
 
     def data_sq(self):
         x2, y2 = C.c_double(0), C.c_double(0)

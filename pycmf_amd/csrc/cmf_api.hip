@@ -132,6 +132,7 @@ struct cmf_ctx {
     int opt_gemm64_tile128 = 1; // batched float64 256^3 products of the refinement on 128 x 128 tiles (gemm64_tile128_kernel); 0: 32 x 32 tiles
     int opt_nt_debug = 0;  // measurement only (tools/r05_nt_probe.py): bit 0 = the error pass without its targets
     int opt_nt_bn256 = 0;  // NT passes on 256 x 256 tiles where the column extent allows (A/B option: 39.9 ms at C4 against 39.7 for the 256 x 128 x 16 tile)
+    int opt_topk_split = 0; // top-n (cmf_topk.hip.h): force the number of candidate shares (<= 0: fill the chip); the result does not depend on it
     int opt_nt_raster = 0; // NT passes: XCD-aware tile order (blocks of 4 x 8 tiles per XCD; gemm_kernel) -- measured no gain at C4 (40.9 against 40.6 ms): the operands beyond L2 are not the bound
     int opt_nt_tile16 = 1; // 256 x 128 NT passes on the 16-deep K-step (two workgroups per CU) instead of 32-deep (one): 39.6 against 40.7 ms at C4
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
@@ -1017,6 +1018,8 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
         c->opt_spmm_stretch = std::max<int64_t>(0, value);
     } else if (!strcmp(name, "spmm_block_cols")) {
         c->opt_spmm_block_cols = std::max<int64_t>(0, value);
+    } else if (!strcmp(name, "topk_split")) {
+        c->opt_topk_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "sparse_mode")) {
         if (value < 0 || value > 2) return fail(CMF_EINVAL, "sparse_mode must be 0 (auto), 1 (dense) or 2 (native CSR)");
         c->opt_sparse = (int)value;
@@ -1948,3 +1951,5 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_newton.hip.h"
 #include "cmf_init.hip.h"
 #include "cmf_comm.hip.h"
+#define CMF_TOPK_HOST
+#include "cmf_topk.hip.h"

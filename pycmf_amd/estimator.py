@@ -281,6 +281,22 @@ class CMF(BaseEstimator, TransformerMixin):
             update_U=update_U, update_V=False, update_Z=update_Z, **self._kwargs())
         return U, V, Z
 
+    def top_n(self, relation="x", axis=0, rows=None, n=10, exclude=None, queries=None):
+        """The ``n`` highest entries per row (``axis=0``) or per column (``axis=1``) of the fitted reconstruction of
+        ``relation`` -- 'x': f(U V^T), 'y': f(V Z^T), f the estimator's own ``x_link`` / ``y_link`` -- as
+        ``(idx int32[nq, n], val float32[nq, n])``, best first, equal scores by smaller index.  The product is never formed: scores
+        and selection run on GPU ``self.device`` (one GPU whatever ``n_gpus``; float32, pycmf_amd/csrc/cmf_topk.hip.h).
+
+        ``rows``: index array of the rows (columns for ``axis=1``) to answer for, ``None`` = all.  ``exclude``: a SciPy sparse
+        matrix of the relation's shape whose stored entries are skipped (pass the training ``X``: what a user has already seen);
+        a row with fewer than n candidates left has ``-1 / -inf`` in the remaining places.  ``queries``: an (nq x k) array used
+        instead of the fitted rows -- the ``U`` that ``transform`` returned for new rows; ``exclude`` then has nq rows (columns
+        for ``axis=1``).  ``rows`` together with ``queries`` is a ``ValueError``."""
+        assert hasattr(self, "components")
+        from .prediction import model_top_n
+        return model_top_n(self.x_weights, self.components, self.y_weights, self.x_link, self.y_link, self.device,
+                           relation=relation, axis=axis, rows=rows, n=n, exclude=exclude, queries=queries)
+
     def print_topic_terms(self, vectorizer, topn_words=10, importances=True):
         """Print the top terms per topic (cmf.py:749-776); works with both the old
         ``get_feature_names`` and the current ``get_feature_names_out`` vectorizer API."""

@@ -1,0 +1,126 @@
+"""Top-n prediction from fitted factors: for every query row the n candidates with the largest f(q . b_j), computed on the device
+without ever forming the product (csrc/cmf_topk.hip.h through ``Context.topk``).
+
+The reference has no counterpart: it returns the three factor arrays and its only consumer of them is the host argsort of
+pycmf/analysis.py:3-16.  Everything here that can fail on its arguments fails BEFORE a device is touched.
+"""
+import numpy as np
+
+from . import _lib
+
+TOPK_MAX_N = 128   # CMF_TOPK_MAX_N of include/cmfhip.h
+
+# relation, axis -> (query factor, candidate factor): X ~ f(U V^T), Y ~ f(V Z^T)
+_PAIRS = {("x", 0): (_lib.CMF_U, _lib.CMF_V), ("x", 1): (_lib.CMF_V, _lib.CMF_U),
+          ("y", 0): (_lib.CMF_V, _lib.CMF_Z), ("y", 1): (_lib.CMF_Z, _lib.CMF_V)}
+
+
+def exclusion_lists(exclude, shape, rows=None, transpose=False):
+    """CSR pair ``(indptr int64[nq + 1], indices int32)`` of the entries to skip: row i lists, strictly ascending, the columns that
+    ``exclude`` stores in row ``rows[i]`` (``rows=None``: every row).  ``exclude`` is a SciPy sparse matrix or a dense array (its
+    non-zeros count) of shape ``shape`` -- of ``shape[::-1]`` when ``transpose`` (a relation queried along axis 1).  Explicitly
+    stored zeros of a sparse matrix are skipped entries too: what is stored was seen."""
+    import scipy.sparse as sp
+    want = tuple(shape[::-1]) if transpose else tuple(shape)
+    if not sp.issparse(exclude):
+        exclude = np.asarray(exclude)
+        if exclude.ndim != 2:
+            raise ValueError("exclude must be a 2-d matrix of shape %r, got %d dimension(s)" % (want, exclude.ndim))
+    if tuple(exclude.shape) != want:
+        raise ValueError("exclude must have shape %r, got %r" % (want, tuple(exclude.shape)))
+    if shape[1] > np.iinfo(np.int32).max:
+        raise ValueError("exclude: %d candidates do not fit int32 indices" % shape[1])
+    M = sp.csr_matrix(exclude.T if transpose else exclude)
+    M = M[np.asarray(rows, dtype=np.int64)] if rows is not None else M.copy()   # never the caller's own arrays
+    M.sum_duplicates()        # sorts the column indices of every row and merges repeated ones
+    return np.asarray(M.indptr, dtype=np.int64), np.asarray(M.indices, dtype=np.int32)
+
+
+def _check_n(n, ncand):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        raise ValueError("n must be an integer, got %r" % (n,))
+    if n < 1:
+        raise ValueError("n must be at least 1, got %d" % n)
+    if n > TOPK_MAX_N:
+        raise ValueError("n = %d exceeds the supported maximum %d" % (n, TOPK_MAX_N))
+    if n > ncand:
+        raise ValueError("n = %d exceeds the %d candidates" % (n, ncand))
+    return int(n)
+
+
+def _check_link(link):
+    if link not in _lib.LINKS:
+        raise ValueError("No such link %s" % (link,))
+    return link
+
+
+def _check_queries(queries, k):
+    Q = np.asarray(queries, dtype=np.float64)
+    if Q.ndim != 2 or Q.shape[1] != k:
+        raise ValueError("queries must be an (nq, %d) array, got shape %r" % (k, Q.shape))
+    return Q
+
+
+def _check_rows(rows, nrows):
+    r = np.asarray(rows)
+    if r.ndim != 1 or (r.size and not np.issubdtype(r.dtype, np.integer)):
+        raise ValueError("rows must be a 1-d integer index array")
+    r = r.astype(np.int64)
+    if r.size and (r.min() < 0 or r.max() >= nrows):
+        raise ValueError("rows must lie in [0, %d)" % nrows)
+    return r
+
+
+def top_n_products(A, B, n, link="linear", exclude=None, device=0):
+    """For every row a_i of ``A`` (nq x k) the ``n`` rows b_j of ``B`` (C x k) with the largest ``f(a_i . b_j)``:
+    ``(idx int32[nq, n], val float32[nq, n])``, best first, equal scores by smaller j.  ``link``: 'linear' | 'logit' (sigmoid).
+    ``exclude``: (nq x C) sparse or dense matrix whose stored / non-zero entries are skipped; a row with fewer than n candidates
+    left has ``-1 / -inf`` in the remaining places.  Float32 arithmetic on GPU ``device``; the nq x C product is never formed."""
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim != 2 or B.shape[0] < 1 or B.shape[1] < 1:
+        raise ValueError("B must be a non-empty (C, k) array, got shape %r" % (B.shape,))
+    A = _check_queries(A, B.shape[1])
+    n = _check_n(n, B.shape[0])
+    _check_link(link)
+    excl = None if exclude is None else exclusion_lists(exclude, (A.shape[0], B.shape[0]))
+    ctx = _lib.Context(device)
+    try:
+        ctx.set_problem(1, B.shape[0], 1, B.shape[1])
+        ctx.set_factor(_lib.CMF_V, B)
+        return ctx.topk(_lib.CMF_U, _lib.CMF_V, n, link=link, exclude=excl, queries=A)
+    finally:
+        ctx.close()
+
+
+def model_top_n(U, V, Z, x_link, y_link, device, relation="x", axis=0, rows=None, n=10, exclude=None, queries=None):
+    """``CMF.top_n`` on explicit factors (see there)."""
+    if relation not in ("x", "y"):
+        raise ValueError("relation must be 'x' or 'y', got %r" % (relation,))
+    if axis not in (0, 1):
+        raise ValueError("axis must be 0 or 1, got %r" % (axis,))
+    if rows is not None and queries is not None:
+        raise ValueError("rows and queries exclude each other: queries replace the fitted rows")
+    factors = (U, V, Z)
+    qf, cf = _PAIRS[(relation, axis)]
+    ncand, k = factors[cf].shape
+    n = _check_n(n, ncand)
+    link = _check_link(x_link if relation == "x" else y_link)
+    if queries is not None:
+        queries = _check_queries(queries, k)
+        nrows = queries.shape[0]
+    else:
+        nrows = factors[qf].shape[0]
+        if rows is not None:
+            rows = _check_rows(rows, nrows)
+    excl = None
+    if exclude is not None:
+        excl = exclusion_lists(exclude, (nrows, ncand), rows=rows, transpose=(axis == 1))
+    ctx = _lib.Context(device)
+    try:
+        ctx.set_problem(U.shape[0], V.shape[0], Z.shape[0], k)
+        ctx.set_factor(cf, factors[cf])
+        if queries is None:
+            ctx.set_factor(qf, factors[qf])
+        return ctx.topk(qf, cf, n, link=link, rows=rows, exclude=excl, queries=queries)
+    finally:
+        ctx.close()
