@@ -59,7 +59,8 @@ enum {
     CMF_K_ROWHESS = 7,   /* fused per-row gradient + Hessian over the sampled rows */
     CMF_K_GEMM_PAIR = 8, /* k_pad = 128: the two data passes of an MU half-iteration as one balanced launch (X^T U with Y Z, X V with Y^T V) */
     CMF_K_TOPK = 9,      /* prediction: top-n of f(Q B^T), scores on the fp32 matrix pipe + per-row selection + merge; flops 2 nq C k */
-    CMF_K_COUNT = 10
+    CMF_K_KLMU = 10,     /* Kullback-Leibler MU: fused quotient passes (T ./ (A B^T)) B, both products on the fp32 matrix pipe, and the divergence; flops 4 rows cols k per dense pass */
+    CMF_K_COUNT = 11
 };
 
 const char *cmf_last_error(void);
@@ -104,7 +105,9 @@ int cmf_sync(cmf_ctx *ctx);
  * "row_certificates" 1 (default) | 0: half such a group shares one threshold test of _safe_invert (cmf_solvers.py:346-356)
  * through the positive semi-definite part of their Hessians the rows have in common | every row runs its own,
  * "topk_split" n: cmf_topk / cmf_topk_queries cut the candidates into n shares (<= 0, default: as many as fill the chip); the
- * result does not depend on it                                                                                        */
+ * result does not depend on it,
+ * "kl_split" n: the dense passes of cmf_mu_kl_step / cmf_kl_divergence cut the streamed dimension into n shares (<= 0, default:
+ * enough to give every CU a workgroup); another n regroups the float32 sums                                              */
 int cmf_set_option(cmf_ctx *ctx, const char *name, int64_t value);
 
 /* ---- problem ---------------------------------------------------------- */
@@ -175,6 +178,31 @@ int cmf_mu_step(cmf_ctx *ctx, double l1, double l2, int update_mask);
  * would cancel (e^2 < 1e-3 ||.||^2), the side is not dense or its factor is not updated.  *ex2 / *ey2 (nullable): squared
  * Frobenius residuals of the local shard, as cmf_residual_sq.                                                              */
 int cmf_mu_step_error(cmf_ctx *ctx, double l1, double l2, int update_mask, double *ex2, double *ey2);
+
+/* ---- MU solver, generalised Kullback-Leibler objective --------------------------------------------------------------------
+ * The reference documents beta_loss='kullback-leibler' and does not implement it (pycmf/cmf.py:245-247).  Here:
+ *   minimise  D(X || U V^T) + D(Y || V Z^T) + l1 (sum U + sum V + sum Z) + l2 / 2 (|U|^2 + |V|^2 + |Z|^2),
+ *   D(T || S) = sum_{t > 0} t log(t / s) - sum t + sum s        (unweighted, like the reference's MU objective)
+ * by sklearn's multiplicative update for beta_loss = 1 applied to each block, in the reference's sweep order V, U, Z
+ * (cmf_solvers.py:248-263).  With EPS = 2^-23 and Q(T, A, B) = T ./ max(A B^T, EPS) (a zero of T gives an exact 0):
+ *   V <- V .* [Q(X,U,V)^T U + Q(Y,V,Z) Z] ./ reg(colsum U + colsum Z, V)
+ *   U <- U .* [Q(X,U,V) V] ./ reg(colsum V, U)     (new V)            Z <- Z .* [Q(Y,V,Z)^T V] ./ reg(colsum V, Z)
+ *   reg(den, F) = den + l1 + l2 F, then den == 0 -> EPS               (cmf_solvers.py:212-228 with gamma = 1)
+ * PRECONDITION: non-negative data and factors (not checked here; the Python layer refuses negative data).
+ * The quotient is never materialised (csrc/cmf_klmu.hip.h): dense data go through a fused two-product kernel on the fp32 matrix
+ * pipe, native CSR data (cmf_data_layout) through a fused gather kernel over the stored entries only; X and Y may differ in
+ * layout.  No floating-point atomics: a repeated call from the same state is bit-identical.  Option "gemm_arith" has no effect
+ * here.  k_pad > 256 (n_components above 256): CMF_EUNSUPPORTED.  A sweep whose data matrix has not been set: CMF_EINVAL.
+ * The call leaves every option, captured graph and buffer of the Frobenius path as it was.  cmf_run is not extended: a KL fit
+ * keeps its loop on the host.
+ *   cmf_kl_divergence: *dx = D(X || U V^T), *dy = D(Y || V Z^T) of the factors on the device (either may be NULL), float32 per
+ *   element, float64 accumulation; a native CSR side is evaluated as sum over the stored entries + colsum(A) . colsum(B)
+ *   (sklearn's sparse branch of _beta_divergence) without a dense image.
+ *   cmf_mu_kl_layout: out4 = { shares S of the streamed dimension in the U sweep, in the V sweep (the larger of its two passes),
+ *   in the Z sweep; device scratch bytes of a full step (numerator slabs + column sums) }.  S = 1 for a native CSR side.       */
+int cmf_mu_kl_step(cmf_ctx *ctx, double l1, double l2, int update_mask);
+int cmf_kl_divergence(cmf_ctx *ctx, double *dx, double *dy);
+int cmf_mu_kl_layout(cmf_ctx *ctx, int64_t *out4);
 
 /* sharded form: rank g holds rows of X/U and columns of
  * Y/Z, V replicated.  buf is a DEVICE buffer of cmf_v_buf_elems() floats:

@@ -17,7 +17,7 @@ CMF_NN_U, CMF_NN_V, CMF_NN_Z = 1, 2, 4      # nn_mask bits
 LINKS = {"linear": 0, "logit": 1}
 UPD_U, UPD_V, UPD_Z = 1, 2, 4
 K_GEMM_NN, K_GEMM_TN, K_GEMM_NT, K_ELEMWISE, K_EIGEN = 0, 1, 2, 3, 4
-KERNEL_CLASSES = {"gemm_nn": 0, "gemm_tn": 1, "gemm_nt": 2, "elementwise": 3, "eigen": 4, "gemm_small": 5, "spmm": 6, "rowhess": 7, "gemm_pair": 8, "topk": 9}
+KERNEL_CLASSES = {"gemm_nn": 0, "gemm_tn": 1, "gemm_nt": 2, "elementwise": 3, "eigen": 4, "gemm_small": 5, "spmm": 6, "rowhess": 7, "gemm_pair": 8, "topk": 9, "klmu": 10}
 
 _ERR = {1: ValueError, 2: RuntimeError, 3: MemoryError, 4: RuntimeError, 5: NotImplementedError}
 
@@ -56,6 +56,9 @@ PROTOTYPES = {
     "cmf_get_factor_f64": [_vp, _i32, _pd, _i64, _i64],
     "cmf_mu_step": [_vp, _dbl, _dbl, _i32],
     "cmf_mu_step_error": [_vp, _dbl, _dbl, _i32, _pd, _pd],
+    "cmf_mu_kl_step": [_vp, _dbl, _dbl, _i32],
+    "cmf_kl_divergence": [_vp, _pd, _pd],
+    "cmf_mu_kl_layout": [_vp, _pi64],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_mu_v_partials": [_vp, _vp],
     "cmf_mu_v_apply": [_vp, _vp, _dbl, _dbl],
@@ -421,6 +424,22 @@ class Context:
     # ---- MU
     def mu_step(self, l1, l2, mask=7):
         check(self._lib.cmf_mu_step(self._h, l1, l2, mask))
+
+    def mu_kl_step(self, l1, l2, mask=7):
+        """One multiplicative-update iteration (V, U, Z) for the generalised Kullback-Leibler objective."""
+        check(self._lib.cmf_mu_kl_step(self._h, l1, l2, mask))
+
+    def kl_divergence(self, want_x=True, want_y=True):
+        """(D(X || U V^T), D(Y || V Z^T)) of the factors on the device; a side that is not asked for comes back as 0.0."""
+        dx, dy = C.c_double(0), C.c_double(0)
+        check(self._lib.cmf_kl_divergence(self._h, C.byref(dx) if want_x else None, C.byref(dy) if want_y else None))
+        return dx.value, dy.value
+
+    def mu_kl_layout(self):
+        """(shares of the U sweep, of the V sweep, of the Z sweep, device scratch bytes of a step) of the KL passes."""
+        out = (C.c_int64 * 4)()
+        check(self._lib.cmf_mu_kl_layout(self._h, out))
+        return tuple(out)
 
     def mu_step_error(self, l1, l2, mask=7):
         """One MU iteration and the squared residuals (ex2, ey2) of the factors it leaves, from the step's own products."""

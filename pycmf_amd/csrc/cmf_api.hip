@@ -133,6 +133,8 @@ struct cmf_ctx {
     int opt_nt_debug = 0;  // measurement only (tools/r05_nt_probe.py): bit 0 = the error pass without its targets
     int opt_nt_bn256 = 0;  // NT passes on 256 x 256 tiles where the column extent allows (A/B option: 39.9 ms at C4 against 39.7 for the 256 x 128 x 16 tile)
     int opt_topk_split = 0; // top-n (cmf_topk.hip.h): force the number of candidate shares (<= 0: fill the chip); the result does not depend on it
+    int opt_kl_split = 0;  // KL passes (cmf_klmu.hip.h): force the number of shares of the streamed dimension (<= 0: one workgroup per CU); S = 1 and S > 1 differ in rounding only
+    DevBuf kl_slab, kl_small, kl_part; // ... their numerator slabs, column sums (+ partials), float64 partials of the divergence
     int opt_nt_raster = 0; // NT passes: XCD-aware tile order (blocks of 4 x 8 tiles per XCD; gemm_kernel) -- measured no gain at C4 (40.9 against 40.6 ms): the operands beyond L2 are not the bound
     int opt_nt_tile16 = 1; // 256 x 128 NT passes on the 16-deep K-step (two workgroups per CU) instead of 32-deep (one): 39.6 against 40.7 ms at C4
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
@@ -296,7 +298,7 @@ struct Timed {
         // the OUTERMOST open scope records, so a stretch of the stream is attributed to exactly one class and the classes of an
         // iteration can never add up to more than the iteration (r04's bench lines double-counted the clamp path)
         const bool want = c->timed_open == 0 &&
-                          (c->timing == 1 || (c->timing == 2 && (cls == CMF_K_GEMM_NN || cls == CMF_K_GEMM_TN || cls == CMF_K_GEMM_PAIR || cls == CMF_K_SPMM || cls == CMF_K_ROWHESS)));
+                          (c->timing == 1 || (c->timing == 2 && (cls == CMF_K_GEMM_NN || cls == CMF_K_GEMM_TN || cls == CMF_K_GEMM_PAIR || cls == CMF_K_SPMM || cls == CMF_K_ROWHESS || cls == CMF_K_KLMU)));
         if (want && ev_get(c, &a) == CMF_OK && ev_get(c, &b) == CMF_OK) {
             on = true;
             ++c->timed_open;
@@ -842,6 +844,7 @@ static void release_problem(cmf_ctx *c) {
     c->trace64 = DevBuf(); c->dsq_valid[0] = c->dsq_valid[1] = false;
     c->nsidx = DevBuf(); c->nsws = DevBuf(); c->eigcl_ws = DevBuf(); c->eigcl_log = DevBuf(); c->eigcl_fail = DevBuf(); c->eigcl_snap = DevBuf(); c->r1_ws = DevBuf();
     c->spmm_bar = DevBuf(); c->spmm_part = DevBuf();
+    c->kl_slab = DevBuf(); c->kl_small = DevBuf(); c->kl_part = DevBuf();
     c->g64a = DevBuf(); c->g64b = DevBuf(); c->gmix64 = DevBuf(); c->h64 = DevBuf();
     c->gslab64 = DevBuf(); c->w64 = DevBuf(); c->ns64 = DevBuf();
     c->hinv64 = DevBuf(); c->opr = DevBuf(); c->v_plain = false;
@@ -1018,6 +1021,8 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
         c->opt_spmm_stretch = std::max<int64_t>(0, value);
     } else if (!strcmp(name, "spmm_block_cols")) {
         c->opt_spmm_block_cols = std::max<int64_t>(0, value);
+    } else if (!strcmp(name, "kl_split")) {
+        c->opt_kl_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "topk_split")) {
         c->opt_topk_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "sparse_mode")) {
@@ -1953,3 +1958,5 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_comm.hip.h"
 #define CMF_TOPK_HOST
 #include "cmf_topk.hip.h"
+#define CMF_KLMU_HOST
+#include "cmf_klmu.hip.h"

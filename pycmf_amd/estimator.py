@@ -12,7 +12,7 @@ from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
-from .solver_shell import HipMUSolver, HipNewtonSolver
+from .solver_shell import HipMUSolver, HipNewtonSolver, check_loss, check_kl_data
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -39,7 +39,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                     update_U=True, update_V=True, update_Z=True,
                                     x_link="linear", y_link="linear",
                                     hessian_pertubation=0.2, sg_sample_ratio=1.,
-                                    device=0, sg_sampler="numpy", n_gpus=1, _return_solver=False):
+                                    device=0, sg_sampler="numpy", n_gpus=1, _return_solver=False, loss="frobenius"):
     """Factorise X ~ f(U V^T) and Y ~ f(V Z^T) with a shared V on an MI355X.
 
     Same contract as the reference function (pycmf/cmf.py:215-456): returns
@@ -50,10 +50,16 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     row block of X / U and a column block of Y / Z, V is reassembled by RCCL once per iteration
     (pycmf_amd/multi_gpu.py).  This process touches no GPU; the initial factors come from the host initialisers.  With
     ``sg_sample_ratio < 1`` the workers draw their samples with the device sampler.
+
+    ``loss``: 'frobenius' (default) | 'kullback-leibler' -- the generalised Kullback-Leibler objective
+    D(X || U V^T) + D(Y || V Z^T), the usual loss for count data (``sklearn.decomposition.NMF(beta_loss='kullback-leibler',
+    solver='mu')`` per block); needs ``solver='mu'``, ``n_gpus=1`` and non-negative X and Y (``ValueError`` otherwise, before any
+    device is touched).  ``beta_loss`` keeps the reference's meaning: parsed and ignored.
     """
     if n_components is None:
         n_components = max(X.shape[1], Y.shape[1])
     _check_beta_loss(beta_loss)
+    check_loss(loss, solver, n_gpus)
 
     if update_U or update_V:
         X = check_array(X, accept_sparse=('csr', 'csc'), dtype=float)
@@ -63,6 +69,8 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     if update_V and X.shape[1] != Y.shape[0]:
         raise ValueError("Expected X.shape[1] == Y.shape[0], " +
                          "found X.shape = {}, Y.shape = {}".format(X.shape[1], Y.shape[0]))
+    if loss == "kullback-leibler":
+        check_kl_data(X, Y)
     if x_link not in ("linear", "logit"):
         raise ValueError("No such link %s for x_link" % x_link)
     if y_link not in ("linear", "logit"):
@@ -75,7 +83,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
         if x_link != "linear" or y_link != "linear":
             warnings.warn("mu solver does not accept link functions other than linear, "
                           "link arguments will be ignored")
-        solver_object = HipMUSolver(beta_loss=beta_loss, **common)
+        solver_object = HipMUSolver(beta_loss=beta_loss, loss=loss, **common)
     elif solver == "newton":
         if alpha == "auto":
             alpha = Y.shape[1] / (X.shape[0] + Y.shape[1])
@@ -201,6 +209,12 @@ class CMF(BaseEstimator, TransformerMixin):
     beyond ~1e7 drawn indices (a ``RuntimeWarning`` says so; BASELINE config C3 would spend ~16 s per iteration there).
     ``'device'`` draws the same distribution (exactly ``int(n * ratio)`` distinct indices per row, uniform) on the GPU from a
     counter-based generator: the benchmarked path (C3: 0.24 s per iteration), statistically but not numerically NumPy's stream.
+
+    ``loss``: ``'frobenius'`` (default) or ``'kullback-leibler'``: multiplicative updates on the generalised Kullback-Leibler
+    objective D(X || U V^T) + D(Y || V Z^T), for count data (the reference documents ``beta_loss='kullback-leibler'`` and does not
+    implement it; ``beta_loss`` stays parsed-and-ignored here too).  Needs ``solver='mu'``, ``n_gpus=1`` and non-negative X, Y.
+    ``reconstruction_err_`` is then sqrt(2 D_x) + sqrt(2 D_y), the stopping test the reference's on
+    alpha sqrt(2 D_x) + (1 - alpha) sqrt(2 D_y).
     """
 
     def __init__(self, n_components=None, x_init=None, y_init=None, solver='mu', alpha='auto',
@@ -208,7 +222,7 @@ class CMF(BaseEstimator, TransformerMixin):
                  random_state=None, l1_reg=0., l2_reg=0., verbose=0,
                  U_non_negative=True, V_non_negative=True, Z_non_negative=True,
                  x_link="linear", y_link="linear", hessian_pertubation=0.2, sg_sample_ratio=1.,
-                 device=0, sg_sampler="numpy", n_gpus=1):
+                 device=0, sg_sampler="numpy", n_gpus=1, loss="frobenius"):
         self.n_components = n_components
         self.x_init = x_init
         self.y_init = y_init
@@ -231,6 +245,7 @@ class CMF(BaseEstimator, TransformerMixin):
         self.device = device
         self.sg_sampler = sg_sampler
         self.n_gpus = n_gpus
+        self.loss = loss
 
     def _kwargs(self):
         return dict(solver=self.solver, beta_loss=self.beta_loss, tol=self.tol, max_iter=self.max_iter,
@@ -239,7 +254,8 @@ class CMF(BaseEstimator, TransformerMixin):
                     V_non_negative=self.V_non_negative, Z_non_negative=self.Z_non_negative,
                     x_link=self.x_link, y_link=self.y_link,
                     hessian_pertubation=self.hessian_pertubation,
-                    sg_sample_ratio=self.sg_sample_ratio, device=self.device, sg_sampler=self.sg_sampler)
+                    sg_sample_ratio=self.sg_sample_ratio, device=self.device, sg_sampler=self.sg_sampler,
+                    loss=self.loss)
 
     def fit_transform(self, X, Y, U=None, V=None, Z=None):
         X = check_array(X, accept_sparse=('csr', 'csc'), dtype=float)

@@ -26,6 +26,31 @@ import numpy as np
 from . import _lib
 
 
+LOSSES = ("frobenius", "kullback-leibler")
+
+
+def check_loss(loss, solver="mu", n_gpus=1):
+    """Validate the ``loss`` keyword (no device is touched): 'frobenius' | 'kullback-leibler'; the latter needs the MU solver and
+    one GPU."""
+    if loss not in LOSSES:
+        raise ValueError("Invalid loss parameter: got %r instead of one of %r" % (loss, list(LOSSES)))
+    if loss == "kullback-leibler":
+        if solver != "mu":
+            raise ValueError("loss='kullback-leibler' is implemented by the multiplicative-update solver only: solver='mu', got %r" % (solver,))
+        if n_gpus != 1:
+            raise ValueError("loss='kullback-leibler' runs on one GPU: n_gpus must be 1, got %r (the sharded form is not built)" % (n_gpus,))
+
+
+def check_kl_data(X, Y):
+    """The generalised Kullback-Leibler divergence is defined for non-negative data only."""
+    for name, M in (("X", X), ("Y", Y)):
+        if M is None:
+            continue
+        vals = M.data if hasattr(M, "tocsr") else np.asarray(M)
+        if vals.size and vals.min() < 0:
+            raise ValueError("loss='kullback-leibler' needs non-negative data: %s has negative entries" % name)
+
+
 def _as_f64(a):
     return a if (isinstance(a, np.ndarray) and a.dtype == np.float64) else np.asarray(a, dtype=np.float64)
 
@@ -105,6 +130,8 @@ class _HipIterativeSolver:
 
     def _bind_dims(self, X, Y, m, d, p, k):
         key = (id(X), id(Y), m, d, p, k)
+        if getattr(self, "loss", "frobenius") == "kullback-leibler" and self._bound != key:
+            check_kl_data(X, Y)
         if self._ctx is None:
             self._ctx = _lib.Context(self.device, self.stream)
             mode = os.environ.get("PYCMF_AMD_SPARSE_MODE")  # "dense" | "native": override the auto choice
@@ -252,17 +279,41 @@ class _HipIterativeSolver:
 
 
 class HipMUSolver(_HipIterativeSolver):
-    """Multiplicative updates V -> U -> Z (pycmf/cmf_solvers.py:198-263) on the GPU."""
+    """Multiplicative updates V -> U -> Z (pycmf/cmf_solvers.py:198-263) on the GPU.
+
+    ``loss='kullback-leibler'`` (``beta_loss`` keeps its reference meaning: parsed, ignored): the same sweep order on the
+    generalised Kullback-Leibler objective D(X || U V^T) + D(Y || V Z^T) -- sklearn's multiplicative update for beta_loss = 1 per
+    block (``cmf_mu_kl_step``).  The error metric is then what ``compute_factorization_error`` would return under beta_loss = 1,
+    sqrt(2 D) per side; the loop stays on the host (``cmf_run`` knows the Frobenius steps only)."""
+
+    def __init__(self, *args, loss="frobenius", **kwargs):
+        check_loss(loss)
+        super().__init__(*args, **kwargs)
+        self.loss = loss
 
     def _device_step(self, l1_reg, l2_reg, alpha):
+        if self.loss == "kullback-leibler":
+            self._ctx.mu_kl_step(l1_reg, l2_reg, self._update_mask())
+            return
         self._ctx.mu_step(l1_reg, l2_reg, self._update_mask())
 
+    def _device_error(self):
+        if self.loss != "kullback-leibler":
+            return super()._device_error()
+        X, Y = self._XY
+        dx, dy = self._ctx.kl_divergence(X is not None, Y is not None)
+        return np.sqrt(2.0 * max(dx, 0.0)), np.sqrt(2.0 * max(dy, 0.0))
+
     def _device_step_error(self, l1_reg, l2_reg, alpha):
+        if self.loss == "kullback-leibler":
+            return None
         ex2, ey2 = self._ctx.mu_step_error(l1_reg, l2_reg, self._update_mask())
         X, Y = self._XY
         return (np.sqrt(ex2) if X is not None else 0.0), (np.sqrt(ey2) if Y is not None else 0.0)
 
     def _run_params(self):
+        if self.loss == "kullback-leibler":
+            return None
         return dict(solver="mu", l1=self.l1_reg, l2=self.l2_reg, alpha_err=self.alpha, update_mask=self._update_mask())
 
 
