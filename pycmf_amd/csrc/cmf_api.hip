@@ -116,27 +116,16 @@ struct cmf_ctx {
     int opt_graph = -1;    // replay MU / linear-Newton steps from a captured hipGraph: 1 always | 0 never | -1 (default) inside cmf_run
                            // only (single steps measured neutral: the ~4 us per dependent kernel boundary is device-side)
     StepGraph mu_graph, newton_graph;
-    int opt_pipe_small = 4; // staging schedule of the factor-side products (0 or 4; 4 measured +5..15 %, tools/ab_small.py)
-    int opt_pipe = 4;      // GEMM staging schedule (see gemm_kernel PIPE); 4 measured best (tools/ab_gemm.py)
     int opt_split = -1;    // force split-K factor (<=0: heuristic)
-    int opt_class_depth = 4; // class blocks in flight per thread of class_sum_blocks_kernel (4 | 8 | 16)
     int opt_pair = 1;      // k_pad = 128, dense X and Y: the two data passes of an MU half-iteration as one balanced launch (cmf_gemm_pair.hip.h) | 0: two split launches
-    int opt_tile512 = 0;   // A/B: k_pad = 128 data passes on a 512 x 128 x 16 tile (GemmCfg TILE 1) instead of 256 x 128 x 32
-    int opt_rounds = 1;    // split-K heuristic of the data passes: aim at this many workgroups per CU (A/B option: 2 measured within noise of 1 at C2)
     int opt_arith_min_tiles = 8;   // ... only for operands of at least this many 256-row tiles
     int opt_arith = 0;     // data passes at k_pad = 256: 0 fp32 MFMA | 1 bf16x6 (three bf16 planes per operand, fp32-equivalent)
     int opt_ns = 1;        // flagged per-row Hessians at k_pad = 256: Newton-Schulz spectral clamp (0: Jacobi)
     bool hess_psd = true;  // the Hessians of the current step are positive semi-definite by construction (0 <= alpha <= 1)
-    int opt_pipe_nt = 4;   // staging schedule of the NT (residual / error) GEMMs: 0 | 4
-    int opt_refine_map = 1;     // batched float64 clamp: spectral map (lambda - pert) / (lambda + pert) in front of the sign iteration (refine_rows64_batched)
-    int opt_gemm64_tile128 = 1; // batched float64 256^3 products of the refinement on 128 x 128 tiles (gemm64_tile128_kernel); 0: 32 x 32 tiles
-    int opt_nt_debug = 0;  // measurement only (tools/r05_nt_probe.py): bit 0 = the error pass without its targets
-    int opt_nt_bn256 = 0;  // NT passes on 256 x 256 tiles where the column extent allows (A/B option: 39.9 ms at C4 against 39.7 for the 256 x 128 x 16 tile)
+    int opt_pipe_nt = 4;   // staging schedule of the NT (residual / error) GEMMs: 0 | 4 (every NN / TN product runs schedule 4)
     int opt_topk_split = 0; // top-n (cmf_topk.hip.h): force the number of candidate shares (<= 0: fill the chip); the result does not depend on it
     int opt_kl_split = 0;  // KL passes (cmf_klmu.hip.h): force the number of shares of the streamed dimension (<= 0: one workgroup per CU); S = 1 and S > 1 differ in rounding only
     DevBuf kl_slab, kl_small, kl_part; // ... their numerator slabs, column sums (+ partials), float64 partials of the divergence
-    int opt_nt_raster = 0; // NT passes: XCD-aware tile order (blocks of 4 x 8 tiles per XCD; gemm_kernel) -- measured no gain at C4 (40.9 against 40.6 ms): the operands beyond L2 are not the bound
-    int opt_nt_tile16 = 1; // 256 x 128 NT passes on the 16-deep K-step (two workgroups per CU) instead of 32-deep (one): 39.6 against 40.7 ms at C4
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
     int opt_chol = 1;      // Cholesky fast path of the safe inverse (0: always Jacobi)
     int opt_chol_mfma = 1; // k_pad = 256 per-row solves: blocked Cholesky on the matrix pipe (0: the rank-1 register kernel chol_solve_kernel<16>)
@@ -174,17 +163,8 @@ struct cmf_ctx {
     int opt_gram32 = 1;                   // k_pad 64 / 128 Grams on gram32_partial_kernel (0: one-tile TN GEMM, split + slab sum)
     DevBuf slabs, slabs_b;                // split-K partial tiles (grow-only); second set for a product whose slabs must outlive the next one
     int slab_sel = 0;                     // which set gemm() writes
-    DevBuf tickets;                       // one arrival counter per output tile of a split-K GEMM (zero between launches)
     int timed_open = 0;                   // open Timed scopes that record (see Timed)
     DevBuf narrow_tmp;                    // output image of an in-place fused update cut into column tiles (gemm(): the siblings of a row tile read all of F)
-    int opt_inred = 0;                    // 0: split-K partials summed by a chip-wide kernel | 1: by the last-arriving workgroup of each tile
-                                          // inside the GEMM kernel (A/B option; measured slower)
-    int opt_side_gram = 0;                // A/B option: small Grams (k_pad 64 / 128) on a side stream beside the data pass that follows them
-                                          // (cmf_mu_step).  Measured at C2, interleaved: 1204-1205 it/s with, 1215-1216 without -- the Gram's
-                                          // workgroups take LDS bandwidth and issue slots from the data pass for longer than they save; default off
-    hipStream_t side = nullptr;           // ... that stream, with the two events of a fork / join
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool side_pending = false;
     int opt_narrow_update = 1;            // fused factor updates with few row tiles run on 256 x 128 / 256 x 64 tiles (gemm())
     int opt_fused_mu = 1;                 // 1: F <- F num / reg(F G) in the epilogue of the F G product | 0: separate kernel
     int opt_small_tile = 1;               // 1: k_pad 64 / 128 factor updates on 64-row tiles (factor_update_kernel) | 0: gemm_kernel's 256-row tile
@@ -195,7 +175,6 @@ struct cmf_ctx {
     DevBuf mask1, mask2;                  // stochastic sample masks (bytes)
     DevBuf lists1, lists2;                // device copies of the per-row sample index lists
     DevBuf hpart;                         // partial Hessians / gradients of the split row launches (few rows, long lists)
-    int opt_ft_tile = 256;                // tile of factor_times64_kernel: 256 = 128 rows x 64 columns, eight waves (default; C5: 2.2 ms per 1e6 x 256 x 256 product) | 64 = 64 x 64 (2.4 ms) | 128 = 64 x 128 (2.8 ms)
     int opt_rowsplit = 1;                 // split the samples of a row over several workgroups when a sweep has fewer rows than CUs
     DevBuf lr_small, lr_rows;             // low-rank per-row side (sweep_v_lowrank): B / Z^T / K images; per-row p x p systems
     int opt_lowrank = 1;                  // Woodbury form of the V sweep when the per-row side has fewer samples than components
@@ -380,24 +359,20 @@ struct GemmPlan {
     int64_t tiles_m;
     int nsplit;
     int64_t klen;
-    int tile = 0; // 1: the 512 x 128 x 16 tile (GemmCfg TILE 1)
 };
 
-static GemmPlan plan_gemm(const cmf_ctx *c, int64_t mout, int64_t n, int64_t kred, bool allow_split, bool data_pass = false) {
+static GemmPlan plan_gemm(const cmf_ctx *c, int64_t mout, int64_t n, int64_t kred, bool allow_split) {
     GemmPlan pl;
     pl.bn = n >= 256 ? 256 : (int)n; // n in {32,64,128} or a multiple of 256
     pl.ntiles_n = (int)(n / pl.bn);
-    pl.tile = (c->opt_tile512 && data_pass && allow_split && pl.bn == 128 && mout % 512 == 0 && c->opt_pipe == 4) ? 1 : 0;
-    pl.tiles_m = pl.tile ? mout / 512 : (mout + 255) / 256;
+    pl.tiles_m = (mout + 255) / 256;
     const int64_t tiles = pl.tiles_m * pl.ntiles_n;
     int64_t s = 1;
     if (allow_split && c->opt_split > 0) {
         s = std::min<int64_t>(c->opt_split, std::max<int64_t>(1, kred / 32));
     } else if (allow_split && tiles < (int64_t)(c->num_cu * 3) / 4) {
-        // a GEMM with too few output tiles splits its reduction so that every CU gets a workgroup (`gemm_rounds` = r: r
-        // per CU for the data passes -- at C2 two rounds measured within run-to-run noise of one, three and four slower)
-        const int64_t want = (int64_t)c->num_cu * (data_pass ? std::max(1, c->opt_rounds) : 1);
-        s = (want + tiles / 2) / tiles;
+        // a GEMM with too few output tiles splits its reduction so that every CU gets a workgroup
+        s = ((int64_t)c->num_cu + tiles / 2) / tiles;
         const int64_t maxs = std::max<int64_t>(1, kred / 128);
         s = std::max<int64_t>(1, std::min(s, maxs));
     }
@@ -406,65 +381,28 @@ static GemmPlan plan_gemm(const cmf_ctx *c, int64_t mout, int64_t n, int64_t kre
     return pl;
 }
 
-template <int MODE, int ROLE, int PIPE>
-static int launch_gemm_pipe(cmf_ctx *c, const GemmArgs &a, const GemmPlan &pl) {
+// NN / TN products on the 256 x BN x 32 tile (BN = pl.bn), every one on staging schedule 4
+template <int MODE, int ROLE>
+static int launch_gemm(cmf_ctx *c, const GemmArgs &a, const GemmPlan &pl) {
+    static_assert(MODE != MODE_NT, "NT passes: gemm_nt");
     dim3 grid((unsigned)pl.tiles_m, (unsigned)pl.ntiles_n, (unsigned)pl.nsplit);
     dim3 block(512);
 #define CMF_LAUNCH(BN_)                                                                          \
     do {                                                                                         \
         using Cfg = GemmCfg<MODE, BN_>;                                                          \
-        CHK(allow_big_lds(c, reinterpret_cast<const void *>(&gemm_kernel<MODE, BN_, ROLE, PIPE>), (int)Cfg::LDS_BYTES)); \
-        hipLaunchKernelGGL((gemm_kernel<MODE, BN_, ROLE, PIPE>), grid, block, Cfg::LDS_BYTES, c->stream, a); \
+        CHK(allow_big_lds(c, reinterpret_cast<const void *>(&gemm_kernel<MODE, BN_, ROLE, 4>), (int)Cfg::LDS_BYTES)); \
+        hipLaunchKernelGGL((gemm_kernel<MODE, BN_, ROLE, 4>), grid, block, Cfg::LDS_BYTES, c->stream, a); \
     } while (0)
-    if constexpr (MODE == MODE_NT) {
-        if (pl.bn == 256 && pl.tile == 0) { // 256 x 256 x 32: the data passes' tile (twice the MFMA work per barrier and per LDS fill)
-            CMF_LAUNCH(256);
-            HIPCHK(hipGetLastError());
-            return CMF_OK;
-        }
-        if (pl.bn != 128) return fail(CMF_EINVAL, "NT tile width must be 128 or 256");
-        if (pl.tile == 2) { // 256 x 128 x 16: two workgroups per CU (GemmCfg TILE 2)
-            using Cfg = GemmCfg<MODE, 128, 2>;
-            CHK(allow_big_lds(c, reinterpret_cast<const void *>(&gemm_kernel<MODE, 128, ROLE, PIPE, 2>), (int)Cfg::LDS_BYTES));
-            hipLaunchKernelGGL((gemm_kernel<MODE, 128, ROLE, PIPE, 2>), grid, block, Cfg::LDS_BYTES, c->stream, a);
-        } else CMF_LAUNCH(128);
-    } else {
-        if constexpr (ROLE == 0 && PIPE == 4) {
-            if (pl.tile == 1 && pl.bn == 128) { // A/B: 512 x 128 x 16 tile
-                using Cfg = GemmCfg<MODE, 128, 1>;
-                CHK(allow_big_lds(c, reinterpret_cast<const void *>(&gemm_kernel<MODE, 128, ROLE, PIPE, 1>), (int)Cfg::LDS_BYTES));
-                hipLaunchKernelGGL((gemm_kernel<MODE, 128, ROLE, PIPE, 1>), grid, block, Cfg::LDS_BYTES, c->stream, a);
-                HIPCHK(hipGetLastError());
-                return CMF_OK;
-            }
-        }
-        switch (pl.bn) {
-        case 256: CMF_LAUNCH(256); break;
-        case 128: CMF_LAUNCH(128); break;
-        case 64: CMF_LAUNCH(64); break;
-        case 32: CMF_LAUNCH(32); break;
-        default: return fail(CMF_EINVAL, "unsupported tile width %d", pl.bn);
-        }
+    switch (pl.bn) {
+    case 256: CMF_LAUNCH(256); break;
+    case 128: CMF_LAUNCH(128); break;
+    case 64: CMF_LAUNCH(64); break;
+    case 32: CMF_LAUNCH(32); break;
+    default: return fail(CMF_EINVAL, "unsupported tile width %d", pl.bn);
     }
 #undef CMF_LAUNCH
     HIPCHK(hipGetLastError());
     return CMF_OK;
-}
-
-template <int MODE, int ROLE>
-static int launch_gemm_mode(cmf_ctx *c, const GemmArgs &a, const GemmPlan &pl) {
-    if (ROLE == 0 && MODE != MODE_NT) {
-        if (c->opt_pipe == 1) return launch_gemm_pipe<MODE, ROLE, (ROLE == 0 && MODE != MODE_NT) ? 1 : 0>(c, a, pl);
-        if (c->opt_pipe == 2) return launch_gemm_pipe<MODE, ROLE, (ROLE == 0 && MODE != MODE_NT) ? 2 : 0>(c, a, pl);
-        if (c->opt_pipe == 3) return launch_gemm_pipe<MODE, ROLE, (ROLE == 0 && MODE != MODE_NT) ? 3 : 0>(c, a, pl);
-        if (c->opt_pipe == 4) return launch_gemm_pipe<MODE, ROLE, (ROLE == 0 && MODE != MODE_NT) ? 4 : 0>(c, a, pl);
-        if (c->opt_pipe == 5) return launch_gemm_pipe<MODE, ROLE, (ROLE == 0 && MODE != MODE_NT) ? 5 : 0>(c, a, pl);
-        if (c->opt_pipe == 10) return launch_gemm_pipe<MODE, ROLE, (ROLE == 0 && MODE != MODE_NT) ? 10 : 0>(c, a, pl);
-    }
-    if (ROLE == 1 && MODE != MODE_NT && c->opt_pipe_small == 4)
-        return launch_gemm_pipe<MODE, ROLE, (ROLE == 1 && MODE != MODE_NT) ? 4 : 0>(c, a, pl);
-    if (MODE == MODE_NT && c->opt_pipe_nt == 4) return launch_gemm_pipe<MODE, ROLE, (MODE == MODE_NT) ? 4 : 0>(c, a, pl);
-    return launch_gemm_pipe<MODE, ROLE, 0>(c, a, pl);
 }
 
 static int sum_slabs(cmf_ctx *c, float *dst, const float *src, int64_t n, int nslab, int64_t stride,
@@ -499,8 +437,8 @@ struct Epilogue { // fused factor update in the epilogue of a factor-side produc
 };
 
 // C[mout x n] (+)= op(A) * B.  mode NN: A is [mout_pad x kred]; TN: A is [kred x >=mout].
-// Result lands in `out` (ld = n); split-K partials go through the slab workspace and are summed in slab order -- by the
-// last-arriving workgroup of each output tile inside the GEMM kernel (default) or by a separate kernel.
+// Result lands in `out` (ld = n); split-K partials go through the slab workspace and are summed in slab order by a
+// separate kernel (or left to a consumer that sums them itself: `defer`).
 // `A` is a factor-sized operand when lda == k_pad (Grams, F*G, step products): those launches
 // use the ROLE=1 symbol and the CMF_K_GEMM_SMALL timing class.
 static int gemm(cmf_ctx *c, int mode, const float *A, int64_t lda, const float *B, int64_t ldb, float *out,
@@ -508,8 +446,8 @@ static int gemm(cmf_ctx *c, int mode, const float *A, int64_t lda, const float *
     const bool data_pass = (lda != c->kp);
     DevBuf &slabbuf = c->slab_sel ? c->slabs_b : c->slabs;
     if (kred % 32 || n % 32) return fail(CMF_EINVAL, "gemm: unpadded extent (k=%lld n=%lld)", (long long)kred, (long long)n);
-    GemmPlan pl = plan_gemm(c, mout, n, kred, mu == nullptr, data_pass);
-    if (mu && c->opt_narrow_update && pl.ntiles_n == 1 && pl.tile == 0) {
+    GemmPlan pl = plan_gemm(c, mout, n, kred, mu == nullptr);
+    if (mu && c->opt_narrow_update && pl.ntiles_n == 1) {
         // a factor-side product with a fused update cannot split its reduction (K = k_pad), and one 256 x 256 x 256 tile is 55 us of
         // one CU whatever the row count: with few row tiles (a rank's 8192-row shard of U at C4 / 8 GPUs: 32) cut the tile's
         // columns instead -- same arithmetic per element, bit-identical results, 4 x the workgroups
@@ -532,8 +470,6 @@ static int gemm(cmf_ctx *c, int mode, const float *A, int64_t lda, const float *
     a.Kred = kred; a.klen = pl.klen;
     a.dbg = data_pass ? c->dbg_stamps : nullptr;
     const int64_t rows_store = (mode == MODE_TN) ? mout : rup(mout, 256);
-    // in-kernel forms: fused update epilogue; out += acc of an unsplit accumulate; (option) last-arriver reduction of splits
-    const bool in_kernel = mu != nullptr || pl.nsplit == 1 || (c->opt_inred != 0 && (int64_t)pl.tiles_m * pl.ntiles_n >= 16 && pl.nsplit <= 16);
     const bool direct = (pl.nsplit == 1 && !accumulate);
     if (mu) {
         if (mode != MODE_NN || pl.nsplit != 1) return fail(CMF_EINVAL, "fused update needs an unsplit NN product");
@@ -544,7 +480,7 @@ static int gemm(cmf_ctx *c, int mode, const float *A, int64_t lda, const float *
     } else if (direct) {
         a.C = out;
         a.slab_stride = 0;
-    } else if (in_kernel && pl.nsplit == 1) {
+    } else if (pl.nsplit == 1) {
         a.red_out = out; a.red_acc = 1; // out += acc in the epilogue
         a.C = out;
     } else {
@@ -552,28 +488,20 @@ static int gemm(cmf_ctx *c, int mode, const float *A, int64_t lda, const float *
         CHK(ensure(c, slabbuf, need));
         a.C = (float *)slabbuf.p;
         a.slab_stride = rows_store * n;
-        if (in_kernel) {
-            const size_t ntile = (size_t)pl.tiles_m * pl.ntiles_n;
-            if (c->tickets.bytes < ntile * sizeof(unsigned)) {
-                CHK(ensure(c, c->tickets, std::max<size_t>(4096, 2 * ntile) * sizeof(unsigned)));
-                HIPCHK(hipMemsetAsync(c->tickets.p, 0, c->tickets.bytes, c->stream));
-            }
-            a.red_out = out; a.red_acc = accumulate ? 1 : 0; a.ticket = (unsigned *)c->tickets.p;
-        }
     }
     {
         Timed tm(c, !data_pass ? CMF_K_GEMM_SMALL : (mode == MODE_NN ? CMF_K_GEMM_NN : CMF_K_GEMM_TN),
                  2.0 * (double)mout * (double)n * (double)kred * c->flop_scale);
         if (mode == MODE_NN) {
-            if (data_pass) CHK((launch_gemm_mode<MODE_NN, 0>(c, a, pl)));
-            else CHK((launch_gemm_mode<MODE_NN, 1>(c, a, pl)));
+            if (data_pass) CHK((launch_gemm<MODE_NN, 0>(c, a, pl)));
+            else CHK((launch_gemm<MODE_NN, 1>(c, a, pl)));
         } else {
-            if (data_pass) CHK((launch_gemm_mode<MODE_TN, 0>(c, a, pl)));
-            else CHK((launch_gemm_mode<MODE_TN, 1>(c, a, pl)));
+            if (data_pass) CHK((launch_gemm<MODE_TN, 0>(c, a, pl)));
+            else CHK((launch_gemm<MODE_TN, 1>(c, a, pl)));
         }
     }
     if (alias_out) HIPCHK(hipMemcpyAsync(alias_out, c->narrow_tmp.p, (size_t)rup(mout, 256) * n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    if (!direct && !in_kernel) {
+    if (!mu && pl.nsplit > 1) {
         if (defer && !accumulate) { // the consumer sums the slabs (valid until the next GEMM reuses the slab workspace)
             defer->base = (const float *)slabbuf.p; defer->nslab = pl.nsplit; defer->stride = a.slab_stride;
             return CMF_OK;
@@ -586,51 +514,19 @@ static int gemm(cmf_ctx *c, int mode, const float *A, int64_t lda, const float *
 
 // G (k_pad x k_pad) = F^T F over rows_pad rows of a factor-sized operand: the dedicated small-Gram kernels at k_pad 64 / 128
 // (cmf_kernels.hip.h), else the TN GEMM
-// Fork / join of the side stream: a small Gram whose consumer sits BEHIND the next data pass (U^T U + Z^T Z before the V update,
-// V^T V before the U / Z updates) is launched on a second stream that starts where the main stream stands and is joined in front
-// of the consumer -- its 96 small workgroups (24 KB of LDS, 256 threads) run in the slots the data pass leaves free on every CU
-// (one 512-thread workgroup with 98 KB of LDS at k_pad = 128) instead of in front of it.  Captured into the step graph as a fork.
-static bool side_gram_ok(const cmf_ctx *c, int64_t rows_pad) {
-    return c->opt_side_gram && c->timing != 1 && c->opt_gram32 && (c->kp == 64 || c->kp == 128) && rows_pad >= 1024 && c->opt_arith == 0;
-}
-static int side_fork(cmf_ctx *c) {
-    if (!c->side) {
-        HIPCHK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    }
-    HIPCHK(hipEventRecord(c->ev_fork, c->stream));
-    HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    return CMF_OK;
-}
-static int side_join(cmf_ctx *c) {
-    if (!c->side_pending) return CMF_OK;
-    HIPCHK(hipEventRecord(c->ev_join, c->side));
-    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    c->side_pending = false;
-    return CMF_OK;
-}
-
-static int gram32(cmf_ctx *c, const float *F, int64_t rows_pad, float *G, bool on_side = false) {
+static int gram32(cmf_ctx *c, const float *F, int64_t rows_pad, float *G) {
     // (k_pad = 256, C4: measured equal to the TN GEMM + slab sum, 0.70 against 0.53 + 0.13 ms per iteration -- not used there)
     if (!(c->opt_gram32 && (c->kp == 64 || c->kp == 128) && rows_pad >= 1024))
         return gemm(c, MODE_TN, F, c->kp, F, c->kp, G, c->kp, c->kp, rows_pad);
-    CHK(side_join(c)); // (the partial slabs are shared: one small Gram in flight at a time)
     const int T = c->kp / 64, ntile = T * (T + 1) / 2;
     // row shares: 32 for a few thousand rows (C2); long factors (C4: 131072 stacked rows) take one share per 1024 rows
     int64_t nsplit = std::min<int64_t>(std::max<int64_t>(c->opt_gram32_shares, std::min<int64_t>(256, rows_pad / 1024)), rows_pad / 32);
     const int64_t chunk = rup((rows_pad + nsplit - 1) / nsplit, 32);
     nsplit = (rows_pad + chunk - 1) / chunk;
     CHK(ensure(c, c->gslab32, (size_t)nsplit * ntile * 64 * 64 * sizeof(float)));
-    hipStream_t st = c->stream;
-    if (on_side && side_gram_ok(c, rows_pad)) {
-        CHK(side_fork(c));
-        st = c->side;
-        c->side_pending = true;
-    }
     Timed tm(c, CMF_K_GEMM_SMALL, 2.0 * (double)rows_pad * c->kp * c->kp);
-    hipLaunchKernelGGL(gram32_partial_kernel, dim3((unsigned)ntile, (unsigned)nsplit), dim3(256), 0, st, F, c->kp, rows_pad, chunk, (float *)c->gslab32.p);
-    hipLaunchKernelGGL(gram32_reduce_kernel, dim3((unsigned)std::min(64, (c->kp * c->kp + 255) / 256)), dim3(256), 0, st, (const float *)c->gslab32.p,
+    hipLaunchKernelGGL(gram32_partial_kernel, dim3((unsigned)ntile, (unsigned)nsplit), dim3(256), 0, c->stream, F, c->kp, rows_pad, chunk, (float *)c->gslab32.p);
+    hipLaunchKernelGGL(gram32_reduce_kernel, dim3((unsigned)std::min(64, (c->kp * c->kp + 255) / 256)), dim3(256), 0, c->stream, (const float *)c->gslab32.p,
                        c->kp, (int)nsplit, G);
     HIPCHK(hipGetLastError());
     return CMF_OK;
@@ -715,19 +611,8 @@ struct NtOut {
 // S = L[rows x kp] * Rt[cols x kp]^T with fused epilogue
 static int gemm_nt(cmf_ctx *c, const float *L, int64_t rows_pad, int64_t rows_valid, const float *Rt,
                    int64_t cols_pad, int64_t cols_valid, const NtOut &o) {
-    GemmPlan pl;
-    pl.bn = 128; pl.ntiles_n = (int)(cols_pad / 128); pl.tiles_m = rows_pad / 256; pl.nsplit = 1; pl.klen = c->kp;
-    pl.tile = c->opt_nt_tile16 ? 2 : 0;
-    if (c->opt_nt_bn256 && cols_pad % 256 == 0 && (rows_pad / 256) * (cols_pad / 256) >= 2 * (int64_t)c->num_cu) {
-        pl.bn = 256; pl.ntiles_n = (int)(cols_pad / 256); pl.tile = 0;
-    }
-    int ras_rb = 0, ras_cb = 0;
-    if (c->opt_nt_raster && pl.ntiles_n % 8 == 0 && pl.tiles_m * pl.ntiles_n >= 8 * 64) {
-        const int per_x = pl.ntiles_n / 8;
-        ras_cb = per_x % 8 == 0 ? 8 : (per_x % 4 == 0 ? 4 : (per_x % 2 == 0 ? 2 : 1));
-        ras_rb = 32 / ras_cb;
-        while (ras_rb > 1 && pl.tiles_m % ras_rb) ras_rb /= 2;
-    }
+    // 256 x 128 output tiles on the 16-deep K-step (GemmCfg TILE 2): two workgroups per CU
+    const dim3 grid((unsigned)(rows_pad / 256), (unsigned)(cols_pad / 128), 1);
     GemmArgs a;
     memset(&a, 0, sizeof a);
     a.A = L; a.lda = c->kp; a.B = Rt; a.ldb = c->kp;
@@ -735,15 +620,22 @@ static int gemm_nt(cmf_ctx *c, const float *L, int64_t rows_pad, int64_t rows_va
     a.T = o.T; a.ldt = o.ldt; a.R = o.R; a.W = o.W; a.ldr = o.ldr; a.mask = o.mask; a.ldm = o.ldm;
     a.Mvalid = rows_valid; a.Nvalid = cols_valid;
     a.scale_r = o.scale_r; a.scale_w = o.scale_w; a.link = o.link; a.w_is_slope = o.w_is_slope;
-    a.ras_rb = ras_rb; a.ras_cb = ras_cb;
-    const int64_t nwg = pl.tiles_m * pl.ntiles_n;
+    const int64_t nwg = (int64_t)grid.x * grid.y;
     if (o.sq) {
         CHK(ensure(c, c->dpart, (size_t)nwg * sizeof(double)));
         a.sq_out = (double *)c->dpart.p;
     }
     {
         Timed tm(c, CMF_K_GEMM_NT, 2.0 * (double)rows_valid * (double)cols_valid * (double)c->kp * c->flop_scale);
-        CHK((launch_gemm_mode<MODE_NT, 0>(c, a, pl)));
+        using Cfg = GemmCfg<MODE_NT, 128, 2>;
+        if (c->opt_pipe_nt == 4) {
+            CHK(allow_big_lds(c, reinterpret_cast<const void *>(&gemm_kernel<MODE_NT, 128, 0, 4, 2>), (int)Cfg::LDS_BYTES));
+            hipLaunchKernelGGL((gemm_kernel<MODE_NT, 128, 0, 4, 2>), grid, dim3(512), Cfg::LDS_BYTES, c->stream, a);
+        } else {
+            CHK(allow_big_lds(c, reinterpret_cast<const void *>(&gemm_kernel<MODE_NT, 128, 0, 0, 2>), (int)Cfg::LDS_BYTES));
+            hipLaunchKernelGGL((gemm_kernel<MODE_NT, 128, 0, 0, 2>), grid, dim3(512), Cfg::LDS_BYTES, c->stream, a);
+        }
+        HIPCHK(hipGetLastError());
     }
     if (o.sq) {
         Timed tm(c, CMF_K_ELEMWISE);
@@ -809,10 +701,6 @@ extern "C" int cmf_ctx_create(cmf_ctx **out, int device, void *stream) {
         c->own_stream = true;
     }
     c->diag_ok = getenv("CMF_DIAG") != nullptr && atoi(getenv("CMF_DIAG")) != 0;
-    if (const char *e = getenv("CMF_GEMM_PIPE")) { // A/B hook for the test-suite: staging schedule of the data-pass GEMMs
-        const int v = atoi(e);
-        if ((v >= 0 && v <= 5) || v == 10) c->opt_pipe = v;
-    }
     void *ds = nullptr;
     int rc = dev_alloc(c, &ds, 8 * sizeof(double));
     if (rc != CMF_OK) {
@@ -834,7 +722,7 @@ static void release_problem(cmf_ctx *c) {
     c->X = c->Y = nullptr;
     c->F[0] = c->F[1] = c->F[2] = nullptr;
     c->num = c->den = c->G = c->G2 = c->Hm = c->Hinv = c->Eye = c->vbuf = nullptr;
-    c->slabs = DevBuf(); c->slabs_b = DevBuf(); c->gslab32 = DevBuf(); c->slab_sel = 0; c->tickets = DevBuf(); c->narrow_tmp = DevBuf(); c->resid = DevBuf(); c->resid2 = DevBuf(); c->resid3 = DevBuf(); c->dpart = DevBuf();
+    c->slabs = DevBuf(); c->slabs_b = DevBuf(); c->gslab32 = DevBuf(); c->slab_sel = 0; c->narrow_tmp = DevBuf(); c->resid = DevBuf(); c->resid2 = DevBuf(); c->resid3 = DevBuf(); c->dpart = DevBuf();
     c->kr1 = DevBuf(); c->kr2 = DevBuf(); c->hrows = DevBuf(); c->mask1 = DevBuf(); c->mask2 = DevBuf();
     c->lists1 = DevBuf(); c->lists2 = DevBuf(); c->lists1s = DevBuf(); c->lists2s = DevBuf(); c->zerobuf = DevBuf(); c->lr_small = DevBuf(); c->lr_rows = DevBuf(); c->hpart = DevBuf();
     for (int q = 0; q < 2; ++q) { c->cls_idx[q] = DevBuf(); c->cls_off[q] = DevBuf(); c->cls_cnt[q] = DevBuf(); c->cls_pat[q] = DevBuf(); }
@@ -877,9 +765,6 @@ extern "C" int cmf_ctx_destroy(cmf_ctx *c) {
         pin_give(c->pin[b]);
         if (c->pin_ev[b]) (void)hipEventDestroy(c->pin_ev[b]);
     }
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return CMF_OK;
@@ -892,13 +777,8 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
         c->opt_graph = value < 0 ? -1 : (value != 0);
         return CMF_OK;
     }
-    if (!strcmp(name, "gemm_pipe")) {
-        if (value < 0 || (value > 5 && value != 10)) return fail(CMF_EINVAL, "gemm_pipe must be 0..5 or 10");
-        c->opt_pipe = (int)value;
-    } else if (!strcmp(name, "gemm_pipe_nt")) {
+    if (!strcmp(name, "gemm_pipe_nt")) {
         c->opt_pipe_nt = (int)value;
-    } else if (!strcmp(name, "gemm_pipe_small")) {
-        c->opt_pipe_small = (int)value;
     } else if (!strcmp(name, "gemm_split")) {
         c->opt_split = (int)value;
     } else if (!strcmp(name, "small_gram_shares")) {
@@ -907,30 +787,10 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
         c->opt_gram32 = value != 0;
     } else if (!strcmp(name, "chol_mfma")) {
         c->opt_chol_mfma = value != 0;
-    } else if (!strcmp(name, "side_gram")) {
-        c->opt_side_gram = value != 0;
-    } else if (!strcmp(name, "refine_spectral_map")) {
-        c->opt_refine_map = value != 0;
-    } else if (!strcmp(name, "gemm64_tile128")) {
-        c->opt_gemm64_tile128 = value != 0;
-    } else if (!strcmp(name, "nt_debug")) {
-        c->opt_nt_debug = (int)value;
-    } else if (!strcmp(name, "nt_bn256")) {
-        c->opt_nt_bn256 = value != 0;
-    } else if (!strcmp(name, "nt_raster")) {
-        c->opt_nt_raster = value != 0;
-    } else if (!strcmp(name, "nt_tile16")) {
-        c->opt_nt_tile16 = value != 0;
     } else if (!strcmp(name, "narrow_update")) {
         c->opt_narrow_update = value != 0;
-    } else if (!strcmp(name, "class_sum_depth")) {
-        c->opt_class_depth = (int)value;
     } else if (!strcmp(name, "pair_passes")) {
         c->opt_pair = (int)value; // 0: split launches | 1: paired data passes, U and Z updates in one launch | 2: paired data passes, separate updates
-    } else if (!strcmp(name, "gemm_tile512")) {
-        c->opt_tile512 = value != 0;
-    } else if (!strcmp(name, "gemm_rounds")) {
-        c->opt_rounds = (int)std::max<int64_t>(1, value);
     } else if (!strcmp(name, "z_logit_hessian_l2")) {
         c->opt_zlogit_l2 = value != 0;
     } else if (!strcmp(name, "row_diag")) {
@@ -983,16 +843,12 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
         c->opt_choldiag = (int)value;
     } else if (!strcmp(name, "safe_inverse_cholesky")) {
         c->opt_chol = value != 0;
-    } else if (!strcmp(name, "split_reduce_in_kernel")) {
-        c->opt_inred = value != 0;
     } else if (!strcmp(name, "small_tile_update")) {
         c->opt_small_tile = value != 0;
     } else if (!strcmp(name, "fused_mu_update")) {
         c->opt_fused_mu = value != 0;
     } else if (!strcmp(name, "shared_hessian_f64")) {
         c->opt_shared64 = value != 0;
-    } else if (!strcmp(name, "factor_times_tile")) {
-        c->opt_ft_tile = (value == 64 || value == 256) ? (int)value : 128;   // 64: 64 x 64 tile | 128: 64 x 128 | 256: 128 rows x 64 columns, eight waves
     } else if (!strcmp(name, "refine_rows")) {
         c->opt_refine = value != 0;
     } else if (!strcmp(name, "refine_rows_batched")) {
@@ -1507,10 +1363,9 @@ static void pair_shape(const cmf_ctx *c, const PairSide &sd, int64_t *mout, int6
     *mout = sd.trans ? cp : rp; *kred = sd.trans ? rp : cp;
 }
 // worth it when BOTH products would otherwise split their reduction (few output tiles against the CUs), and only on the plain
-// fp32 path the kernel restates (k_pad = 128, staging schedule 4, dense inputs, slabs summed by factor_update_kernel)
+// fp32 path the kernel restates (k_pad = 128, dense inputs, slabs summed by factor_update_kernel)
 static bool pair_ok(const cmf_ctx *c, const PairSide &a0, const PairSide &a1) {
-    if (!c->opt_pair || c->kp != 128 || !c->X || !c->Y || c->opt_arith || c->opt_pipe != 4 || c->opt_tile512 || c->opt_split > 0 ||
-        c->opt_inred || !c->opt_fused_mu || !c->opt_small_tile)
+    if (!c->opt_pair || c->kp != 128 || !c->X || !c->Y || c->opt_arith || c->opt_split > 0 || !c->opt_fused_mu || !c->opt_small_tile)
         return false;
     for (const PairSide *sd : {&a0, &a1}) {
         int64_t mout, kred;
@@ -1565,7 +1420,7 @@ extern "C" int cmf_mu_uz_update(cmf_ctx *c, double l1, double l2, int mask) {
     NEED_PROBLEM(c);
     DeviceGuard dg(c->device);
     if (!(mask & (CMF_UPD_U | CMF_UPD_Z))) return CMF_OK;
-    CHK(gram32(c, c->F[CMF_V], c->dp, c->G2, true));   // V^T V beside the first data pass of the U / Z updates
+    CHK(gram32(c, c->F[CMF_V], c->dp, c->G2));   // V^T V
     return mu_uz_update_with(c, c->G2, l1, l2, mask);
 }
 
@@ -1650,7 +1505,6 @@ static int mu_uz_update_with(cmf_ctx *c, const float *G2, double l1, double l2, 
         // X V and Y^T V (cmf_solvers.py:232, :238) read the same V: one balanced launch, then the two updates
         SlabRef su, sz;
         CHK(data_times_pair(c, xv, ytv, &su, &sz));
-        CHK(side_join(c));
         if (c->opt_pair == 2) { // A/B: the two updates as two launches
             CHK(mu_update(c, c->F[CMF_U], G2, c->num, c->mp, l1, l2, &su));
             return mu_update(c, c->F[CMF_Z], G2, c->num, c->pp, l1, l2, &sz);
@@ -1661,22 +1515,20 @@ static int mu_uz_update_with(cmf_ctx *c, const float *G2, double l1, double l2, 
         return factor_update2(c, c->F[CMF_U], eu, c->mp, c->F[CMF_Z], ez, c->pp, G2);
     }
     if (mask & CMF_UPD_U) {
-        if (!have_data(c, 0)) { (void)side_join(c); return fail(CMF_EINVAL, "X must be set before a U update"); }
+        if (!have_data(c, 0)) return fail(CMF_EINVAL, "X must be set before a U update");
         SlabRef sl;
         CHK(data_times(c, 0, false, c->F[CMF_V], c->num, false, (small_tile_ok(c, c->mp) && !c->mu_dots) ? &sl : nullptr));
-        CHK(side_join(c)); // G2 (when it was formed on the side stream)
         CHK(mu_update(c, c->F[CMF_U], G2, c->num, c->mp, l1, l2, &sl));
         if (c->mu_dots) CHK(factor_dot(c->F[CMF_U], c->mp * c->kp, c->dscalar + 2));
     }
     if (mask & CMF_UPD_Z) {
-        if (!have_data(c, 1)) { (void)side_join(c); return fail(CMF_EINVAL, "Y must be set before a Z update"); }
+        if (!have_data(c, 1)) return fail(CMF_EINVAL, "Y must be set before a Z update");
         SlabRef sl;
         CHK(data_times(c, 1, true, c->F[CMF_V], c->num, false, (small_tile_ok(c, c->pp) && !c->mu_dots) ? &sl : nullptr));
-        CHK(side_join(c));
         CHK(mu_update(c, c->F[CMF_Z], G2, c->num, c->pp, l1, l2, &sl));
         if (c->mu_dots) CHK(factor_dot(c->F[CMF_Z], c->pp * c->kp, c->dscalar + 3));
     }
-    return side_join(c);
+    return CMF_OK;
 }
 // cmf_mu_uz_update with V^T V supplied by the caller (the all-reduced sum of the ranks' cmf_mu_gram_v_rows)
 extern "C" int cmf_mu_uz_update_gram(cmf_ctx *c, const float *G2, double l1, double l2, int mask) {
@@ -1743,11 +1595,10 @@ static int mu_v_fused(cmf_ctx *c, double l1, double l2) {
     float *P = c->vbuf, *Gs = c->vbuf + c->dp * c->kp;
     SlabRef s1, s2;
     // the Gram first: its own split goes through slab set 0, which the deferred products below must own until the update
-    CHK(gram32(c, c->F[CMF_U], c->mp + c->pp, Gs, true));             // beside the data passes below; joined in front of the update
+    CHK(gram32(c, c->F[CMF_U], c->mp + c->pp, Gs));
     const PairSide xtu{0, true, c->F[CMF_U]}, yz{1, false, c->F[CMF_Z]};
     if (pair_ok(c, xtu, yz)) { // P = X^T U + Y Z (cmf_solvers.py:244) as one balanced launch, its partial tiles summed by the update
         CHK(data_times_pair(c, xtu, yz, &s1, &s2));
-        CHK(side_join(c));
         Epilogue e;
         e.kind = EPI_MU; e.F = c->F[CMF_V]; e.out = c->F[CMF_V]; e.a = l1; e.b = l2; e.c = 1.1920928955078125e-07;
         e.P = nullptr; e.Pslabs = &s1; e.Pslabs2 = &s2;
@@ -1764,7 +1615,6 @@ static int mu_v_fused(cmf_ctx *c, double l1, double l2) {
     } else {
         CHK(data_times(c, 1, false, c->F[CMF_Z], P, true));            // accumulate onto P as usual
     }
-    CHK(side_join(c));
     Epilogue e;
     e.kind = EPI_MU; e.F = c->F[CMF_V]; e.out = c->F[CMF_V]; e.a = l1; e.b = l2; e.c = 1.1920928955078125e-07;
     e.P = direct; e.Pslabs = &s1; e.Pslabs2 = &s2;
@@ -1801,7 +1651,7 @@ extern "C" int cmf_residual_sq(cmf_ctx *c, int x_link, int y_link, double *ex2, 
             CHK(sparse_residual_sq(c, 0, c->dscalar, x_link));
         } else {
             CHK(need_dense(c, 0));
-            NtOut o; o.T = c->opt_nt_debug & 1 ? nullptr : c->X; o.ldt = c->dp; o.sq = c->dscalar; o.link = x_link;
+            NtOut o; o.T = c->X; o.ldt = c->dp; o.sq = c->dscalar; o.link = x_link;
             CHK(gemm_nt(c, c->F[CMF_U], c->mp, c->m, c->F[CMF_V], c->dp, c->d, o));
         }
     }
@@ -1810,7 +1660,7 @@ extern "C" int cmf_residual_sq(cmf_ctx *c, int x_link, int y_link, double *ex2, 
             CHK(sparse_residual_sq(c, 1, c->dscalar + 1, y_link));
         } else {
             CHK(need_dense(c, 1));
-            NtOut o; o.T = c->opt_nt_debug & 1 ? nullptr : c->Y; o.ldt = c->pp; o.sq = c->dscalar + 1; o.link = y_link;
+            NtOut o; o.T = c->Y; o.ldt = c->pp; o.sq = c->dscalar + 1; o.link = y_link;
             CHK(gemm_nt(c, c->F[CMF_V], c->dp, c->d, c->F[CMF_Z], c->pp, c->p, o));
         }
     }

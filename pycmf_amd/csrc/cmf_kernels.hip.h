@@ -46,19 +46,14 @@ struct GemmArgs {
     float scale_r, scale_w;
     int link;            // 0 linear, 1 logit
     int w_is_slope;      // W = scale_w * sigma'(S) (1) or scale_w (0)
-    // XCD-aware tile order of the NT passes (ras_rb > 0): see the remap at the top of gemm_kernel
-    int ras_rb, ras_cb;
     unsigned long long *dbg; // diagnostic only: per-workgroup {memtime, memrealtime} at start and end (nullable)
     // ---- ROLE 2 (block-diagonal batch of k_pad = 256 products, NN form): row tile x multiplies its own B ----
     int64_t b_batch;     // elements between the B operands of consecutive row tiles
     const float *D;      // C = alpha * A B + beta * D + gamma * I  (D stacked like C, nullable)
     float alpha, beta, gamma;
-    // ---- in-kernel split-K reduction (NN / TN): red_out != null ----
-    // every split writes its partial tile to slab z of C (write-through stores) and takes a ticket of its output tile; the
-    // workgroup that arrives last sums the slabs IN SLAB ORDER (deterministic) into red_out (+= when red_acc).
-    // A single split writes (or adds) straight into red_out.
+    // ---- unsplit accumulate (NN / TN): red_out != null ----
+    // the single split writes (red_acc: adds) its tile straight into red_out instead of a slab of C
     float *red_out;
-    unsigned *ticket;    // one zero-initialised word per output tile; reset by the last arriver
     int red_acc;
     // ---- fused factor update (NN, factor-side product with one N tile): epi != 0 ----
     //  EPI_MU     acc = F G is the MU denominator: F <- F * P / reg(acc)                    (cmf_solvers.py:212-228)
@@ -79,18 +74,7 @@ struct GemmArgs {
 };
 enum { EPI_NONE = 0, EPI_MU = 1, EPI_GRAD = 2, EPI_APPLY = 3, EPI_DIRECT = 4, EPI_COMBINE = 5 };
 
-// write-through (sc1) stores: the bytes leave the XCD's L2 at once, so a workgroup on another XCD can read them after
-// the storing wave's s_waitcnt vmcnt(0) and a ticket, with no release fence (MI355X_MICROARCH.md, publish-large)
-__device__ __forceinline__ void store_wt(float *p, f32x4 v) { asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
-__device__ __forceinline__ void store_wt(float *p, f32x2 v) { asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
-typedef float f32x1 __attribute__((ext_vector_type(1)));
-__device__ __forceinline__ void store_wt(float *p, f32x1 v) { asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v[0]) : "memory"); }
-__device__ __forceinline__ void store_wt(float *p, float v) { asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
-
-// TILE 0: 256 x BN output tile, 32-deep K-step (everything).  TILE 1 (BN = 128 data passes, A/B option gemm_tile512): 512 x 128
-// output tile, 16-deep K-step -- wave tile 128 x 64 like the 256 x 256 kernel's 64 x 128 (six fragment reads per eight MFMAs
-// instead of four per four, half the B-tile fill per flop), the same MFMA work per barrier as the 256 x 128 x 32 step, and
-// 98 KB of LDS double-buffered (a 32-deep step of this tile would need 180 KB).  TILE 2 (NT form, option nt_tile16): the 256 x 128
+// TILE 0: 256 x BN output tile, 32-deep K-step (NN / TN).  TILE 2 (NT form): the 256 x 128
 // output tile with a 16-deep K-step -- 61 KB of LDS instead of 110, so that TWO workgroups share a CU: the NT passes reduce over
 // K = k_pad only (8 K-steps of 32 at k_pad = 256), a third of a workgroup's life is the fill in front of the first MFMA and the
 // epilogue behind the last one (targets from HBM, link, squared residual), and with one workgroup per CU the matrix pipe idles
@@ -99,7 +83,7 @@ constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
 
 template <int MODE, int BN, int TILE = 0>
 struct GemmCfg {
-    static constexpr int BM = TILE == 1 ? 512 : 256, BK = TILE ? 16 : 32, PADK = BK + 4, NT = 512;
+    static constexpr int BM = 256, BK = TILE ? 16 : 32, PADK = BK + 4, NT = 512;
     static constexpr bool A_KC = (MODE != MODE_TN);
     static constexpr bool B_KC = (MODE == MODE_NT);
     static constexpr int A_ELEMS = A_KC ? BM * PADK : BK * BM;
@@ -183,27 +167,19 @@ struct VecLoad<4> {
 // ROLE 2 (NN, BN = 256 only) is the batched 256 x 256 x 256 product of the Newton-Schulz spectral clamp: the
 // matrices of a batch are stacked vertically, row tile x = matrix x reads ITS B operand (B + x * b_batch) and the
 // epilogue forms alpha * A B + beta * D + gamma * I.
-// PIPE selects the staging schedule inside a K-step (A/B-able in one process, cmf_set_option):
-//   0: global loads of tile t+1 at group 0, all LDS writes as a burst after group 15
-//   1: LDS writes of tile t+1 one piece per group in groups 0..7, loads of tile t+2 at group 8
-//   2: LDS writes two pieces per group in groups 0..3, loads of tile t+2 at group 4
-//   3: LDS writes four pieces per group in groups 0..1, loads of tile t+2 at group 2
-//   4: all eight LDS writes in group 0, loads of tile t+2 at group 1
-//   5: schedule 4 with waves 4-7 staging half a K-step later than waves 0-3 (stagger)
-//  10: direct-to-LDS loads of tile t+1 at group 0 (no staging registers, no ds_write): TN +1 %, NN -5 %
+// PIPE, like ROLE, only names the symbol now: the staging schedule inside a K-step is schedule 4 -- all LDS writes of
+// tile t+1 in MFMA group 0, the global loads of tile t+2 at group 1 -- except that the NT form may still run schedule 0
+// (option gemm_pipe_nt = 0: loads of tile t+1 at group 0, LDS writes as a burst behind the last group).
 // Diagnostic builds (not kept): no staging at all 153-154 TF/s (98 %), LDS writes only 146-147, no barrier +0.5 %:
 // the 7 % between schedule 4 and the bare MFMA+fragment loop is the 64 KB/step of LDS fill traffic and the
-// global loads themselves, not where in the step they are issued.
-// (also tried and dropped: piece p written in group p and re-loaded at once: -1..-3 %; one piece in the shadow
-//  of each MFMA: -25 %, hipcc's conservative waitcnts serialise it; wave specialisation, 12 waves with one
-//  loader wave per SIMD doing all the staging and the 8 MFMA waves only reading fragments: 131/121 TF/s NN/TN
-//  with direct-to-LDS loads, 131/136 with register staging, against 142.5/141.7 for schedule 4 - a third wave
-//  per SIMD costs more than the staging instructions it takes off the MFMA waves)
+// global loads themselves, not where in the step they are issued.  The schedules and designs that lost against it
+// are listed in DESIGN.md, "Retired knobs".
 template <int MODE, int BN, int ROLE = 0, int PIPE = 0, int TILE = 0>
 __global__ __launch_bounds__(512, TILE == 2 ? 4 : 2) void gemm_kernel(GemmArgs g) {
     using C = GemmCfg<MODE, BN, TILE>;
-    static_assert(TILE == 0 || (TILE == 1 && BN == 128 && MODE != MODE_NT && ROLE == 0 && PIPE == 4) || (TILE == 2 && BN == 128 && MODE == MODE_NT),
-                  "the 512 x 128 x 16 tile: k_pad = 128 data passes only; the 256 x 128 x 16 tile: NT passes only");
+    static_assert(PIPE == 4 || (PIPE == 0 && MODE == MODE_NT), "schedule 4; schedule 0 for the NT form only");
+    static_assert((TILE == 0 && MODE != MODE_NT) || (TILE == 2 && BN == 128 && MODE == MODE_NT),
+                  "the 256 x BN x 32 tile: NN / TN; the 256 x 128 x 16 tile: NT passes");
     // (shifts and masks, not / and %: with the signed division hipcc stopped folding the four A-tile LDS addresses of a thread into
     // one base + immediate offsets, and that alone cost the TN pass 2.7 % and 0.5 GB of extra operand fetch per launch at C4 --
     // profiles/HISTORY.md, round 4, A/B of the library builds)
@@ -218,25 +194,8 @@ __global__ __launch_bounds__(512, TILE == 2 ? 4 : 2) void gemm_kernel(GemmArgs g
     const int wm = wid / C::WN, wn = wid % C::WN;
     const int wrow0 = wm * C::WTM, wcol0 = wn * C::WTN;
 
-    // NT passes reduce over K = k_pad only: a 256 x 128 tile reads 384 KB of factor rows for 16.8 MFLOP, and in launch order (row
-    // tile fastest, workgroups dealt round-robin over the XCDs) the 32 workgroups an XCD runs at a time touch 32 DIFFERENT row tiles
-    // (8 MB against 4 MB of L2): every operand byte comes from beyond L2, 2.5 TB/s at C4.  With ras_rb > 0 the workgroups that share
-    // an XCD (linear id mod 8, speed only -- nothing depends on the placement) walk their own eighth of the column tiles in blocks
-    // of ras_rb row tiles x ras_cb column tiles: 1 MB + 1 MB of operands per 32 tiles, re-read from the XCD's L2.
-    unsigned tile_x = blockIdx.x, tile_y = blockIdx.y;
-    if constexpr (MODE == MODE_NT) {
-        if (g.ras_rb > 0) {
-            const unsigned lin = blockIdx.y * gridDim.x + blockIdx.x;
-            const unsigned xcd = lin & 7u, q = lin >> 3;
-            const unsigned per_x = gridDim.y >> 3, blk = (unsigned)(g.ras_rb * g.ras_cb);
-            const unsigned b = q / blk, w = q % blk;
-            const unsigned nrb = gridDim.x / (unsigned)g.ras_rb;
-            tile_x = (b % nrb) * (unsigned)g.ras_rb + w % (unsigned)g.ras_rb;
-            tile_y = xcd * per_x + (b / nrb) * (unsigned)g.ras_cb + w / (unsigned)g.ras_rb;
-        }
-    }
-    const int64_t row0 = (int64_t)tile_x * C::BM; // output-row tile origin
-    const int64_t n0 = (int64_t)tile_y * BN;      // output-col tile origin
+    const int64_t row0 = (int64_t)blockIdx.x * C::BM; // output-row tile origin
+    const int64_t n0 = (int64_t)blockIdx.y * BN;      // output-col tile origin
     const int64_t kbeg = (int64_t)blockIdx.z * g.klen;
     int64_t kend = kbeg + g.klen;
     if (kend > g.Kred) kend = g.Kred;
@@ -332,77 +291,22 @@ __global__ __launch_bounds__(512, TILE == 2 ? 4 : 2) void gemm_kernel(GemmArgs g
         for (int p = 0; p < C::A_LD + C::B_LD; ++p) lstore_piece(As, Bs, p);
     };
 
-    // One K-step = 16 MFMA groups (one per k-pair).  Software pipeline inside the step:
+    // One K-step = NGRP MFMA groups (one per k-pair).  Software pipeline inside the step:
     //  * fragment reads of group s+1 are issued before the MFMAs of group s (register double
     //    buffer), so LDS latency sits under 8-16 MFMAs of 64 cycles;
     //  * the staged registers of tile t+1 (loaded during step t-1) are written to the other LDS
-    //    buffer one 16-byte piece per group in groups 0..7, i.e. under MFMAs instead of as a
-    //    burst in front of the barrier;
-    //  * the global loads of tile t+2 are issued at group 8 into the registers just drained.
+    //    buffer in group 0, i.e. under MFMAs instead of as a burst in front of the barrier;
+    //  * the global loads of tile t+2 are issued at group 1 into the registers just drained.
     // sched_barrier(0) pins that order (hipcc otherwise re-serialises reads and MFMAs).
-    const bool late = __builtin_amdgcn_readfirstlane(wid) >= 4; // wave-uniform by construction
-    // PIPE 10: direct-to-LDS loads (global_load_lds_dwordx4): no staging registers, no ds_write.  The LDS
-    // image must then be lane-linear, so the k-contiguous A tile of the NN form loses its row padding and is
-    // XOR-swizzled instead (16-byte chunk c of row r lives at chunk c ^ (r & 7)); the permutation is applied to
-    // the per-lane SOURCE address and again on the fragment read.
-    constexpr bool GLDS = (PIPE == 10);
-    static_assert(!GLDS || TILE == 0, "direct-to-LDS staging is laid out for the 256-row tile");
-    constexpr int APK = GLDS ? C::BK : C::PADK; // floats per row of a k-contiguous A tile
-    auto glds_tile = [&](float *As, float *Bs, int64_t k0) {
-        typedef __attribute__((address_space(3))) float lds_f;
-#pragma unroll
-        for (int p = 0; p < C::A_LD; ++p) {
-            const int idx = t + C::NT * p;
-            const int wave_first = __builtin_amdgcn_readfirstlane(idx & ~63);
-            const float *src;
-            if constexpr (C::A_KC) {
-                const int r = idx >> 3, cpos = idx & 7;
-                src = g.A + (row0 + r) * g.lda + k0 + 4 * (cpos ^ (r & 7));
-            } else {
-                const int r = idx >> 6, c4 = idx & 63;
-                int64_t col = row0 + 4 * c4;
-                if (ROLE == 1 && col > g.Mout - 4) col = g.Mout - 4;
-                src = g.A + (k0 + r) * g.lda + col;
-            }
-            __builtin_amdgcn_global_load_lds(src, (lds_f *)(As + 4 * wave_first), 16, 0, 0);
-        }
-#pragma unroll
-        for (int p = 0; p < C::B_LD; ++p) {
-            const int idx = t + C::NT * p;
-            if (C::B_F4 >= C::NT || idx < C::B_F4) {
-                const int wave_first = __builtin_amdgcn_readfirstlane(idx & ~63);
-                constexpr int F4R = BN / 4;
-                const int r = idx / F4R, c4 = idx % F4R;
-                const float *src = Bbase + (k0 + r) * g.ldb + n0 + 4 * c4;
-                __builtin_amdgcn_global_load_lds(src, (lds_f *)(Bs + 4 * wave_first), 16, 0, 0);
-            }
-        }
-    };
     auto compute = [&](const float *As, const float *Bs, float *nAs, float *nBs, bool do_write, bool do_load,
                        int64_t next_k0) {
         auto side = [&](int sidx) {
             if constexpr (PIPE == 0) {
                 if (sidx == 0 && do_load) gload(next_k0);
-            } else if constexpr (PIPE == 10) {
-                if (sidx == 0 && do_write) glds_tile(nAs, nBs, next_k0); // next_k0 = tile t+1 here
-            } else if constexpr (PIPE == 5) {
-                // schedule 4 with the two waves of every SIMD staggered by half a K-step: waves 0-3 stage in
-                // groups 0/1, waves 4-7 in groups 8/9, so one wave's staging sits beside its partner's MFMAs
-                const int g0 = late ? 8 : 0;
-                if (sidx == g0) {
-                    if (do_write) lstore(nAs, nBs);
-                } else if (sidx == g0 + 1) {
-                    if (do_load) gload(next_k0);
-                }
             } else {
-                constexpr int WPG = 1 << (PIPE - 1); // LDS-write pieces per group: 1, 2 or 4
-                constexpr int NG = 8 / WPG;          // groups that carry writes; loads go at group NG
-                if (sidx < NG) {
-                    if (do_write) {
-#pragma unroll
-                        for (int w = 0; w < WPG; ++w) lstore_piece(nAs, nBs, WPG * sidx + w);
-                    }
-                } else if (sidx == NG) {
+                if (sidx == 0) {
+                    if (do_write) lstore(nAs, nBs);
+                } else if (sidx == 1) {
                     if (do_load) gload(next_k0);
                 }
             }
@@ -413,8 +317,7 @@ __global__ __launch_bounds__(512, TILE == 2 ? 4 : 2) void gemm_kernel(GemmArgs g
 #pragma unroll
                 for (int i = 0; i < C::TM; ++i) {
                     const int row = wrow0 + 32 * i + l31;
-                    const int chunk = GLDS ? ((2 * q + lh) ^ (row & 7)) : (2 * q + lh);
-                    dst[i] = *reinterpret_cast<const f32x4 *>(As + row * APK + 4 * chunk);
+                    dst[i] = *reinterpret_cast<const f32x4 *>(As + row * C::PADK + 4 * (2 * q + lh));
                 }
             };
             if constexpr (C::B_KC) {
@@ -474,7 +377,7 @@ __global__ __launch_bounds__(512, TILE == 2 ? 4 : 2) void gemm_kernel(GemmArgs g
             // every fragment address with four vector adds per MFMA group; from a pinned base the 16 groups are one register
             // plus immediate offsets, as in the 256-wide build (which folds them by itself and is left exactly as it was).
             typedef __attribute__((address_space(3))) const float lds_cf;
-            constexpr bool PIN = (BN == 128 && TILE == 0);
+            constexpr bool PIN = (BN == 128);
             lds_cf *Ap = (lds_cf *)(As + lh * C::BM + wrow0 + C::TM * l31);
             lds_cf *Bp = (lds_cf *)(Bs + lh * BN + wcol0 + C::TN * l31);
             if constexpr (PIN) asm volatile("" : "+v"(Ap), "+v"(Bp));
@@ -508,21 +411,7 @@ __global__ __launch_bounds__(512, TILE == 2 ? 4 : 2) void gemm_kernel(GemmArgs g
         }
     };
 
-    if constexpr (GLDS) {
-        static_assert(MODE != MODE_NT, "direct-to-LDS staging is wired for the NN / TN forms");
-        if (nkt > 0) {
-            glds_tile(smem, smem + C::A_ELEMS, kbeg);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            for (int kt = 0; kt < nkt; ++kt) {
-                float *cur = smem + (kt & 1) * C::STAGE;
-                float *nxt = smem + ((kt + 1) & 1) * C::STAGE;
-                compute(cur, cur + C::A_ELEMS, nxt, nxt + C::A_ELEMS, kt + 1 < nkt, false, kbeg + (int64_t)(kt + 1) * C::BK);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-            }
-        }
-    } else if (nkt > 0) {
+    if (nkt > 0) {
         gload(kbeg);
         lstore(smem, smem + C::A_ELEMS);
         if (PIPE != 0 && nkt > 1) gload(kbeg + C::BK); // tile 1 waits in registers
@@ -551,8 +440,7 @@ __global__ __launch_bounds__(512, TILE == 2 ? 4 : 2) void gemm_kernel(GemmArgs g
     // ---------------------------------------------------------------- epilogue
     if constexpr (MODE != MODE_NT) {
         typedef float vecN __attribute__((ext_vector_type(C::TN)));
-        const int nsplit = (int)gridDim.z;
-        const bool in_red = g.red_out != nullptr;
+        const bool in_red = g.red_out != nullptr; // unsplit accumulate: this tile goes straight into red_out
         if (ROLE == 1 && MODE == MODE_NN && g.epi != EPI_NONE) {
             // fused factor update.  F and the second operand of EIGHT rows are fetched before any arithmetic: one latency per
             // batch instead of one per row
@@ -607,7 +495,7 @@ __global__ __launch_bounds__(512, TILE == 2 ? 4 : 2) void gemm_kernel(GemmArgs g
                     }
                 }
         } else {
-            float *Cs = (in_red && nsplit == 1) ? g.red_out : g.C + (int64_t)blockIdx.z * g.slab_stride;
+            float *Cs = in_red ? g.red_out : g.C + (int64_t)blockIdx.z * g.slab_stride;
 #pragma unroll
             for (int i = 0; i < C::TM; ++i)
 #pragma unroll
@@ -630,71 +518,11 @@ __global__ __launch_bounds__(512, TILE == 2 ? 4 : 2) void gemm_kernel(GemmArgs g
                             vecN v;
 #pragma unroll
                             for (int j = 0; j < C::TN; ++j) v[j] = acc[i][j][r];
-                            if (in_red && nsplit == 1) {
-                                if (g.red_acc) v += *reinterpret_cast<const vecN *>(dst);
-                                *reinterpret_cast<vecN *>(dst) = v;
-                            } else if (in_red) {
-                                store_wt(dst, v);
-                            } else {
-                                *reinterpret_cast<vecN *>(dst) = v;
-                            }
+                            if (in_red && g.red_acc) v += *reinterpret_cast<const vecN *>(dst);
+                            *reinterpret_cast<vecN *>(dst) = v;
                         }
                     }
                 }
-        }
-        if (ROLE != 2 && in_red && nsplit > 1) {
-            // ticket: the last of the nsplit workgroups of this output tile reduces (Guideline 16: every storing wave drains
-            // its write-through stores, workgroup barrier, ONE agent-scope atomic add; the last arriver acquires once)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            unsigned *tk = g.ticket + (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-            int *flag = reinterpret_cast<int *>(smem);
-            if (t == 0) {
-                const unsigned old = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const int last = (old == (unsigned)(nsplit - 1)) ? 1 : 0;
-                if (last) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // ready for the next launch
-                }
-                *flag = last;
-            }
-            __syncthreads();
-            if (*flag) {
-                // 16 independent row segments in flight per thread and slab (a dependent chain of single loads made
-                // this reduction latency-bound: 100 us for 1 MB)
-#pragma unroll
-                for (int i = 0; i < C::TM; ++i) {
-                    vecN sum[16];
-                    int64_t offs[16];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        int64_t row = row0 + wrow0 + (C::A_KC ? (32 * i + rr) : (C::TM * rr + i));
-                        if (row >= g.Mout) row = g.Mout - 1; // clamped: loaded, never stored
-                        offs[r] = row * g.ldc + n0 + wcol0 + C::TN * l31;
-                        if (g.red_acc) sum[r] = *reinterpret_cast<const vecN *>(g.red_out + offs[r]);
-                        else {
-#pragma unroll
-                            for (int j = 0; j < C::TN; ++j) sum[r][j] = 0.f;
-                        }
-                    }
-                    for (int sidx = 0; sidx < nsplit; ++sidx) {
-                        const float *slab = g.C + (int64_t)sidx * g.slab_stride;
-                        vecN part[16];
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) part[r] = *reinterpret_cast<const vecN *>(slab + offs[r]);
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) sum[r] += part[r];
-                    }
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        const int64_t row = row0 + wrow0 + (C::A_KC ? (32 * i + rr) : (C::TM * rr + i));
-                        if (row < g.Mout) *reinterpret_cast<vecN *>(g.red_out + offs[r]) = sum[r];
-                    }
-                }
-            }
         }
     } else {
         float sq = 0.0f;
@@ -713,8 +541,8 @@ __global__ __launch_bounds__(512, TILE == 2 ? 4 : 2) void gemm_kernel(GemmArgs g
             // no byte mask (everything but the masked-dense Newton formulation): fetch ALL targets of the wave tile
             // first -- one latency for 64 loads in flight instead of 64 dependent load -> wait -> use rounds, which
             // made this epilogue longer than the 8 K-steps in front of it -- then the arithmetic
-            // (TILE 2 -- two workgroups per CU, 128 registers per lane: one block row of the wave tile at a time, 32 loads in flight)
-            constexpr int IB = (TILE == 2 || BN == 256) ? 1 : C::TM;   // block rows per batch (256-wide tile: 64 of its 128 targets per lane at a time)
+            // (two workgroups per CU, 128 registers per lane: one block row of the wave tile at a time, 32 loads in flight)
+            constexpr int IB = 1;   // block rows per batch
             const float slope = g.w_is_slope ? 1.0f : 0.0f, nslope = 1.0f - slope;
 #pragma unroll
             for (int i0 = 0; i0 < C::TM; i0 += IB) {

@@ -764,9 +764,8 @@ static bool use_reassoc(const cmf_ctx *c) { return c->opt_reassoc && c->opt_shar
 static int factor_times_hinv(cmf_ctx *c, const float *O, int64_t rows_pad, double scale, float *out) {
     Timed tm(c, CMF_K_GEMM_SMALL, 2.0 * (double)rows_pad * c->kp * c->kp);
     if (c->kp == 32) hipLaunchKernelGGL((factor_times64_kernel<32>), dim3(1, (unsigned)(rows_pad / 64)), dim3(256), 0, c->stream, O, (const double *)c->hinv64.p, out, c->kp, scale);
-    else if (c->kp >= 64 && c->opt_ft_tile == 256 && rows_pad % 128 == 0) hipLaunchKernelGGL((factor_times64_kernel<64, 128>), dim3((unsigned)(c->kp / 64), (unsigned)(rows_pad / 128)), dim3(512), 0, c->stream, O, (const double *)c->hinv64.p, out, c->kp, scale);
-    else if (c->kp >= 128 && c->opt_ft_tile == 128) hipLaunchKernelGGL((factor_times64_kernel<128>), dim3((unsigned)(c->kp / 128), (unsigned)(rows_pad / 64)), dim3(256), 0, c->stream, O, (const double *)c->hinv64.p, out, c->kp, scale);
-    else hipLaunchKernelGGL((factor_times64_kernel<64>), dim3((unsigned)(c->kp / 64), (unsigned)(rows_pad / 64)), dim3(256), 0, c->stream, O, (const double *)c->hinv64.p, out, c->kp, scale);
+    // (factor rows are padded to a multiple of 256 -- cmf_set_problem -- so the 128-row tile always divides them)
+    else hipLaunchKernelGGL((factor_times64_kernel<64, 128>), dim3((unsigned)(c->kp / 64), (unsigned)(rows_pad / 128)), dim3(512), 0, c->stream, O, (const double *)c->hinv64.p, out, c->kp, scale);
     HIPCHK(hipGetLastError());
     return CMF_OK;
 }
@@ -1669,7 +1668,7 @@ static int refine_rows64_batched(cmf_ctx *c, int which, const RowSide &s1, const
             // float64 products PER ROW here)
             const double delta = 1e-5 * pert;
             const dim3 gg((unsigned)(kp / 32), (unsigned)(kp / 32), (unsigned)ncl);
-            // Spectral map in front of the sign iteration (option refine_spectral_map).  H is positive semi-definite, so B = H - pert I
+            // Spectral map in front of the sign iteration.  H is positive semi-definite, so B = H - pert I
             // has its spectrum in [-pert, ||H||]: ||H|| / pert is 1e3 ... 1e4 here, and the growth phase spends log_3.44 of that ratio
             // in steps just to bring the eigenvalues near the threshold up from delta / ||H||.  f(lambda) = (lambda - pert) /
             // (lambda + pert) is increasing with f(pert) = 0, so sign(f(H)) = sign(B), and it maps [0, inf) into [-1, 1): the start
@@ -1677,7 +1676,7 @@ static int refine_rows64_batched(cmf_ctx *c, int which, const RowSide &s1, const
             // Cost: one batched register Cholesky of H + pert I, its triangular inverse, one product -- against six growth steps
             // (eighteen products) saved at ||H|| / pert = 2600.
             bool mapped = false;
-            if (c->opt_refine_map && n > 64) {
+            if (n > 64) {
                 int *mflag0 = dflag; // (the flags of the threshold test were read above)
                 if (n <= 128) hipLaunchKernelGGL((chol64_reg_kernel<4>), dim3((unsigned)ncl), dim3(1024), 0, c->stream, (const double *)Hc, n, kp, Y, kk, kp, -pert, -pert, mflag0, kk, 1);
                 else hipLaunchKernelGGL((chol64_reg_kernel<8>), dim3((unsigned)ncl), dim3(1024), 0, c->stream, (const double *)Hc, n, kp, Y, kk, kp, -pert, -pert, mflag0, kk, 1);
@@ -1700,7 +1699,7 @@ static int refine_rows64_batched(cmf_ctx *c, int which, const RowSide &s1, const
             int nq = (int)std::ceil(std::log(mapped ? 2.0 * pert / delta : hmax / delta) / std::log(3.4445));
             nq = std::min(std::max(nq, 4), 48);
             auto mm = [&](const double *A, const double *B, double *Cc, const double *D, double al, double be, double ga) {
-                if (c->opt_gemm64_tile128 && kp % 128 == 0 &&
+                if (kp % 128 == 0 &&
                     allow_big_lds(c, reinterpret_cast<const void *>(&gemm64_tile128_kernel), GEMM64_TILE128_LDS) == CMF_OK)
                     hipLaunchKernelGGL(gemm64_tile128_kernel, dim3((unsigned)(kp / 128), (unsigned)(kp / 128), (unsigned)ncl), dim3(512), GEMM64_TILE128_LDS, c->stream, A, B, Cc, D, al, be, ga, kp, (int64_t)kk);
                 else
@@ -1895,13 +1894,8 @@ static int fused_rows_finish(cmf_ctx *c, int which, const RowSide &s1, const Row
                             certimg = (float *)c->certimg.p;
                         }
                         const unsigned grid = (unsigned)std::min<int64_t>(ng * 36, (int64_t)c->num_cu * 16);
-#define CMF_CLASS_SUM(NB_)                                                                                                     \
-    hipLaunchKernelGGL(class_sum_blocks_kernel<NB_>, dim3(grid), dim3(256), 0, c->stream, Hc, (const float *)c->hclass.p,      \
-                       have_h ? nullptr : S, have_h ? 0.f : (float)diag, nr, R, c->k, have_h ? 1 : 0, certimg, split)
-                        if (c->opt_class_depth >= 16) CMF_CLASS_SUM(16);
-                        else if (c->opt_class_depth >= 8) CMF_CLASS_SUM(8);
-                        else CMF_CLASS_SUM(4);
-#undef CMF_CLASS_SUM
+                        hipLaunchKernelGGL(class_sum_blocks_kernel<4>, dim3(grid), dim3(256), 0, c->stream, Hc, (const float *)c->hclass.p,
+                                           have_h ? nullptr : S, have_h ? 0.f : (float)diag, nr, R, c->k, have_h ? 1 : 0, certimg, split);
                         if (want_cert) {
                             cert.flags = (const int *)c->certflag.p; cert.rows = R; cert.split = split;
                         }

@@ -34,8 +34,11 @@ def test_call_order_and_arguments(lib):
         ctx.newton_step(0.5, 0, 0, "linear", "linear", 7, 7, 0.2, 0.5)   # ratio < 1 without lists
     with pytest.raises(ValueError, match="unknown option"):
         ctx.set_option("no_such_knob", 1)
-    with pytest.raises(ValueError, match="gemm_pipe must be"):
-        ctx.set_option("gemm_pipe", 99)
+    with pytest.raises(ValueError, match="spmm_blocked must be"):
+        ctx.set_option("spmm_blocked", 99)
+    for retired in ("gemm_pipe", "side_gram"):
+        with pytest.raises(ValueError, match="unknown option"):
+            ctx.set_option(retired, 1)
     with pytest.raises(ValueError, match="gemm_arith must be"):
         ctx.set_option("gemm_arith", 2)
     with pytest.raises(ValueError, match="operand has 5 rows, expected 3"):

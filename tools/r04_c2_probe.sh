@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round 4: where the C2 iteration's time is -- per-launch durations of the four data passes (rocprofv3 kernel trace), then the
-# staging schedules / tile options as bench lines
+# interleaved A/B of the library builds
 set -u
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/r04_c2_probe
@@ -34,17 +34,3 @@ for i in range(i0, len(seq)):
 PY
 python3 tools/ab_lib_versions.py 16384,8192,4096,128 60 > "$O/ab_pin.txt" 2>&1; tail -n 3 "$O/ab_pin.txt"
 python3 tools/ab_lib_versions.py 16384,8192,4096,128 60 > "$O/ab_pin2.txt" 2>&1; tail -n 3 "$O/ab_pin2.txt"
-for pipe in 0 1 2 3 4 5 10; do
-  python3 bench.py --workload c2 --steps 300 --warmup 30 --no-cpu-baseline --option gemm_pipe=$pipe > "$O/bench_pipe$pipe.json" 2> "$O/bench_pipe$pipe.err"
-done
-python3 bench.py --workload c2 --steps 300 --warmup 30 --no-cpu-baseline --option gemm_tile512=1 > "$O/bench_tile512.json" 2> "$O/bench_tile512.err"
-python3 bench.py --workload c2 --steps 300 --warmup 30 --no-cpu-baseline --option split_reduce_in_kernel=1 > "$O/bench_inred.json" 2> "$O/bench_inred.err"
-python3 - <<PY
-import json, glob
-for f in sorted(glob.glob("$O/bench_*.json")):
-    try:
-        d = json.loads(open(f).read().strip().splitlines()[-1])
-        print(f.split('/')[-1], "it/s %.1f ms %.4f" % (d["value"], d["ms_per_step"]), {k: round(v, 4) for k, v in d["roofline"]["per_class_ms_per_step"].items()})
-    except Exception as e:
-        print(f, "ERR", e, open(f.replace('.json', '.err')).read()[-400:])
-PY

@@ -1,12 +1,12 @@
 #!/bin/bash
-# Round 4: C2 with the paired launch -- small Grams on the side stream, row shares, graph replay (one box, alternating)
+# Round 4: C2 with the paired launch -- row shares, graph replay (one box, alternating)
 set -u
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/r04_step13
 mkdir -p "$O"
 cd "$R"
 i=0
-for opt in "pair_passes=1" "side_gram=1" "small_gram_shares=64" "graph=1" "pair_passes=1" "side_gram=1" "small_gram_shares=16" "graph=1"; do
+for opt in "pair_passes=1" "small_gram_shares=64" "graph=1" "pair_passes=1" "small_gram_shares=16" "graph=1"; do
   i=$((i+1))
   timeout 300 python3 bench.py --workload c2 --steps 300 --warmup 30 --no-cpu-baseline --option $opt > "$O/bench_${i}_$opt.json" 2> "$O/bench_${i}_$opt.err"
 done

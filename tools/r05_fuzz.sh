@@ -29,7 +29,7 @@ for tag in ("fuzz_r05", "fuzz_r05_pair"):
     opts = collections.Counter()
     for r in cases:
         for n, v in r["case"]["options"].items():
-            if n in ("nt_tile16", "nt_bn256", "nt_raster", "gemm64_tile128", "narrow_update", "refine_rows_batched", "chol_mfma", "pair_passes"):
+            if n in ("narrow_update", "refine_rows_batched", "chol_mfma", "pair_passes"):
                 opts["%s=%d" % (n, v)] += 1
     worst = sorted(cases, key=lambda r: -(max(r["err"]) if "err" in r else 9e9))[:3]
     out[tag] = {"groups": groups, "option_draws": dict(opts), "bad_cases": [r for r in cases if r["bad"]][:10],
