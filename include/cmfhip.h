@@ -104,7 +104,8 @@ int cmf_sync(cmf_ctx *ctx);
  * "row_certificates" 1 (default) | 0: half such a group shares one threshold test of _safe_invert (cmf_solvers.py:346-356)
  * through the positive semi-definite part of their Hessians the rows have in common | every row runs its own,
  * "topk_split" n: cmf_topk / cmf_topk_queries cut the candidates into n shares (<= 0, default: as many as fill the chip); the
- * result does not depend on it,
+ * result does not depend on it.  The same option fixes the shares of cmf_rank / cmf_rank_queries, whose result does not depend on
+ * it either,
  * "kl_split" n: the dense passes of cmf_mu_kl_step / cmf_kl_divergence cut the streamed dimension into n shares (<= 0, default:
  * enough to give every CU a workgroup); another n regroups the float32 sums                                              */
 int cmf_set_option(cmf_ctx *ctx, const char *name, int64_t value);
@@ -310,6 +311,39 @@ int cmf_topk(cmf_ctx *ctx, int query, int cand, int link, const int64_t *rows, i
 int cmf_topk_queries(cmf_ctx *ctx, const double *Q, int64_t rs, int64_t cs, int64_t nq, int cand, int link, int n,
                      const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *idx, float *val);
 int cmf_topk_layout(cmf_ctx *ctx, int64_t nq, int cand, int n, int64_t excl_nnz, int own_queries, int64_t *out4);
+
+/* ---- held-out ranking evaluation: the exact rank of held-out entries under cmf_topk's order ----
+ * How good are the rankings on entries held back from training?  Every ranking metric (recall@n, NDCG@n, MRR, MAP, AUC) is a
+ * function of one integer per held-out entry (i, j): its rank.  It is a count over the same score tiles cmf_topk streams, so it is
+ * computed exactly, in integers, without the product (csrc/cmf_rank.hip.h).  The reference has no counterpart.
+ *   Queries and candidates: as cmf_topk / cmf_topk_queries (the four factor pairs, `rows` -- may repeat; NULL: all rows, nq
+ *   ignored --, or caller-supplied vectors).
+ *   Held-out entries: host CSR over the nq queries, held_indptr int64[nq + 1], held_indices int32 -- strictly ascending per query,
+ *   inside [0, candidates) (checked, CMF_EINVAL).  Exclusion lists (nullable, both or neither): as cmf_topk's.
+ *   Order: cmf_topk's, bit for bit -- larger raw float32 score first, -0 counts as +0, equal scores by smaller candidate index, a
+ *   NaN-scored candidate is absent.  There is no link argument: the links are monotone.
+ *   rank(i, j) = the number of candidates c != j of query i that are not in i's exclusion list and precede j in that order.
+ *   0-based: rank r < n <=> j is entry r of cmf_topk's list under the same exclusion list.  Whether j itself is in the exclusion
+ *   list is ignored here.  A held-out entry whose own score is NaN gets rank -1.
+ * Outputs (host): rank int32[held_nnz] and score float32[held_nnz] (the raw score; nullable) in the order of held_indices,
+ * eligible int32[nq] = candidates - length of the query's exclusion list.
+ * Every score -- a held-out entry's own included -- is the fma chain of cmf_topk (the same matrix instruction sequence and k
+ * pairing), so ranks and cmf_topk agree bit for bit; counts are integers, summed without atomics: the result is bit-identical when
+ * the call is repeated, whichever other queries are in the call and however the candidates are split ("topk_split" fixes the
+ * number of shares S of these calls too).  A query with more than HB held-out entries is scanned as several virtual queries.
+ * Needs cmf_set_problem and the factors, no data; modifies no factor, data, option, captured graph or RNG state.  k_pad <= 256.
+ * One GPU.  Kernel time goes to class CMF_K_TOPK, 2 (virtual queries) C k flops per scan.
+ * cmf_rank_layout: out4 = { HB, candidate shares S, virtual queries per launch, device scratch bytes } for nq queries with held_nnz
+ * held-out entries against factor `cand` (excl_nnz < 0: no exclusion lists; own_queries: cmf_rank_queries). */
+int cmf_rank(cmf_ctx *ctx, int query, int cand, const int64_t *rows, int64_t nq,
+             const int64_t *held_indptr, const int32_t *held_indices,
+             const int64_t *excl_indptr, const int32_t *excl_indices,
+             int32_t *rank, float *score, int32_t *eligible);
+int cmf_rank_queries(cmf_ctx *ctx, const double *Q, int64_t rs, int64_t cs, int64_t nq, int cand,
+             const int64_t *held_indptr, const int32_t *held_indices,
+             const int64_t *excl_indptr, const int32_t *excl_indices,
+             int32_t *rank, float *score, int32_t *eligible);
+int cmf_rank_layout(cmf_ctx *ctx, int64_t nq, int cand, int64_t held_nnz, int64_t excl_nnz, int own_queries, int64_t *out4);
 
 /* ---- batched safe inverse (exposed for tests): _safe_invert :346-356 --- */
 /* H: n symmetric k x k float64 matrices (host), out: Q diag(1/max(|l|,pert)) Q^T */

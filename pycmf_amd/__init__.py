@@ -3,7 +3,8 @@
 The public names are resolved on first use (PEP 562): ``from pycmf_amd import _lib`` -- what bench.py and the sharded
 drivers need -- then imports NumPy only, not scikit-learn / SciPy / pandas behind the estimator."""
 
-__all__ = ["CMF", "collective_matrix_factorization", "HipMUSolver", "HipNewtonSolver", "top_n_products"]
+__all__ = ["CMF", "collective_matrix_factorization", "HipMUSolver", "HipNewtonSolver", "top_n_products", "rank_products",
+           "ranking_metrics"]
 
 
 def __getattr__(name):
@@ -16,6 +17,12 @@ def __getattr__(name):
     if name == "top_n_products":
         from . import prediction
         return prediction.top_n_products
+    if name == "rank_products":
+        from . import prediction
+        return prediction.rank_products
+    if name == "ranking_metrics":
+        from . import evaluation
+        return evaluation.ranking_metrics
     raise AttributeError("module 'pycmf_amd' has no attribute %r" % name)
 
 

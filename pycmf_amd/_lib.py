@@ -83,6 +83,9 @@ PROTOTYPES = {
     "cmf_topk": [_vp, _i32, _i32, _i32, _pi64, _i64, _i32, _pi64, _pi32, _pi32, _pf],
     "cmf_topk_queries": [_vp, _pd, _i64, _i64, _i64, _i32, _i32, _i32, _pi64, _pi32, _pi32, _pf],
     "cmf_topk_layout": [_vp, _i64, _i32, _i32, _i64, _i32, _pi64],
+    "cmf_rank": [_vp, _i32, _i32, _pi64, _i64, _pi64, _pi32, _pi64, _pi32, _pi32, _pf, _pi32],
+    "cmf_rank_queries": [_vp, _pd, _i64, _i64, _i64, _i32, _pi64, _pi32, _pi64, _pi32, _pi32, _pf, _pi32],
+    "cmf_rank_layout": [_vp, _i64, _i32, _i64, _i64, _i32, _pi64],
     "cmf_safe_invert_batch": [_vp, _pd, _pd, _i32, _i32, _dbl],
     "cmf_safe_invert_f64": [_vp, _pd, _pd, _i32, _dbl],
     "cmf_safe_solve_batch": [_vp, _pd, _pd, _pd, _pd, _i32, _i32, _dbl, _i32],
@@ -603,6 +606,57 @@ class Context:
         """(queries per workgroup, candidate shares, queries per launch, device scratch bytes) of such a call."""
         out = (C.c_int64 * 4)()
         check(self._lib.cmf_topk_layout(self._h, int(nq), cand, int(n), int(excl_nnz), int(bool(own_queries)), out))
+        return tuple(out)
+
+    def rank(self, query, cand, held, rows=None, exclude=None, queries=None):
+        """Exact ranks of held-out entries under ``topk``'s order: ``(rank int32[nnz], score float32[nnz], eligible int32[nq])``.
+        ``held`` = ``(indptr int64[nq + 1], indices int32)``: per query a strictly ascending list of held-out candidates; rank =
+        how many candidates outside the query's ``exclude`` list precede the entry (larger raw score first, ties by smaller index;
+        0-based, -1 where the entry's own score is NaN), score = its raw float32 score, eligible = candidates - len(exclude list).
+        Queries, ``rows``, ``exclude`` and ``queries`` as in ``topk``."""
+        hp = np.ascontiguousarray(held[0], dtype=np.int64)
+        hi = np.ascontiguousarray(held[1], dtype=np.int32)
+        xp = xi = None
+        if exclude is not None:
+            xp = np.ascontiguousarray(exclude[0], dtype=np.int64)
+            xi = np.ascontiguousarray(exclude[1], dtype=np.int32)
+        if queries is not None:
+            if rows is not None:
+                raise ValueError("rows and queries exclude each other")
+            Q = np.asarray(queries, dtype=np.float64)
+            if Q.ndim != 2 or Q.shape[1] != self.shape[3]:
+                raise ValueError("queries must be (nq, %d), got %r" % (self.shape[3], Q.shape))
+            nq = Q.shape[0]
+        elif rows is not None:
+            r = np.ascontiguousarray(rows, dtype=np.int64).ravel()
+            nq = r.size
+        else:
+            nq = self.shape[query] if query in (0, 1, 2) else 0
+        for name, p, i in (("held", hp, hi), ("exclude", xp, xi)):
+            if p is None:
+                continue
+            if p.ndim != 1 or p.size != nq + 1:
+                raise ValueError("%s: indptr must have nq + 1 = %d entries, got %d" % (name, nq + 1, p.size))
+            if p[-1] > i.size:
+                raise ValueError("%s: indptr points beyond indices" % name)
+        nnz = int(hp[-1]) if hp[-1] > 0 else 0
+        rank = np.empty(nnz, dtype=np.int32)
+        score = np.empty(nnz, dtype=np.float32)
+        eligible = np.empty(nq, dtype=np.int32)
+        args = (hp.ctypes.data_as(_pi64), hi.ctypes.data_as(_pi32),
+                xp.ctypes.data_as(_pi64) if xp is not None else None, xi.ctypes.data_as(_pi32) if xi is not None else None,
+                rank.ctypes.data_as(_pi32), score.ctypes.data_as(_pf), eligible.ctypes.data_as(_pi32))
+        if queries is not None:
+            rs, cs = _strides(Q) if nq else (Q.shape[1], 1)
+            check(self._lib.cmf_rank_queries(self._h, Q.ctypes.data_as(_pd), rs, cs, nq, cand, *args))
+        else:
+            check(self._lib.cmf_rank(self._h, query, cand, r.ctypes.data_as(_pi64) if rows is not None else None, nq, *args))
+        return rank, score, eligible
+
+    def rank_layout(self, nq, cand, held_nnz, excl_nnz=-1, own_queries=False):
+        """(held-out entries per virtual query HB, candidate shares, virtual queries per launch, device scratch bytes) of such a call."""
+        out = (C.c_int64 * 4)()
+        check(self._lib.cmf_rank_layout(self._h, int(nq), cand, int(held_nnz), int(excl_nnz), int(bool(own_queries)), out))
         return tuple(out)
 
     def data_sq(self):

@@ -1810,3 +1810,5 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_topk.hip.h"
 #define CMF_KLMU_HOST
 #include "cmf_klmu.hip.h"
+#define CMF_RANK_HOST
+#include "cmf_rank.hip.h"

@@ -313,6 +313,33 @@ class CMF(BaseEstimator, TransformerMixin):
         return model_top_n(self.x_weights, self.components, self.y_weights, self.x_link, self.y_link, self.device,
                            relation=relation, axis=axis, rows=rows, n=n, exclude=exclude, queries=queries)
 
+    def ranks(self, held_out, relation="x", axis=0, exclude=None, rows=None, queries=None):
+        """The exact rank of every entry ``held_out`` stores in the fitted reconstruction of ``relation``, per row (``axis=0``) or
+        per column (``axis=1``): ``(indptr int64[nq + 1], indices int32, rank int32, eligible int32[nq])`` -- the canonical CSR
+        order of ``held_out`` (of its transpose for ``axis=1``), ``rank[e]`` = how many candidates of the row that ``exclude``
+        does not store the model scores higher than entry e (equal scores: the smaller index first; 0-based, so rank r < n <=>
+        the entry is place r of ``top_n(n=n, exclude=exclude)``; -1 if the entry's own score is NaN), ``eligible[i]`` = candidates
+        - entries ``exclude`` stores in row i.  The product is never formed (float32, pycmf_amd/csrc/cmf_rank.hip.h; one GPU).
+
+        ``held_out`` / ``exclude``: SciPy sparse (stored entries) or dense (non-zeros) matrices of the relation's shape -- pass
+        the test split and the training ``X``.  A held-out entry that ``exclude`` stores too is a ``ValueError``: a test entry
+        among the training entries is a leak.  ``rows`` / ``queries`` as in ``top_n`` (both matrices then have nq rows for
+        ``queries``); ``rows`` together with ``queries`` is a ``ValueError``."""
+        assert hasattr(self, "components")
+        from .prediction import model_ranks
+        return model_ranks(self.x_weights, self.components, self.y_weights, self.device, held_out, relation=relation, axis=axis,
+                           exclude=exclude, rows=rows, queries=queries)
+
+    def evaluate(self, held_out, n=(10,), relation="x", axis=0, exclude=None, rows=None, queries=None):
+        """Ranking metrics of the fitted model on the entries ``held_out`` stores: ``ranks`` with the same keywords, then
+        ``pycmf_amd.ranking_metrics`` at the cut-offs ``n`` -- a dict with ``hit_rate@n``, ``recall@n``, ``precision@n``,
+        ``ndcg@n`` per cut-off, ``mrr``, ``map``, ``auc`` and the row counts."""
+        assert hasattr(self, "components")
+        from .evaluation import ranking_metrics, _check_cutoffs
+        _check_cutoffs(n)
+        indptr, _, rank, eligible = self.ranks(held_out, relation=relation, axis=axis, exclude=exclude, rows=rows, queries=queries)
+        return ranking_metrics(indptr, rank, eligible, n=n)
+
     def print_topic_terms(self, vectorizer, topn_words=10, importances=True):
         """Print the top terms per topic (cmf.py:749-776); works with both the old
         ``get_feature_names`` and the current ``get_feature_names_out`` vectorizer API."""

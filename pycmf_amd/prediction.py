@@ -1,5 +1,6 @@
 """Top-n prediction from fitted factors: for every query row the n candidates with the largest f(q . b_j), computed on the device
-without ever forming the product (csrc/cmf_topk.hip.h through ``Context.topk``).
+without ever forming the product (csrc/cmf_topk.hip.h through ``Context.topk``) -- and the exact rank of held-out entries under
+the same order (csrc/cmf_rank.hip.h through ``Context.rank``; the metrics over those ranks: evaluation.py).
 
 The reference has no counterpart: it returns the three factor arrays and its only consumer of them is the host argsort of
 pycmf/analysis.py:3-16.  Everything here that can fail on its arguments fails BEFORE a device is touched.
@@ -15,7 +16,7 @@ _PAIRS = {("x", 0): (_lib.CMF_U, _lib.CMF_V), ("x", 1): (_lib.CMF_V, _lib.CMF_U)
           ("y", 0): (_lib.CMF_V, _lib.CMF_Z), ("y", 1): (_lib.CMF_Z, _lib.CMF_V)}
 
 
-def exclusion_lists(exclude, shape, rows=None, transpose=False):
+def exclusion_lists(exclude, shape, rows=None, transpose=False, name="exclude"):
     """CSR pair ``(indptr int64[nq + 1], indices int32)`` of the entries to skip: row i lists, strictly ascending, the columns that
     ``exclude`` stores in row ``rows[i]`` (``rows=None``: every row).  ``exclude`` is a SciPy sparse matrix or a dense array (its
     non-zeros count) of shape ``shape`` -- of ``shape[::-1]`` when ``transpose`` (a relation queried along axis 1).  Explicitly
@@ -25,11 +26,11 @@ def exclusion_lists(exclude, shape, rows=None, transpose=False):
     if not sp.issparse(exclude):
         exclude = np.asarray(exclude)
         if exclude.ndim != 2:
-            raise ValueError("exclude must be a 2-d matrix of shape %r, got %d dimension(s)" % (want, exclude.ndim))
+            raise ValueError("%s must be a 2-d matrix of shape %r, got %d dimension(s)" % (name, want, exclude.ndim))
     if tuple(exclude.shape) != want:
-        raise ValueError("exclude must have shape %r, got %r" % (want, tuple(exclude.shape)))
+        raise ValueError("%s must have shape %r, got %r" % (name, want, tuple(exclude.shape)))
     if shape[1] > np.iinfo(np.int32).max:
-        raise ValueError("exclude: %d candidates do not fit int32 indices" % shape[1])
+        raise ValueError("%s: %d candidates do not fit int32 indices" % (name, shape[1]))
     M = sp.csr_matrix(exclude.T if transpose else exclude)
     M = M[np.asarray(rows, dtype=np.int64)] if rows is not None else M.copy()   # never the caller's own arrays
     M.sum_duplicates()        # sorts the column indices of every row and merges repeated ones
@@ -124,3 +125,82 @@ def model_top_n(U, V, Z, x_link, y_link, device, relation="x", axis=0, rows=None
         return ctx.topk(qf, cf, n, link=link, rows=rows, exclude=excl, queries=queries)
     finally:
         ctx.close()
+
+
+def held_out_lists(held_out, shape, rows=None, transpose=False):
+    """CSR pair ``(indptr int64[nq + 1], indices int32)`` of the held-out entries: ``exclusion_lists`` under another name -- row i
+    lists, strictly ascending, the columns that ``held_out`` stores in row ``rows[i]`` (``rows=None``: every row; ``transpose``:
+    ``held_out`` has ``shape[::-1]``, a relation queried along axis 1).  Repeated entries are merged, stored zeros count."""
+    return exclusion_lists(held_out, shape, rows=rows, transpose=transpose, name="held_out")
+
+
+def _check_no_leak(held, excl, ncand):
+    """A held-out entry that the exclusion lists store too is a test entry among the training entries."""
+    if excl is None or not held[1].size or not excl[1].size:
+        return
+    def keys(pair):
+        return np.repeat(np.arange(pair[0].size - 1, dtype=np.int64), np.diff(pair[0])) * ncand + pair[1]
+    hk = keys(held)
+    both = np.isin(hk, keys(excl), assume_unique=True)
+    if both.any():
+        e = int(np.flatnonzero(both)[0])
+        raise ValueError("%d held-out entries are also stored in exclude (the first: query %d, candidate %d): a test entry among "
+                         "the training entries is a leak" % (int(both.sum()), hk[e] // ncand, hk[e] % ncand))
+
+
+def rank_products(A, B, held_out, exclude=None, device=0):
+    """Exact ranks of the entries ``held_out`` stores (nq x C sparse or dense matrix) among the scores ``a_i . b_j`` of row i of
+    ``A`` (nq x k) against the rows of ``B`` (C x k): ``(indptr, indices, rank, eligible)`` -- the canonical CSR order of
+    ``held_out``, ``rank[e]`` = how many candidates outside row i's ``exclude`` list score higher than entry e (equal scores: a
+    smaller index goes first; 0-based), ``eligible[i]`` = C - the length of that list.  A held-out entry that ``exclude`` stores as
+    well is a ``ValueError``.  Float32 arithmetic on GPU ``device``, the order of ``top_n_products``; the product is never formed."""
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim != 2 or B.shape[0] < 1 or B.shape[1] < 1:
+        raise ValueError("B must be a non-empty (C, k) array, got shape %r" % (B.shape,))
+    A = _check_queries(A, B.shape[1])
+    held = held_out_lists(held_out, (A.shape[0], B.shape[0]))
+    excl = None if exclude is None else exclusion_lists(exclude, (A.shape[0], B.shape[0]))
+    _check_no_leak(held, excl, B.shape[0])
+    ctx = _lib.Context(device)
+    try:
+        ctx.set_problem(1, B.shape[0], 1, B.shape[1])
+        ctx.set_factor(_lib.CMF_V, B)
+        rank, _, eligible = ctx.rank(_lib.CMF_U, _lib.CMF_V, held, exclude=excl, queries=A)
+    finally:
+        ctx.close()
+    return held[0], held[1], rank, eligible
+
+
+def model_ranks(U, V, Z, device, held_out, relation="x", axis=0, exclude=None, rows=None, queries=None):
+    """``CMF.ranks`` on explicit factors (see there)."""
+    if relation not in ("x", "y"):
+        raise ValueError("relation must be 'x' or 'y', got %r" % (relation,))
+    if axis not in (0, 1):
+        raise ValueError("axis must be 0 or 1, got %r" % (axis,))
+    if rows is not None and queries is not None:
+        raise ValueError("rows and queries exclude each other: queries replace the fitted rows")
+    factors = (U, V, Z)
+    qf, cf = _PAIRS[(relation, axis)]
+    ncand, k = factors[cf].shape
+    if queries is not None:
+        queries = _check_queries(queries, k)
+        nrows = queries.shape[0]
+    else:
+        nrows = factors[qf].shape[0]
+        if rows is not None:
+            rows = _check_rows(rows, nrows)
+    held = held_out_lists(held_out, (nrows, ncand), rows=rows, transpose=(axis == 1))
+    excl = None
+    if exclude is not None:
+        excl = exclusion_lists(exclude, (nrows, ncand), rows=rows, transpose=(axis == 1))
+    _check_no_leak(held, excl, ncand)
+    ctx = _lib.Context(device)
+    try:
+        ctx.set_problem(U.shape[0], V.shape[0], Z.shape[0], k)
+        ctx.set_factor(cf, factors[cf])
+        if queries is None:
+            ctx.set_factor(qf, factors[qf])
+        rank, _, eligible = ctx.rank(qf, cf, held, rows=rows, exclude=excl, queries=queries)
+    finally:
+        ctx.close()
+    return held[0], held[1], rank, eligible
