@@ -204,6 +204,43 @@ int cmf_mu_kl_step(cmf_ctx *ctx, double l1, double l2, int update_mask);
 int cmf_kl_divergence(cmf_ctx *ctx, double *dx, double *dy);
 int cmf_mu_kl_layout(cmf_ctx *ctx, int64_t *out4);
 
+/* ---- MU solver, Frobenius objective with per-entry weights ---------------------------------------------------------------
+ * The reference lists "Add support for weight matrices on relations" as an open item (its README).  Here, with fixed
+ * non-negative Wx (m x d) and Wy (d x p) -- a 0/1 mask restricts the loss to the observed entries:
+ *   minimise  1/2 |sqrt(Wx) .* (X - U V^T)|^2 + 1/2 |sqrt(Wy) .* (Y - V Z^T)|^2 + l1 (sum U + sum V + sum Z) + l2 / 2 (|U|^2 + |V|^2 + |Z|^2)
+ *   V <- V .* [(Wx.*X)^T U + (Wy.*Y) Z] ./ reg((Wx.*(U V^T))^T U + (Wy.*(V Z^T)) Z, V)
+ *   U <- U .* [(Wx.*X) V] ./ reg((Wx.*(U V^T)) V, U)   (new V)         Z <- Z .* [(Wy.*Y)^T V] ./ reg((Wy.*(V Z^T))^T V, Z)
+ *   reg(den, F) = den + l1 + l2 F, then den == 0 -> EPS = 2^-23         (cmf_solvers.py:212-228 with gamma = 1)
+ * A relation without weights takes part with W == 1 (no matrix of ones is formed); with both absent this is cmf_mu_step's
+ * update in another association.  The m x d product under the weights is never materialised (csrc/cmf_wmu.hip.h).
+ * PRECONDITION: non-negative data, weights and factors.  which: 0 = X, 1 = Y.
+ *   cmf_set_weight_f64 / _f32: dense weights of the relation's shape, element (i,j) at ptr[i*rs + j*cs].  The relation's data
+ *   must be set and held dense (CMF_EINVAL otherwise); call again after the data change.  Forms the image W .* T once.
+ *   cmf_set_weighted_csr: the observed pattern (scipy CSR layout, nnz = indptr[rows]) with the data and the weights on it; the
+ *   loss of that relation then runs over the stored entries only (explicit zeros of either array included), cost O(nnz k) per
+ *   pass, no dense image.  Held in buffers of its own: the data slot of that relation need not be set and is not read.
+ *   cmf_clear_weight: back to unweighted.  cmf_set_problem drops all weights.
+ *   cmf_mu_weighted_step: one iteration in the sweep order V, U, Z.  k_pad > 256: CMF_EUNSUPPORTED; a relation named by the mask
+ *   that has neither data nor CSR weights: CMF_EINVAL; an unweighted relation held only as native CSR: CMF_EUNSUPPORTED (give it
+ *   a dense image, sparse_mode 1).  No floating-point atomics: a repeated call from the same state is bit-identical.
+ *   cmf_weighted_residual_sq: *ex = sum Wx .* (X - U V^T)^2, *ey likewise (either may be NULL), every term in float32 in the
+ *   direct form, float64 accumulation.
+ *   cmf_mu_weighted_layout: out4 = { shares of the streamed dimension in the U, V, Z sweeps (option "wmu_split" n forces them,
+ *   as "kl_split" does for the KL passes; 1 for CSR weights); device scratch bytes of a full step }.
+ *   cmf_fill_weight_synthetic: a Bernoulli(density) 0/1 mask from the counter-based generator of cmf_fill_data_synthetic as dense
+ *   weights; cmf_get_weight_block_f32: a block of the dense weight image (full-size tests, the timing tool).
+ * cmf_mu_step, cmf_mu_kl_step, cmf_run and cmf_residual_sq ignore weights; every option, captured graph and buffer of theirs is
+ * left as it was.                                                                                                            */
+int cmf_set_weight_f64(cmf_ctx *ctx, int which, const double *ptr, int64_t rs, int64_t cs);
+int cmf_set_weight_f32(cmf_ctx *ctx, int which, const float *ptr, int64_t rs, int64_t cs);
+int cmf_set_weighted_csr(cmf_ctx *ctx, int which, const int64_t *indptr, const int32_t *indices, const double *t_values, const double *w_values);
+int cmf_clear_weight(cmf_ctx *ctx, int which);
+int cmf_mu_weighted_step(cmf_ctx *ctx, double l1, double l2, int update_mask);
+int cmf_weighted_residual_sq(cmf_ctx *ctx, double *ex, double *ey);
+int cmf_mu_weighted_layout(cmf_ctx *ctx, int64_t *out4);
+int cmf_fill_weight_synthetic(cmf_ctx *ctx, int which, uint64_t seed, double density);
+int cmf_get_weight_block_f32(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, int64_t col0, int64_t ncols, float *host_dst);
+
 /* sharded form: rank g holds rows of X/U and columns of
  * Y/Z, V replicated.  buf is a DEVICE buffer of cmf_v_buf_elems() floats:
  *   [ X_g^T U_g + Y_g Z_g  (d_pad x k_pad) | U_g^T U_g + Z_g^T Z_g (k_pad x k_pad) ]

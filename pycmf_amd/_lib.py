@@ -59,6 +59,15 @@ PROTOTYPES = {
     "cmf_mu_kl_step": [_vp, _dbl, _dbl, _i32],
     "cmf_kl_divergence": [_vp, _pd, _pd],
     "cmf_mu_kl_layout": [_vp, _pi64],
+    "cmf_set_weight_f64": [_vp, _i32, _pd, _i64, _i64],
+    "cmf_set_weight_f32": [_vp, _i32, _pf, _i64, _i64],
+    "cmf_set_weighted_csr": [_vp, _i32, _pi64, _pi32, _pd, _pd],
+    "cmf_clear_weight": [_vp, _i32],
+    "cmf_mu_weighted_step": [_vp, _dbl, _dbl, _i32],
+    "cmf_weighted_residual_sq": [_vp, _pd, _pd],
+    "cmf_mu_weighted_layout": [_vp, _pi64],
+    "cmf_fill_weight_synthetic": [_vp, _i32, C.c_uint64, _dbl],
+    "cmf_get_weight_block_f32": [_vp, _i32, _i64, _i64, _i64, _i64, _pf],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_mu_v_partials": [_vp, _vp],
     "cmf_mu_v_apply": [_vp, _vp, _dbl, _dbl],
@@ -443,6 +452,58 @@ class Context:
         out = (C.c_int64 * 4)()
         check(self._lib.cmf_mu_kl_layout(self._h, out))
         return tuple(out)
+
+    # ---- MU with per-entry weights (csrc/cmf_wmu.hip.h)
+    def set_weight(self, which, W):
+        """Dense non-negative weights of the shape of X (which=0) / Y (which=1); the relation's data must be set and dense."""
+        W = np.asarray(W)
+        if W.dtype == np.float32:
+            rs, cs = _strides(W)
+            check(self._lib.cmf_set_weight_f32(self._h, which, W.ctypes.data_as(_pf), rs, cs))
+        else:
+            W = W if W.dtype == np.float64 else W.astype(np.float64)
+            rs, cs = _strides(W)
+            check(self._lib.cmf_set_weight_f64(self._h, which, W.ctypes.data_as(_pd), rs, cs))
+
+    def set_weighted_csr(self, which, indptr, indices, t_values, w_values):
+        """The observed pattern of a relation (CSR arrays) with the data and the weights on it; the loss runs over it only."""
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        t = np.ascontiguousarray(t_values, dtype=np.float64)
+        w = np.ascontiguousarray(w_values, dtype=np.float64)
+        if not (indices.shape == t.shape == w.shape and indptr.ndim == 1 and indptr.size and indptr[-1] == indices.size):
+            raise ValueError("set_weighted_csr: indices, t_values and w_values must have indptr[-1] entries each")
+        check(self._lib.cmf_set_weighted_csr(self._h, which, indptr.ctypes.data_as(_pi64), indices.ctypes.data_as(_pi32),
+                                             t.ctypes.data_as(_pd), w.ctypes.data_as(_pd)))
+
+    def clear_weight(self, which):
+        check(self._lib.cmf_clear_weight(self._h, which))
+
+    def mu_weighted_step(self, l1, l2, mask=7):
+        """One multiplicative-update iteration (V, U, Z) of the weighted Frobenius objective; an unweighted relation counts with W = 1."""
+        check(self._lib.cmf_mu_weighted_step(self._h, l1, l2, mask))
+
+    def weighted_residual_sq(self, want_x=True, want_y=True):
+        """(sum Wx (X - U V^T)^2, sum Wy (Y - V Z^T)^2) of the factors on the device; a side that is not asked for comes back as 0.0."""
+        ex, ey = C.c_double(0), C.c_double(0)
+        check(self._lib.cmf_weighted_residual_sq(self._h, C.byref(ex) if want_x else None, C.byref(ey) if want_y else None))
+        return ex.value, ey.value
+
+    def mu_weighted_layout(self):
+        """(shares of the U sweep, of the V sweep, of the Z sweep, device scratch bytes of a step) of the weighted passes."""
+        out = (C.c_int64 * 4)()
+        check(self._lib.cmf_mu_weighted_layout(self._h, out))
+        return tuple(out)
+
+    def fill_weight_synthetic(self, which, seed, density):
+        """Dense Bernoulli(density) 0/1 weights from the device generator."""
+        check(self._lib.cmf_fill_weight_synthetic(self._h, which, seed, density))
+
+    def get_weight_block(self, which, row0, nrows, col0, ncols):
+        """float32 block of the dense weight image of X (0) / Y (1)."""
+        out = np.empty((nrows, ncols), dtype=np.float32)
+        check(self._lib.cmf_get_weight_block_f32(self._h, which, row0, nrows, col0, ncols, out.ctypes.data_as(_pf)))
+        return out
 
     def mu_step_error(self, l1, l2, mask=7):
         """One MU iteration and the squared residuals (ex2, ey2) of the factors it leaves, from the step's own products."""

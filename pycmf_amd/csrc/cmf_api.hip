@@ -83,6 +83,14 @@ struct CsrDev {
     int b_nsplit = 0, b_nslots = 0;
 };
 
+// Weights of a relation held as CSR (cmf_wmu.hip.h): one pattern, the values p = w t and w (and t on the row image)
+struct WCsrDev {
+    int64_t *indptr = nullptr;
+    int32_t *idx = nullptr;
+    float *pv = nullptr, *wv = nullptr, *tv = nullptr;
+    int64_t rows = 0, cols = 0, nnz = 0;
+};
+
 // A captured update step: replayed with hipGraphLaunch while the key (hyper-parameters baked into
 // kernel arguments) and every device pointer it references stay unchanged.
 struct StepGraph {
@@ -126,6 +134,11 @@ struct cmf_ctx {
     int opt_topk_split = 0; // top-n (cmf_topk.hip.h): force the number of candidate shares (<= 0: fill the chip); the result does not depend on it
     int opt_kl_split = 0;  // KL passes (cmf_klmu.hip.h): force the number of shares of the streamed dimension (<= 0: one workgroup per CU); S = 1 and S > 1 differ in rounding only
     DevBuf kl_slab, kl_small, kl_part; // ... their numerator slabs, column sums (+ partials), float64 partials of the divergence
+    int opt_wmu_split = 0; // weighted passes (cmf_wmu.hip.h): force the number of shares of the streamed dimension, as kl_split does for the KL passes
+    int wm_kind[2] = {0, 0};              // per-entry weights of X / Y: 0 none | 1 dense image | 2 CSR (the loss runs over the stored pattern)
+    float *wm_w[2] = {nullptr, nullptr}, *wm_p[2] = {nullptr, nullptr}; // dense weights W and P = W .* T, the relation's padded shape
+    WCsrDev wm_sp[2][2];                  // [X|Y][pattern | its transpose]
+    DevBuf wm_slab, wm_small, wm_part;    // numerator / denominator slabs, the residual's sum and its float64 partials
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
     int opt_chol = 1;      // Cholesky fast path of the safe inverse (0: always Jacobi)
     int opt_chol_mfma = 1; // k_pad = 256 per-row solves: blocked Cholesky on the matrix pipe (0: the rank-1 register kernel chol_solve_kernel<16>)
@@ -733,6 +746,11 @@ static void release_problem(cmf_ctx *c) {
     c->nsidx = DevBuf(); c->nsws = DevBuf(); c->eigcl_ws = DevBuf(); c->eigcl_log = DevBuf(); c->eigcl_fail = DevBuf(); c->eigcl_snap = DevBuf(); c->r1_ws = DevBuf();
     c->spmm_bar = DevBuf(); c->spmm_part = DevBuf();
     c->kl_slab = DevBuf(); c->kl_small = DevBuf(); c->kl_part = DevBuf();
+    c->wm_slab = DevBuf(); c->wm_small = DevBuf(); c->wm_part = DevBuf();
+    for (int w = 0; w < 2; ++w) {
+        c->wm_kind[w] = 0; c->wm_w[w] = c->wm_p[w] = nullptr;
+        c->wm_sp[w][0] = WCsrDev(); c->wm_sp[w][1] = WCsrDev();
+    }
     c->g64a = DevBuf(); c->g64b = DevBuf(); c->gmix64 = DevBuf(); c->h64 = DevBuf();
     c->gslab64 = DevBuf(); c->w64 = DevBuf(); c->ns64 = DevBuf();
     c->hinv64 = DevBuf(); c->opr = DevBuf(); c->v_plain = false;
@@ -879,6 +897,8 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
         c->opt_spmm_block_cols = std::max<int64_t>(0, value);
     } else if (!strcmp(name, "kl_split")) {
         c->opt_kl_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
+    } else if (!strcmp(name, "wmu_split")) {
+        c->opt_wmu_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "topk_split")) {
         c->opt_topk_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "sparse_mode")) {
@@ -1810,5 +1830,7 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_topk.hip.h"
 #define CMF_KLMU_HOST
 #include "cmf_klmu.hip.h"
+#define CMF_WMU_HOST
+#include "cmf_wmu.hip.h"
 #define CMF_RANK_HOST
 #include "cmf_rank.hip.h"

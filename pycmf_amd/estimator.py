@@ -12,7 +12,7 @@ from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
-from .solver_shell import HipMUSolver, HipNewtonSolver, check_loss, check_kl_data
+from .solver_shell import HipMUSolver, HipNewtonSolver, check_loss, check_kl_data, check_entry_weights
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -39,7 +39,8 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                     update_U=True, update_V=True, update_Z=True,
                                     x_link="linear", y_link="linear",
                                     hessian_pertubation=0.2, sg_sample_ratio=1.,
-                                    device=0, sg_sampler="numpy", n_gpus=1, _return_solver=False, loss="frobenius"):
+                                    device=0, sg_sampler="numpy", n_gpus=1, _return_solver=False, loss="frobenius",
+                                    x_entry_weights=None, y_entry_weights=None):
     """Factorise X ~ f(U V^T) and Y ~ f(V Z^T) with a shared V on an MI355X.
 
     Same contract as the reference function (pycmf/cmf.py:215-456): returns
@@ -55,11 +56,21 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     D(X || U V^T) + D(Y || V Z^T), the usual loss for count data (``sklearn.decomposition.NMF(beta_loss='kullback-leibler',
     solver='mu')`` per block); needs ``solver='mu'``, ``n_gpus=1`` and non-negative X and Y (``ValueError`` otherwise, before any
     device is touched).  ``beta_loss`` keeps the reference's meaning: parsed and ignored.
+
+    ``x_entry_weights`` / ``y_entry_weights``: fixed non-negative weights per entry of X / Y; the fit then minimises
+    1/2 |sqrt(Wx) .* (X - U V^T)|^2 + 1/2 |sqrt(Wy) .* (Y - V Z^T)|^2 -- with a 0/1 mask, the observed entries only, instead of
+    training on the missing ones as zeros.  None | a dense array of the relation's shape (a sparse relation is then densified on
+    the host) | a SciPy sparse matrix (its stored pattern is the observed set, its values the weights; cost proportional to the
+    stored entries) | ``'observed'`` (the relation must be SciPy sparse: its stored entries, explicit zeros included, carry
+    weight 1).  A relation without weights takes part with weight 1 everywhere.  Needs ``solver='mu'``, ``loss='frobenius'``
+    and ``n_gpus=1`` (``ValueError`` otherwise, as for negative, NaN or infinite weights or a shape mismatch, before any device is
+    touched); ``n_components`` above 256 is a ``NotImplementedError``.
     """
     if n_components is None:
         n_components = max(X.shape[1], Y.shape[1])
     _check_beta_loss(beta_loss)
     check_loss(loss, solver, n_gpus)
+    check_entry_weights(x_entry_weights, y_entry_weights, solver, loss, n_gpus)
 
     if update_U or update_V:
         X = check_array(X, accept_sparse=('csr', 'csc'), dtype=float)
@@ -83,7 +94,9 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
         if x_link != "linear" or y_link != "linear":
             warnings.warn("mu solver does not accept link functions other than linear, "
                           "link arguments will be ignored")
-        solver_object = HipMUSolver(beta_loss=beta_loss, loss=loss, **common)
+        solver_object = HipMUSolver(beta_loss=beta_loss, loss=loss, x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights,
+                                    **common)
+        solver_object.check_weights(X, Y)
     elif solver == "newton":
         if alpha == "auto":
             alpha = Y.shape[1] / (X.shape[0] + Y.shape[1])
@@ -257,7 +270,9 @@ class CMF(BaseEstimator, TransformerMixin):
                     sg_sample_ratio=self.sg_sample_ratio, device=self.device, sg_sampler=self.sg_sampler,
                     loss=self.loss)
 
-    def fit_transform(self, X, Y, U=None, V=None, Z=None):
+    def fit_transform(self, X, Y, U=None, V=None, Z=None, x_entry_weights=None, y_entry_weights=None):
+        """``x_entry_weights`` / ``y_entry_weights``: per-entry weights of X / Y for this fit (``collective_matrix_factorization``);
+        ``reconstruction_err_`` is then sqrt(sum Wx (X - U V^T)^2) + sqrt(sum Wy (Y - V Z^T)^2)."""
         X = check_array(X, accept_sparse=('csr', 'csc'), dtype=float)
         Y = check_array(Y, accept_sparse=('csr', 'csc'), dtype=float)
         if X.shape[1] != Y.shape[0]:
@@ -266,7 +281,7 @@ class CMF(BaseEstimator, TransformerMixin):
         U, V, Z, n_iter_, solver_object = collective_matrix_factorization(
             X=X, Y=Y, U=U, V=V, Z=Z, n_components=self.n_components,
             x_init=self.x_init, y_init=self.y_init, alpha=self.alpha, n_gpus=self.n_gpus,
-            _return_solver=True, **self._kwargs())
+            _return_solver=True, x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, **self._kwargs())
         # unweighted sum of the two residual norms, evaluated on the device where the
         # data and the final factors still live (cmf.py:697-698)
         self.reconstruction_err_ = solver_object.reconstruction_error()
@@ -282,9 +297,10 @@ class CMF(BaseEstimator, TransformerMixin):
         self.fit_transform(X, Y, **params)
         return self
 
-    def transform(self, X, Y):
+    def transform(self, X, Y, x_entry_weights=None, y_entry_weights=None):
         """Re-fit U and/or Z with the learnt components V held fixed; pass ``None`` for
-        the side that should be left alone (cmf.py:726-747)."""
+        the side that should be left alone (cmf.py:726-747).  ``x_entry_weights`` / ``y_entry_weights``: per-entry weights of
+        the given X / Y, as in ``fit_transform``."""
         assert hasattr(self, "components")
         update_U = X is not None
         update_Z = Y is not None
@@ -294,7 +310,8 @@ class CMF(BaseEstimator, TransformerMixin):
         U, V, Z, _ = collective_matrix_factorization(
             X=X, Y=Y, U=U, V=self.components, Z=Z, n_components=self.n_components,
             x_init="custom", y_init="custom", alpha=alpha,
-            update_U=update_U, update_V=False, update_Z=update_Z, **self._kwargs())
+            update_U=update_U, update_V=False, update_Z=update_Z, x_entry_weights=x_entry_weights,
+            y_entry_weights=y_entry_weights, **self._kwargs())
         return U, V, Z
 
     def top_n(self, relation="x", axis=0, rows=None, n=10, exclude=None, queries=None):

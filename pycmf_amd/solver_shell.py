@@ -51,6 +51,82 @@ def check_kl_data(X, Y):
             raise ValueError("loss='kullback-leibler' needs non-negative data: %s has negative entries" % name)
 
 
+class EntryWeights:
+    """Per-entry weights of one relation as the device takes them.  ``kind`` 'dense': ``W`` and ``data`` are dense float64 arrays of
+    the relation's shape (a sparse relation densified on the host).  ``kind`` 'csr': the observed pattern ``indptr`` / ``indices``
+    with the relation's values ``t`` and the weights ``w`` on it, stored zeros of either included."""
+
+    def __init__(self, kind, W=None, data=None, indptr=None, indices=None, t=None, w=None):
+        self.kind, self.W, self.data, self.indptr, self.indices, self.t, self.w = kind, W, data, indptr, indices, t, w
+
+
+def _canonical_csr(A):
+    A = A.tocsr()
+    if not A.has_canonical_format:
+        A = A.copy()               # never canonicalise the caller's matrix in place
+        A.sum_duplicates()         # (keeps explicit zeros: a stored zero stays an observed entry)
+    return A
+
+
+def _check_weight_values(vals, name):
+    vals = np.asarray(vals, dtype=np.float64)
+    if vals.size and not np.isfinite(vals).all():
+        raise ValueError("%s_entry_weights must be finite: found NaN or infinite weights" % name)
+    if vals.size and vals.min() < 0:
+        raise ValueError("%s_entry_weights must be non-negative: found negative weights" % name)
+    return vals
+
+
+def resolve_entry_weights(M, W, name):
+    """Validate the weights ``W`` of relation ``M`` (``name`` 'x' | 'y') and put them in the form the device takes; no device is
+    touched.  ``W``: None | dense array of M's shape | SciPy sparse matrix (its stored pattern is the observed set, its values the
+    weights) | 'observed' (M must be SciPy sparse: its stored entries, explicit zeros included, carry weight 1)."""
+    import scipy.sparse as sp
+    if W is None:
+        return None
+    if M is None:
+        raise ValueError("%s_entry_weights given for a relation that is not" % name)
+    if isinstance(W, str):
+        if W != "observed":
+            raise ValueError("%s_entry_weights: got %r instead of an array, a SciPy sparse matrix, 'observed' or None" % (name, W))
+        if not sp.issparse(M):
+            raise ValueError("%s_entry_weights='observed' needs a SciPy sparse %s (its stored entries are the observed ones); "
+                             "for a dense relation pass a 0/1 array" % (name, name.upper()))
+        A = _canonical_csr(M)
+        return EntryWeights("csr", indptr=A.indptr.astype(np.int64), indices=A.indices.astype(np.int32),
+                            t=np.asarray(A.data, dtype=np.float64), w=np.ones(A.nnz))
+    if sp.issparse(W):
+        if W.shape != M.shape:
+            raise ValueError("%s_entry_weights has shape %s, the relation %s" % (name, W.shape, M.shape))
+        P = _canonical_csr(W)
+        w = _check_weight_values(P.data, name)
+        rows = np.repeat(np.arange(P.shape[0]), np.diff(P.indptr))
+        if sp.issparse(M):
+            t = np.asarray(M.tocsr()[rows, P.indices], dtype=np.float64).ravel() if P.nnz else np.zeros(0)
+        else:
+            t = np.asarray(M, dtype=np.float64)[rows, P.indices]
+        return EntryWeights("csr", indptr=P.indptr.astype(np.int64), indices=P.indices.astype(np.int32), t=t, w=w)
+    W = np.asarray(W)
+    if W.dtype.kind not in "fiub":
+        raise ValueError("%s_entry_weights: got an array of dtype %s instead of numbers" % (name, W.dtype))
+    if W.shape != M.shape:
+        raise ValueError("%s_entry_weights has shape %s, the relation %s" % (name, W.shape, M.shape))
+    W = _check_weight_values(W, name)
+    return EntryWeights("dense", W=W, data=(M.toarray() if sp.issparse(M) else M))
+
+
+def check_entry_weights(x_entry_weights, y_entry_weights, solver="mu", loss="frobenius", n_gpus=1):
+    """Per-entry weights need the multiplicative-update solver, the Frobenius loss and one GPU (no device is touched)."""
+    if x_entry_weights is None and y_entry_weights is None:
+        return
+    if solver != "mu":
+        raise ValueError("x_entry_weights / y_entry_weights are implemented by the multiplicative-update solver only: solver='mu', got %r" % (solver,))
+    if loss != "frobenius":
+        raise ValueError("x_entry_weights / y_entry_weights are implemented for loss='frobenius' only, got %r" % (loss,))
+    if n_gpus != 1:
+        raise ValueError("x_entry_weights / y_entry_weights run on one GPU: n_gpus must be 1, got %r (the sharded form is not built)" % (n_gpus,))
+
+
 def _as_f64(a):
     return a if (isinstance(a, np.ndarray) and a.dtype == np.float64) else np.asarray(a, dtype=np.float64)
 
@@ -129,9 +205,10 @@ class _HipIterativeSolver:
         self._bound = None
 
     def _bind_dims(self, X, Y, m, d, p, k):
-        key = (id(X), id(Y), m, d, p, k)
+        key = (id(X), id(Y), m, d, p, k) + self._weights_key()
         if getattr(self, "loss", "frobenius") == "kullback-leibler" and self._bound != key:
             check_kl_data(X, Y)
+        wx, wy = self._resolve_weights(X, Y) if self._bound != key else (None, None)   # ValueError before any device is opened
         if self._ctx is None:
             self._ctx = _lib.Context(self.device, self.stream)
             mode = os.environ.get("PYCMF_AMD_SPARSE_MODE")  # "dense" | "native": override the auto choice
@@ -145,17 +222,30 @@ class _HipIterativeSolver:
                 self._ctx.set_option("refine_rows", 0)
         if self._bound != key:
             self._ctx.set_problem(m, d, p, k)
-            if X is not None:
-                if X.shape != (m, d):
-                    raise ValueError("X has shape %s, factors imply %s" % (X.shape, (m, d)))
-                self._ctx.set_data(0, X)
-            if Y is not None:
-                if Y.shape != (d, p):
-                    raise ValueError("Y has shape %s, factors imply %s" % (Y.shape, (d, p)))
-                self._ctx.set_data(1, Y)
+            weighted = wx is not None or wy is not None
+            for which, M, name, shape, ew in ((0, X, "X", (m, d), wx), (1, Y, "Y", (d, p), wy)):
+                if M is None:
+                    continue
+                if M.shape != shape:
+                    raise ValueError("%s has shape %s, factors imply %s" % (name, M.shape, shape))
+                if ew is not None and ew.kind == "dense":
+                    M = ew.data            # (a sparse relation under dense weights: densified on the host)
+                elif weighted and ew is None and hasattr(M, "tocsr"):
+                    M = M.toarray()        # the unweighted side of a weighted fit takes part with W = 1 through its dense image
+                self._ctx.set_data(which, M)
+                if ew is not None and ew.kind == "dense":
+                    self._ctx.set_weight(which, ew.W)
+                elif ew is not None:
+                    self._ctx.set_weighted_csr(which, ew.indptr, ew.indices, ew.t, ew.w)
             self._bound = key
             self._XY = (X, Y)  # keep ids alive
         return self._ctx
+
+    def _weights_key(self):
+        return ()
+
+    def _resolve_weights(self, X, Y):
+        return None, None
 
     def _push_factors(self, U, V, Z):
         self._ctx.set_factor(_lib.CMF_U, U)
@@ -284,20 +374,50 @@ class HipMUSolver(_HipIterativeSolver):
     ``loss='kullback-leibler'`` (``beta_loss`` keeps its reference meaning: parsed, ignored): the same sweep order on the
     generalised Kullback-Leibler objective D(X || U V^T) + D(Y || V Z^T) -- sklearn's multiplicative update for beta_loss = 1 per
     block (``cmf_mu_kl_step``).  The error metric is then what ``compute_factorization_error`` would return under beta_loss = 1,
-    sqrt(2 D) per side; the loop stays on the host (``cmf_run`` knows the Frobenius steps only)."""
+    sqrt(2 D) per side; the loop stays on the host (``cmf_run`` knows the Frobenius steps only).
 
-    def __init__(self, *args, loss="frobenius", **kwargs):
+    ``x_entry_weights`` / ``y_entry_weights`` (``resolve_entry_weights``): fixed non-negative weights per entry of X / Y on the
+    Frobenius objective, 1/2 |sqrt(Wx) .* (X - U V^T)|^2 + 1/2 |sqrt(Wy) .* (Y - V Z^T)|^2 (``cmf_mu_weighted_step``); a 0/1 mask
+    or ``'observed'`` fits the observed entries only.  The error metric weighs the residuals the same way; the loop stays on the
+    host."""
+
+    def __init__(self, *args, loss="frobenius", x_entry_weights=None, y_entry_weights=None, **kwargs):
         check_loss(loss)
+        check_entry_weights(x_entry_weights, y_entry_weights, "mu", loss)
         super().__init__(*args, **kwargs)
         self.loss = loss
+        self.x_entry_weights = x_entry_weights
+        self.y_entry_weights = y_entry_weights
+        self._weighted = x_entry_weights is not None or y_entry_weights is not None
+
+    def _weights_key(self):
+        return (id(self.x_entry_weights), id(self.y_entry_weights)) if self._weighted else ()
+
+    def _resolve_weights(self, X, Y):
+        key = (id(X), id(Y))
+        if getattr(self, "_resolved_for", None) != key:
+            self._resolved = (resolve_entry_weights(X, self.x_entry_weights, "x"), resolve_entry_weights(Y, self.y_entry_weights, "y"))
+            self._resolved_for, self._resolved_keep = key, (X, Y)
+        return self._resolved
+
+    def check_weights(self, X, Y):
+        """Raise the ValueError of unusable weights now, before any device is opened."""
+        self._resolve_weights(X, Y)
 
     def _device_step(self, l1_reg, l2_reg, alpha):
+        if self._weighted:
+            self._ctx.mu_weighted_step(l1_reg, l2_reg, self._update_mask())
+            return
         if self.loss == "kullback-leibler":
             self._ctx.mu_kl_step(l1_reg, l2_reg, self._update_mask())
             return
         self._ctx.mu_step(l1_reg, l2_reg, self._update_mask())
 
     def _device_error(self):
+        if self._weighted:
+            X, Y = self._XY
+            ex2, ey2 = self._ctx.weighted_residual_sq(X is not None, Y is not None)
+            return np.sqrt(max(ex2, 0.0)), np.sqrt(max(ey2, 0.0))
         if self.loss != "kullback-leibler":
             return super()._device_error()
         X, Y = self._XY
@@ -305,14 +425,14 @@ class HipMUSolver(_HipIterativeSolver):
         return np.sqrt(2.0 * max(dx, 0.0)), np.sqrt(2.0 * max(dy, 0.0))
 
     def _device_step_error(self, l1_reg, l2_reg, alpha):
-        if self.loss == "kullback-leibler":
+        if self.loss == "kullback-leibler" or self._weighted:
             return None
         ex2, ey2 = self._ctx.mu_step_error(l1_reg, l2_reg, self._update_mask())
         X, Y = self._XY
         return (np.sqrt(ex2) if X is not None else 0.0), (np.sqrt(ey2) if Y is not None else 0.0)
 
     def _run_params(self):
-        if self.loss == "kullback-leibler":
+        if self.loss == "kullback-leibler" or self._weighted:
             return None
         return dict(solver="mu", l1=self.l1_reg, l2=self.l2_reg, alpha_err=self.alpha, update_mask=self._update_mask())
 
