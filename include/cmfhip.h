@@ -62,6 +62,13 @@ enum {
     CMF_K_KLMU = 10,     /* Kullback-Leibler MU: fused quotient passes (T ./ (A B^T)) B, both products on the fp32 matrix pipe, and the divergence; flops 4 rows cols k per dense pass */
     CMF_K_COUNT = 11
 };
+/* CMF_K_COUNT is FROZEN at the eleven classes above (callers size their tables by it) and no longer counts the classes: the real
+ * bound is CMF_K_END -- cmf_kernel_time accepts every class below it.  A new class goes into THIS enum, numbered on, and moves
+ * CMF_K_END; the first enum does not change again.                                                                         */
+enum {
+    CMF_K_HALS = 11,     /* HALS sweeps (hals_sweep_kernel): F G[:, b] on the fp32 matrix pipe + the sequential part of a coordinate block; flops 2 rows k^2 per sweep */
+    CMF_K_END = 12
+};
 
 const char *cmf_last_error(void);
 /* sha256 of the sources the library was built from (everything under csrc/ and this header): pycmf_amd/_lib.py refuses a library whose stamp differs
@@ -240,6 +247,30 @@ int cmf_weighted_residual_sq(cmf_ctx *ctx, double *ex, double *ey);
 int cmf_mu_weighted_layout(cmf_ctx *ctx, int64_t *out4);
 int cmf_fill_weight_synthetic(cmf_ctx *ctx, int which, uint64_t seed, double density);
 int cmf_get_weight_block_f32(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, int64_t col0, int64_t ncols, float *host_dst);
+
+/* ---- HALS solver: cyclic coordinate descent on MU's objective ---------------------------------------------------------------
+ * The reference has multiplicative updates only for the non-negative Frobenius fit; sklearn's default for that objective is
+ * coordinate descent.  Here:
+ *   minimise  1/2 |X - U V^T|^2 + 1/2 |Y - V Z^T|^2 + l1 (sum U + sum V + sum Z) + l2 / 2 (|U|^2 + |V|^2 + |Z|^2),  U, V, Z >= 0
+ * in MU's sweep order V, U, Z (cmf_solvers.py:248-263), the new V used for U and Z.  One sweep of a factor F with numerator N
+ * and Gram G -- V: N = X^T U + Y Z, G = U^T U + Z^T Z;  U: N = X V, G = V^T V;  Z: N = Y^T V, G = V^T V -- runs, for every row f
+ * of F on its own,
+ *   for j = 0 .. k - 1:  h = G[j][j] + l2;  h == 0: f[j] stays;
+ *                        f[j] <- max(0, f[j] - (sum_l f[l] G[l][j] + l2 f[j] - N[j] + l1) / h)    (l < j: already updated)
+ * which is sklearn's _update_coordinate_descent without shuffling.  There is no EPS floor: exact zeros are results and can
+ * become positive again.  PRECONDITION: non-negative factors (data may have any sign).
+ * The products are the ones of cmf_mu_step (dense images and native CSR alike), run whole into its buffers; the sweep is
+ * csrc/cmf_hals.hip.h: F G[:, b] per block b of 32 coordinates on the fp32 matrix pipe, the 32 sequential steps of the block in
+ * registers.  Padding rows and columns of the factors stay zero.  No atomics: a repeated call from the same state is
+ * bit-identical.  k_pad > 256 (n_components above 256), or per-entry weights bound to the context (HALS has no weighted
+ * objective; it would silently ignore them): CMF_EUNSUPPORTED.  update_mask outside 1 .. 7, or a sweep whose data matrix has not
+ * been set: CMF_EINVAL.  One GPU; cmf_run is not extended (a HALS fit keeps its loop on the host) and the step
+ * is never captured into a graph.  cmf_mu_step's captured graph may be dropped and captured again; its results do not change.
+ *   cmf_hals_sweep (tests): one sweep of factor `which` (CMF_U | CMF_V | CMF_Z) with the caller's numerator N[rows x k] and Gram
+ *   G[k x k] (host, row-major float64, rounded to float32 on upload).  Needs cmf_set_problem and the factor, no data.
+ * Kernel time goes to class CMF_K_HALS. */
+int cmf_hals_step(cmf_ctx *ctx, double l1, double l2, int update_mask);
+int cmf_hals_sweep(cmf_ctx *ctx, int which, const double *N, const double *G, double l1, double l2);
 
 /* sharded form: rank g holds rows of X/U and columns of
  * Y/Z, V replicated.  buf is a DEVICE buffer of cmf_v_buf_elems() floats:

@@ -18,6 +18,10 @@ LINKS = {"linear": 0, "logit": 1}
 UPD_U, UPD_V, UPD_Z = 1, 2, 4
 K_GEMM_NN, K_GEMM_TN, K_GEMM_NT, K_ELEMWISE, K_EIGEN = 0, 1, 2, 3, 4
 KERNEL_CLASSES = {"gemm_nn": 0, "gemm_tn": 1, "gemm_nt": 2, "elementwise": 3, "eigen": 4, "gemm_small": 5, "spmm": 6, "rowhess": 7, "gemm_pair": 8, "topk": 9, "klmu": 10}
+# KERNEL_CLASSES mirrors the first enum of include/cmfhip.h, which is frozen at CMF_K_COUNT = 11 entries; the real bound of
+# cmf_kernel_time is CMF_K_END.  Classes added since live in the header's second enum and HERE: the next one is added to this
+# dict, not to KERNEL_CLASSES.  A caller that wants every class iterates both (tools/hals_timing.py).
+LATER_KERNEL_CLASSES = {"hals": 11}
 
 _ERR = {1: ValueError, 2: RuntimeError, 3: MemoryError, 4: RuntimeError, 5: NotImplementedError}
 
@@ -68,6 +72,8 @@ PROTOTYPES = {
     "cmf_mu_weighted_layout": [_vp, _pi64],
     "cmf_fill_weight_synthetic": [_vp, _i32, C.c_uint64, _dbl],
     "cmf_get_weight_block_f32": [_vp, _i32, _i64, _i64, _i64, _i64, _pf],
+    "cmf_hals_step": [_vp, _dbl, _dbl, _i32],
+    "cmf_hals_sweep": [_vp, _i32, _pd, _pd, _dbl, _dbl],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_mu_v_partials": [_vp, _vp],
     "cmf_mu_v_apply": [_vp, _vp, _dbl, _dbl],
@@ -505,6 +511,20 @@ class Context:
         check(self._lib.cmf_get_weight_block_f32(self._h, which, row0, nrows, col0, ncols, out.ctypes.data_as(_pf)))
         return out
 
+    # ---- HALS (csrc/cmf_hals.hip.h)
+    def hals_step(self, l1, l2, mask=7):
+        """One HALS iteration (coordinate-descent sweeps of V, U, Z) on the non-negative Frobenius objective."""
+        check(self._lib.cmf_hals_step(self._h, l1, l2, mask))
+
+    def hals_sweep(self, which, N, G, l1, l2):
+        """One coordinate-descent sweep of factor ``which`` with the caller's numerator N (rows x k) and Gram G (k x k)."""
+        m, d, p, k = self.shape
+        N = np.ascontiguousarray(N, dtype=np.float64)
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        if N.shape != ((m, d, p)[which], k) or G.shape != (k, k):
+            raise ValueError("hals_sweep: N must be %s and G %s, got %s and %s" % (((m, d, p)[which], k), (k, k), N.shape, G.shape))
+        check(self._lib.cmf_hals_sweep(self._h, which, N.ctypes.data_as(_pd), G.ctypes.data_as(_pd), l1, l2))
+
     def mu_step_error(self, l1, l2, mask=7):
         """One MU iteration and the squared residuals (ex2, ey2) of the factors it leaves, from the step's own products."""
         ex2, ey2 = C.c_double(0), C.c_double(0)
@@ -881,7 +901,7 @@ class Context:
     def kernel_time(self, cls):
         """(accumulated ms, launches, algorithmic flops) of one kernel class."""
         ms, n, fl = C.c_double(0), C.c_int64(0), C.c_double(0)
-        check(self._lib.cmf_kernel_time(self._h, KERNEL_CLASSES.get(cls, cls), C.byref(ms), C.byref(n), C.byref(fl)))
+        check(self._lib.cmf_kernel_time(self._h, KERNEL_CLASSES.get(cls, LATER_KERNEL_CLASSES.get(cls, cls)), C.byref(ms), C.byref(n), C.byref(fl)))
         return ms.value, n.value, fl.value
 
     def rowhess_samples(self):

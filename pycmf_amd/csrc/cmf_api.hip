@@ -139,6 +139,7 @@ struct cmf_ctx {
     float *wm_w[2] = {nullptr, nullptr}, *wm_p[2] = {nullptr, nullptr}; // dense weights W and P = W .* T, the relation's padded shape
     WCsrDev wm_sp[2][2];                  // [X|Y][pattern | its transpose]
     DevBuf wm_slab, wm_small, wm_part;    // numerator / denominator slabs, the residual's sum and its float64 partials
+    DevBuf hals_ws;                       // cmf_hals_sweep (test entry of cmf_hals.hip.h): the caller's numerator and Gram
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
     int opt_chol = 1;      // Cholesky fast path of the safe inverse (0: always Jacobi)
     int opt_chol_mfma = 1; // k_pad = 256 per-row solves: blocked Cholesky on the matrix pipe (0: the rank-1 register kernel chol_solve_kernel<16>)
@@ -245,9 +246,9 @@ struct cmf_ctx {
     int timing = 0;                       // 0 off | 1 events around every launch | 2 around the data-pass classes only
     std::vector<EvPair> pending;
     std::vector<hipEvent_t> evpool;
-    double ms[CMF_K_COUNT] = {0};
-    int64_t launches[CMF_K_COUNT] = {0};
-    double flops[CMF_K_COUNT] = {0};
+    double ms[CMF_K_END] = {0};
+    int64_t launches[CMF_K_END] = {0};
+    double flops[CMF_K_END] = {0};
     std::vector<hipEvent_t> markers;      // cmf_marker: per-iteration time series of a bench run
     // host <-> device staging: two pinned 64 MB buffers, filled / drained by several host threads while the other one is
     // on the wire (upload_strided / download_strided)
@@ -747,6 +748,7 @@ static void release_problem(cmf_ctx *c) {
     c->spmm_bar = DevBuf(); c->spmm_part = DevBuf();
     c->kl_slab = DevBuf(); c->kl_small = DevBuf(); c->kl_part = DevBuf();
     c->wm_slab = DevBuf(); c->wm_small = DevBuf(); c->wm_part = DevBuf();
+    c->hals_ws = DevBuf();
     for (int w = 0; w < 2; ++w) {
         c->wm_kind[w] = 0; c->wm_w[w] = c->wm_p[w] = nullptr;
         c->wm_sp[w][0] = WCsrDev(); c->wm_sp[w][1] = WCsrDev();
@@ -1795,7 +1797,7 @@ extern "C" int cmf_kernel_timing(cmf_ctx *c, int enable) {
     return CMF_OK;
 }
 extern "C" int cmf_kernel_time(cmf_ctx *c, int cls, double *ms, int64_t *launches, double *flops) {
-    if (!c || cls < 0 || cls >= CMF_K_COUNT) return fail(CMF_EINVAL, "bad kernel class");
+    if (!c || cls < 0 || cls >= CMF_K_END) return fail(CMF_EINVAL, "bad kernel class");
     DeviceGuard dg(c->device);
     CHK(flush_timing(c));
     if (ms) *ms = c->ms[cls];
@@ -1807,7 +1809,7 @@ extern "C" int cmf_kernel_timing_reset(cmf_ctx *c) {
     if (!c) return fail(CMF_EINVAL, "null context");
     DeviceGuard dg(c->device);
     CHK(flush_timing(c));
-    for (int i = 0; i < CMF_K_COUNT; ++i) { c->ms[i] = 0; c->launches[i] = 0; c->flops[i] = 0; }
+    for (int i = 0; i < CMF_K_END; ++i) { c->ms[i] = 0; c->launches[i] = 0; c->flops[i] = 0; }
     c->rh_credited = c->rh_gathered = 0.0;
     HIPCHK(hipMemsetAsync(c->dscalar + 7, 0, 8, c->stream));
     return CMF_OK;
@@ -1834,3 +1836,5 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_wmu.hip.h"
 #define CMF_RANK_HOST
 #include "cmf_rank.hip.h"
+#define CMF_HALS_HOST
+#include "cmf_hals.hip.h"

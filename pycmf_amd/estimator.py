@@ -12,7 +12,7 @@ from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
-from .solver_shell import HipMUSolver, HipNewtonSolver, check_loss, check_kl_data, check_entry_weights
+from .solver_shell import HipMUSolver, HipNewtonSolver, HipHALSSolver, check_loss, check_kl_data, check_entry_weights, check_hals
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -105,6 +105,12 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                         x_link=x_link, y_link=y_link,
                                         hessian_pertubation=hessian_pertubation,
                                         sg_sample_ratio=sg_sample_ratio, sg_sampler=sg_sampler, **common)
+    elif solver == "hals":
+        check_hals(U_non_negative, V_non_negative, Z_non_negative, n_gpus, n_components)
+        if x_link != "linear" or y_link != "linear":
+            warnings.warn("hals solver does not accept link functions other than linear, "
+                          "link arguments will be ignored")
+        solver_object = HipHALSSolver(**common)
     else:
         raise ValueError("No such solver: %s" % solver)
 

@@ -437,6 +437,39 @@ class HipMUSolver(_HipIterativeSolver):
         return dict(solver="mu", l1=self.l1_reg, l2=self.l2_reg, alpha_err=self.alpha, update_mask=self._update_mask())
 
 
+def check_hals(U_non_negative=True, V_non_negative=True, Z_non_negative=True, n_gpus=1, n_components=None):
+    """What the HALS solver cannot do, refused before any device is touched."""
+    if not (U_non_negative and V_non_negative and Z_non_negative):
+        raise ValueError("solver='hals' keeps every factor non-negative (that is the method): U_non_negative, V_non_negative and "
+                         "Z_non_negative must be True; for signed factors use solver='newton'")
+    if n_gpus != 1:
+        raise ValueError("solver='hals' runs on one GPU: n_gpus must be 1, got %r (the sharded form is not built)" % (n_gpus,))
+    if n_components is not None and n_components > 256:
+        raise NotImplementedError("solver='hals' is built for n_components <= 256, got %d" % (n_components,))
+
+
+class HipHALSSolver(_HipIterativeSolver):
+    """HALS, cyclic coordinate descent on MU's objective in MU's sweep order V -> U -> Z (``cmf_hals_step``): per factor one pass
+    over its k columns, every row solving its one-dimensional non-negative least-squares problems exactly -- sklearn's
+    ``solver='cd'`` without shuffling, per block of the collective model.  An iteration forms the products of an MU iteration and
+    needs far fewer of them.  Non-negative factors only; like MU it ignores alpha and the links.  The error metric is the
+    Frobenius one; the loop stays on the host (``cmf_run`` knows the MU and Newton steps only)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        check_hals(self.U_non_negative, self.V_non_negative, self.Z_non_negative)
+
+    def _bind_dims(self, X, Y, m, d, p, k):
+        check_hals(n_components=k)
+        return super()._bind_dims(X, Y, m, d, p, k)
+
+    def _device_step(self, l1_reg, l2_reg, alpha):
+        self._ctx.hals_step(l1_reg, l2_reg, self._update_mask())
+
+    def _run_params(self):
+        return None
+
+
 class HipNewtonSolver(_HipIterativeSolver):
     """Row-wise Newton-Raphson sweeps U -> Z -> V (pycmf/cmf_solvers.py:318-522) on the GPU.
 
