@@ -114,7 +114,9 @@ int cmf_sync(cmf_ctx *ctx);
  * result does not depend on it.  The same option fixes the shares of cmf_rank / cmf_rank_queries, whose result does not depend on
  * it either,
  * "kl_split" n: the dense passes of cmf_mu_kl_step / cmf_kl_divergence cut the streamed dimension into n shares (<= 0, default:
- * enough to give every CU a workgroup); another n regroups the float32 sums                                              */
+ * enough to give every CU a workgroup); another n regroups the float32 sums,
+ * "als_piece" n: stored entries per piece of a row in the normal-equation kernel of cmf_als_step (<= 0, default: 4096; rounded up
+ * to a multiple of 32); another n regroups the float32 sums                                                                */
 int cmf_set_option(cmf_ctx *ctx, const char *name, int64_t value);
 
 /* ---- problem ---------------------------------------------------------- */
@@ -271,6 +273,43 @@ int cmf_get_weight_block_f32(cmf_ctx *ctx, int which, int64_t row0, int64_t nrow
  * Kernel time goes to class CMF_K_HALS. */
 int cmf_hals_step(cmf_ctx *ctx, double l1, double l2, int update_mask);
 int cmf_hals_sweep(cmf_ctx *ctx, int which, const double *N, const double *G, double l1, double l2);
+
+/* ---- ALS solver: per-row normal equations over the observed entries ---------------------------------------------------------
+ * The standard method for a quadratic loss over an observed pattern; the reference has no counterpart (its solvers are mu and
+ * newton, neither with weights).  Here:
+ *   minimise  1/2 sum_{Ox} wx_ij (x_ij - u_i . v_j)^2 + 1/2 sum_{Oy} wy_jc (y_jc - v_j . z_c)^2 + l2 / 2 (|U|^2 + |V|^2 + |Z|^2)
+ * in MU's sweep order V, U, Z (cmf_solvers.py:248-263), the new V used for U and Z; only the factors in update_mask are swept.
+ * A relation is OBSERVED -- weights bound through cmf_set_weighted_csr: the loss runs over the stored pattern only -- or FULL --
+ * no weights: every cell counts with weight 1, zeros of a sparse matrix included; dense image or native CSR.  Every row f_i of
+ * the swept factor becomes the exact minimiser of its own system
+ *   (sum_{c in O_i} w_ic b_c b_c^T + S + l2 I) f_i = sum_{c in O_i} w_ic t_ic b_c + N_i
+ * with the sums over the observed relation(s) of the sweep and S = B^T B, N = T B of a full one (U: the X side, Z: the Y side,
+ * V: both, mixed freely).  A row without observations and without a full side solves to exact zeros.  A sweep without an observed
+ * side has ONE matrix for all rows: G + l2 I is inverted once in float64 and applied with one product.
+ * nn_mask (CMF_NN_*): the solved rows of those factors are projected, max(0, .), as the Newton solver honours *_non_negative.
+ * EXACT MINIMISATION PER ROW, AND WITH IT THE MONOTONE DESCENT OF THE OBJECTIVE, HOLDS FOR SIGNED FACTORS (nn_mask = 0) ONLY: the
+ * projection of an unconstrained minimiser is not the constrained one.  cmf_hals_step and cmf_mu_step / cmf_mu_weighted_step
+ * are the solvers built for non-negative factors.  There is no l1 term.
+ * The normal equations are formed by csrc/cmf_als.hip.h: gathered rows staged through LDS 32 at a time, H_i on the fp32 matrix
+ * pipe from ONE sqrt(w)-scaled image, rows longer than a piece length (option "als_piece" n, default 4096, rounded up to 32) cut
+ * into pieces whose partial sums are added in piece order.  No floating-point atomics: a repeated call from the same state is
+ * bit-identical.  The k x k solves are the plain Cholesky route of the per-row Newton sweeps (lambda_min(H_i) >= l2: the
+ * spectral clamp never acts; cmf_newton_clamp_stats stays at zero rows).  Padding rows and columns of the factors stay zero.
+ *   CMF_EINVAL: l2 <= 0, update_mask outside 1 .. 7, a swept relation with neither data nor CSR weights.
+ *   CMF_EUNSUPPORTED: k_pad > 256 (n_components above 256); a swept relation with DENSE weights bound (cmf_set_weight_f64 / _f32).
+ * One GPU; cmf_run is not extended (an ALS fit keeps its loop on the host) and the step is never captured into a graph.
+ * cmf_mu_step, cmf_mu_weighted_step, cmf_hals_step, cmf_newton_step keep their options, buffers and results; a captured graph of
+ * theirs may be dropped and captured again.  The error metric of such a fit is cmf_weighted_residual_sq (observed sides) /
+ * cmf_residual_sq (full sides).  Kernel time: the normal equations go to class CMF_K_ROWHESS (2 nnz k^2 flops), the solves to
+ * the classes the Newton sweeps charge.
+ *   cmf_als_normal (tests): the finished H_i (k_pad x k_pad, both triangles, 1 on the padding diagonal) and g_i (k_pad) of rows
+ *   [row0, row0 + nrows) of factor `which`, as the step would hand them to the solver, into host memory.  The sweep must have an
+ *   observed relation (CMF_EINVAL otherwise).
+ *   cmf_als_layout: out4 = { piece length, pieces of the U sweep, of the V sweep, of the Z sweep } (0 for a sweep without an
+ *   observed relation).                                                                                                       */
+int cmf_als_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask);
+int cmf_als_normal(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, double l2, float *host_H, float *host_g);
+int cmf_als_layout(cmf_ctx *ctx, int64_t *out4);
 
 /* sharded form: rank g holds rows of X/U and columns of
  * Y/Z, V replicated.  buf is a DEVICE buffer of cmf_v_buf_elems() floats:

@@ -3,7 +3,7 @@
 The public names are resolved on first use (PEP 562): ``from pycmf_amd import _lib`` -- what bench.py and the sharded
 drivers need -- then imports NumPy only, not scikit-learn / SciPy / pandas behind the estimator."""
 
-__all__ = ["CMF", "collective_matrix_factorization", "HipMUSolver", "HipNewtonSolver", "HipHALSSolver", "top_n_products", "rank_products",
+__all__ = ["CMF", "collective_matrix_factorization", "HipMUSolver", "HipNewtonSolver", "HipHALSSolver", "HipALSSolver", "top_n_products", "rank_products",
            "ranking_metrics"]
 
 
@@ -11,7 +11,7 @@ def __getattr__(name):
     if name in ("CMF", "collective_matrix_factorization"):
         from . import estimator
         return getattr(estimator, name)
-    if name in ("HipMUSolver", "HipNewtonSolver", "HipHALSSolver"):
+    if name in ("HipMUSolver", "HipNewtonSolver", "HipHALSSolver", "HipALSSolver"):
         from . import solver_shell
         return getattr(solver_shell, name)
     if name == "top_n_products":

@@ -74,6 +74,9 @@ PROTOTYPES = {
     "cmf_get_weight_block_f32": [_vp, _i32, _i64, _i64, _i64, _i64, _pf],
     "cmf_hals_step": [_vp, _dbl, _dbl, _i32],
     "cmf_hals_sweep": [_vp, _i32, _pd, _pd, _dbl, _dbl],
+    "cmf_als_step": [_vp, _dbl, _i32, _i32],
+    "cmf_als_normal": [_vp, _i32, _i64, _i64, _dbl, _pf, _pf],
+    "cmf_als_layout": [_vp, _pi64],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_mu_v_partials": [_vp, _vp],
     "cmf_mu_v_apply": [_vp, _vp, _dbl, _dbl],
@@ -524,6 +527,27 @@ class Context:
         if N.shape != ((m, d, p)[which], k) or G.shape != (k, k):
             raise ValueError("hals_sweep: N must be %s and G %s, got %s and %s" % (((m, d, p)[which], k), (k, k), N.shape, G.shape))
         check(self._lib.cmf_hals_sweep(self._h, which, N.ctypes.data_as(_pd), G.ctypes.data_as(_pd), l1, l2))
+
+    # ---- ALS (csrc/cmf_als.hip.h)
+    def als_step(self, l2, nn_mask=0, mask=7):
+        """One ALS iteration (V, U, Z): every row of a swept factor becomes the exact minimiser of its own normal equations over
+        the observed entries (relations with CSR weights) and all cells (relations without weights); ``nn_mask`` projects."""
+        check(self._lib.cmf_als_step(self._h, l2, nn_mask, mask))
+
+    def als_normal(self, which, row0, nrows, l2):
+        """(H float32[nrows, k_pad, k_pad], g float32[nrows, k_pad]): the finished normal equations of rows [row0, row0 + nrows)
+        of factor ``which`` as ``als_step`` would hand them to the solver."""
+        kp = self.geometry()[3]
+        H = np.empty((nrows, kp, kp), dtype=np.float32)
+        g = np.empty((nrows, kp), dtype=np.float32)
+        check(self._lib.cmf_als_normal(self._h, which, row0, nrows, l2, H.ctypes.data_as(_pf), g.ctypes.data_as(_pf)))
+        return H, g
+
+    def als_layout(self):
+        """(piece length, pieces of the U sweep, of the V sweep, of the Z sweep) of the ALS normal-equation kernel."""
+        out = (C.c_int64 * 4)()
+        check(self._lib.cmf_als_layout(self._h, out))
+        return tuple(out)
 
     def mu_step_error(self, l1, l2, mask=7):
         """One MU iteration and the squared residuals (ex2, ey2) of the factors it leaves, from the step's own products."""

@@ -12,7 +12,8 @@ from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
-from .solver_shell import HipMUSolver, HipNewtonSolver, HipHALSSolver, check_loss, check_kl_data, check_entry_weights, check_hals
+from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_entry_weights, check_hals,
+                           check_als)
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -65,6 +66,12 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     weight 1).  A relation without weights takes part with weight 1 everywhere.  Needs ``solver='mu'``, ``loss='frobenius'``
     and ``n_gpus=1`` (``ValueError`` otherwise, as for negative, NaN or infinite weights or a shape mismatch, before any device is
     touched); ``n_components`` above 256 is a ``NotImplementedError``.
+
+    ``solver='als'``: alternating least squares on that weighted objective plus l2/2 (|U|^2 + |V|^2 + |Z|^2) -- every factor row the
+    exact minimiser of its own normal equations over the observed entries (``HipALSSolver``).  Needs ``l2_reg > 0``,
+    ``l1_reg == 0``, ``loss='frobenius'`` and ``n_gpus=1`` (``ValueError`` otherwise, before any device is touched).  Exact
+    minimisation and monotone descent hold for signed factors (``U/V/Z_non_negative=False``); with ``*_non_negative=True`` the
+    solved rows are only projected, which is much weaker -- ``'hals'`` and ``'mu'`` are the solvers built for non-negative factors.
     """
     if n_components is None:
         n_components = max(X.shape[1], Y.shape[1])
@@ -111,6 +118,14 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
             warnings.warn("hals solver does not accept link functions other than linear, "
                           "link arguments will be ignored")
         solver_object = HipHALSSolver(**common)
+    elif solver == "als":
+        check_als(l1_reg, l2_reg, n_gpus, loss, n_components)
+        if x_link != "linear" or y_link != "linear":
+            warnings.warn("als solver does not accept link functions other than linear, "
+                          "link arguments will be ignored")
+        solver_object = HipALSSolver(U_non_negative=U_non_negative, V_non_negative=V_non_negative, Z_non_negative=Z_non_negative,
+                                     x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, **common)
+        solver_object.check_weights(X, Y)
     else:
         raise ValueError("No such solver: %s" % solver)
 
