@@ -289,7 +289,8 @@ int cmf_hals_sweep(cmf_ctx *ctx, int which, const double *N, const double *G, do
  * nn_mask (CMF_NN_*): the solved rows of those factors are projected, max(0, .), as the Newton solver honours *_non_negative.
  * EXACT MINIMISATION PER ROW, AND WITH IT THE MONOTONE DESCENT OF THE OBJECTIVE, HOLDS FOR SIGNED FACTORS (nn_mask = 0) ONLY: the
  * projection of an unconstrained minimiser is not the constrained one.  cmf_hals_step and cmf_mu_step / cmf_mu_weighted_step
- * are the solvers built for non-negative factors.  There is no l1 term.
+ * are the solvers built for non-negative factors, and cmf_als_nnls_step (below) is this step with the constrained row solve.
+ * There is no l1 term.
  * The normal equations are formed by csrc/cmf_als.hip.h: gathered rows staged through LDS 32 at a time, H_i on the fp32 matrix
  * pipe from ONE sqrt(w)-scaled image, rows longer than a piece length (option "als_piece" n, default 4096, rounded up to 32) cut
  * into pieces whose partial sums are added in piece order.  No floating-point atomics: a repeated call from the same state is
@@ -306,10 +307,27 @@ int cmf_hals_sweep(cmf_ctx *ctx, int which, const double *N, const double *G, do
  *   [row0, row0 + nrows) of factor `which`, as the step would hand them to the solver, into host memory.  The sweep must have an
  *   observed relation (CMF_EINVAL otherwise).
  *   cmf_als_layout: out4 = { piece length, pieces of the U sweep, of the V sweep, of the Z sweep } (0 for a sweep without an
- *   observed relation).                                                                                                       */
+ *   observed relation).
+ * NON-NEGATIVE ROWS BY COORDINATE DESCENT, cmf_als_nnls_step: the step above, except that a swept factor in nn_mask is not solved
+ * and projected: each of its rows runs `sweeps` (1 .. 1024) passes of cyclic coordinate descent on its own constrained problem
+ *   min_{f >= 0} 1/2 f^T H_i f - g_i^T f,     per pass:  r = g_i - H_i f;  for j = 0 .. k - 1:  new = max(0, f_j + r_j / H_jj),
+ *                                                        r -= (new - f_j) H_i[j, :],  f_j = new
+ * from the row it has (csrc/cmf_als_nnls.hip.h: one wave per row, H_i streamed once per pass, no Cholesky, the state of the
+ * Newton solves untouched).  Every coordinate step is an exact one-dimensional minimisation, so the objective descends
+ * monotonically WITH non-negative factors; one pass is a weighted HALS sweep, each row under its own Gram, many passes approach
+ * alternating non-negative least squares (4 is the documented choice).  There is no tolerance-based stop; a row that a whole pass
+ * leaves unchanged stops, which changes no bit.  A row without information becomes exact zeros.  A swept factor outside nn_mask
+ * takes the route of cmf_als_step, signed; with nn_mask = 0 the step IS cmf_als_step, byte for byte.  A factor in nn_mask whose
+ * relations are all full runs the sweep of cmf_hals_step (l1 = 0) `sweeps` times on its one Gram.  Validation as cmf_als_step,
+ * and CMF_EINVAL for sweeps outside 1 .. 1024.  Kernel time of the passes: class CMF_K_HALS, 2 rows k^2 sweeps flops.
+ *   cmf_als_nnls_rows (tests): the kernel on the caller's nrows systems in cmf_als_normal's layout (k / k_pad of the bound
+ *   problem; positive diagonals), host_f[nrows x k_pad] the start and the result.  CMF_EINVAL: a null pointer, nrows < 0, sweeps
+ *   outside 1 .. 1024, no problem bound; CMF_EUNSUPPORTED: k_pad > 256.                                                        */
 int cmf_als_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask);
 int cmf_als_normal(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, double l2, float *host_H, float *host_g);
 int cmf_als_layout(cmf_ctx *ctx, int64_t *out4);
+int cmf_als_nnls_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask, int sweeps);
+int cmf_als_nnls_rows(cmf_ctx *ctx, int64_t nrows, const float *host_H, const float *host_g, float *host_f, int sweeps);
 
 /* sharded form: rank g holds rows of X/U and columns of
  * Y/Z, V replicated.  buf is a DEVICE buffer of cmf_v_buf_elems() floats:

@@ -77,6 +77,8 @@ PROTOTYPES = {
     "cmf_als_step": [_vp, _dbl, _i32, _i32],
     "cmf_als_normal": [_vp, _i32, _i64, _i64, _dbl, _pf, _pf],
     "cmf_als_layout": [_vp, _pi64],
+    "cmf_als_nnls_step": [_vp, _dbl, _i32, _i32, _i32],
+    "cmf_als_nnls_rows": [_vp, _i64, _pf, _pf, _pf, _i32],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_mu_v_partials": [_vp, _vp],
     "cmf_mu_v_apply": [_vp, _vp, _dbl, _dbl],
@@ -548,6 +550,24 @@ class Context:
         out = (C.c_int64 * 4)()
         check(self._lib.cmf_als_layout(self._h, out))
         return tuple(out)
+
+    def als_nnls_step(self, l2, nn_mask, mask, sweeps):
+        """``als_step`` with the factors in ``nn_mask`` swept by ``sweeps`` passes of cyclic coordinate descent on each row's
+        non-negative least-squares problem (from the current rows) instead of solved and projected."""
+        check(self._lib.cmf_als_nnls_step(self._h, l2, nn_mask, mask, sweeps))
+
+    def als_nnls_rows(self, H, g, f, sweeps):
+        """The swept copy of ``f`` (nrows x k_pad): ``sweeps`` passes of the coordinate-descent kernel on the caller's systems
+        H float32[nrows, k_pad, k_pad], g float32[nrows, k_pad] (``als_normal``'s layout, k / k_pad of the bound problem)."""
+        kp = self.geometry()[3]
+        H = np.ascontiguousarray(H, dtype=np.float32)
+        g = np.ascontiguousarray(g, dtype=np.float32)
+        f = np.array(f, dtype=np.float32, order="C")
+        n = f.shape[0] if f.ndim == 2 else -1
+        if f.shape != (n, kp) or H.shape != (n, kp, kp) or g.shape != (n, kp):
+            raise ValueError("als_nnls_rows: H must be (n, %d, %d), g and f (n, %d), got %s, %s and %s" % (kp, kp, kp, H.shape, g.shape, f.shape))
+        check(self._lib.cmf_als_nnls_rows(self._h, n, H.ctypes.data_as(_pf), g.ctypes.data_as(_pf), f.ctypes.data_as(_pf), sweeps))
+        return f
 
     def mu_step_error(self, l1, l2, mask=7):
         """One MU iteration and the squared residuals (ex2, ey2) of the factors it leaves, from the step's own products."""

@@ -26,8 +26,12 @@
 // (lambda_min(H_i) >= l2: the spectral clamp never acts) and the float64 refinement off.
 // A sweep without an observed side has ONE matrix G + l2 I for all rows: inverted once in float64 (shared_inverse64) and applied
 // with one product.
+// Non-negative rows (cmf_als_nnls_step): the finished systems of a chunk go to als_nnls_kernel (cmf_als_nnls.hip.h) instead of the
+// Cholesky solves -- cyclic coordinate descent from the current rows, `sweeps` passes; a sweep whose relations are all full runs
+// hals_sweep (cmf_hals.hip.h) that many times on the one Gram.
 #pragma once
 #include "cmf_kernels.hip.h"
+#include "cmf_als_nnls.hip.h"
 
 namespace cmfk {
 
@@ -339,9 +343,27 @@ static int als_launch_normal(cmf_ctx *c, const cmfk::AlsArgs &a, int64_t npieces
     return CMF_OK;
 }
 
+static int als_nnls_launch(cmf_ctx *c, const float *H, const float *g, float *F, const int64_t *first, int64_t nrows, int sweeps) {
+    if (nrows <= 0) return CMF_OK;
+    cmfk::NnlsArgs a;
+    a.H = H; a.g = g; a.F = F; a.first = first; a.nrows = nrows; a.k = c->k; a.sweeps = sweeps;
+    Timed tm(c, CMF_K_HALS, 2.0 * (double)nrows * c->k * c->k * sweeps);
+    const dim3 grid((unsigned)((nrows + cmfk::NNLS_WAVES - 1) / cmfk::NNLS_WAVES)), block(64 * cmfk::NNLS_WAVES);
+    switch (c->kp) {
+    case 32: hipLaunchKernelGGL((cmfk::als_nnls_kernel<32>), grid, block, 0, c->stream, a); break;
+    case 64: hipLaunchKernelGGL((cmfk::als_nnls_kernel<64>), grid, block, 0, c->stream, a); break;
+    case 128: hipLaunchKernelGGL((cmfk::als_nnls_kernel<128>), grid, block, 0, c->stream, a); break;
+    case 256: hipLaunchKernelGGL((cmfk::als_nnls_kernel<256>), grid, block, 0, c->stream, a); break;
+    default: return fail(CMF_EUNSUPPORTED, "the non-negative row solve is built for n_components <= 256 (k_pad = %d)", c->kp);
+    }
+    HIPCHK(hipGetLastError());
+    return CMF_OK;
+}
+
 // Rows [r_begin, r_end) of the sweep of factor f in per-row form: normal equations chunk by chunk, then (solve) the Cholesky
-// solves into c->als_sol, or (host_H / host_g, one chunk) the finished systems back to the host.
-static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end, bool solve, float *host_H, float *host_g) {
+// solves into c->als_sol -- or, nnls_sweeps > 0, that many coordinate-descent sweeps of the chunk's rows of F, in place -- or
+// (host_H / host_g, one chunk) the finished systems back to the host.
+static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end, bool solve, float *host_H, float *host_g, int nnls_sweeps = 0) {
     using namespace cmfk;
     AlsRel rel[2], obs[2];
     const int nrel = als_rels(f, rel);
@@ -378,7 +400,7 @@ static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end
     CHK(kl_ensure(c, c->als_h, (size_t)std::max<int64_t>(1, max_rows) * kk * sizeof(float)));
     CHK(kl_ensure(c, c->als_part, (size_t)std::max<int64_t>(1, max_pieces) * (kk + kp) * sizeof(float)));
     CHK(kl_ensure(c, c->als_g, (size_t)rows_pad * kp * sizeof(float)));
-    CHK(kl_ensure(c, c->als_sol, (size_t)rows_pad * kp * sizeof(float)));
+    if (!nnls_sweeps) CHK(kl_ensure(c, c->als_sol, (size_t)rows_pad * kp * sizeof(float)));
     const size_t pbytes = std::max<size_t>(16, pl.pieces.size() * sizeof(AlsPiece)), fbytes = pl.first.size() * sizeof(int64_t);
     CHK(kl_ensure(c, c->als_desc, pbytes + fbytes));
     AlsPiece *dpieces = (AlsPiece *)c->als_desc.p;
@@ -395,7 +417,7 @@ static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end
         if (s == 0) a.s0 = sd; else a.s1 = sd;
     }
     float *Hc = (float *)c->als_h.p, *Hp = (float *)c->als_part.p;
-    float *grad = (float *)c->als_g.p, *sol = (float *)c->als_sol.p;
+    float *grad = (float *)c->als_g.p, *sol = (float *)c->als_sol.p;   // (sol: null and unused under nnls_sweeps)
     a.Hp = Hp;
     // the threshold of the plain Cholesky route, well below l2 <= lambda_min(H_i): its test (a Cholesky of H_i - pert I whose pivots
     // must exceed 4e-6 max H_jj) passes unless cond(H_i) is above ~2e5, where a float32 factorisation has nothing left to give
@@ -414,7 +436,10 @@ static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end
                                pbase, S, N ? N + row0 * kp : nullptr, (float)l2, c->k, kp, Hc, grad + row0 * kp);
             HIPCHK(hipGetLastError());
         }
-        if (solve) {
+        if (solve && nnls_sweeps) {
+            // the gathered factors are the other ones: the chunks to come do not read the rows written here
+            CHK(als_nnls_launch(c, Hc, grad + row0 * kp, c->F[f] + row0 * kp, full ? nullptr : dfirst + c0, nr, nnls_sweeps));
+        } else if (solve) {
             // the plain Cholesky route of the per-row Newton sweeps; what it reads of the Newton step's state is put back
             const bool save_psd = c->hess_psd;
             const int64_t save_r1 = c->rank1_rows, save_eig = c->eig_clamp_rows;
@@ -473,9 +498,23 @@ static int als_check(cmf_ctx *c, const char *what, double l2, int mask) {
     return CMF_OK;
 }
 
-extern "C" int cmf_als_step(cmf_ctx *c, double l2, int nn_mask, int mask) {
-    NEED_PROBLEM(c);
-    CHK(als_check(c, "cmf_als_step", l2, mask));
+// a non-negative sweep whose relations are all full: N and G as cmf_hals_step forms them, `sweeps` passes of hals_sweep
+static int als_nnls_sweep_shared(cmf_ctx *c, int f, double l2, int sweeps) {
+    const float *N = c->num, *G = c->G2;
+    if (f == CMF_V) {
+        CHK(cmf_mu_v_partials(c, c->vbuf));
+        N = c->vbuf;
+        G = c->vbuf + c->dp * c->kp;
+    } else {
+        CHK(gram32(c, c->F[CMF_V], c->dp, c->G2));
+        CHK(data_times(c, f == CMF_U ? 0 : 1, f == CMF_Z, c->F[CMF_V], c->num));
+    }
+    for (int s = 0; s < sweeps; ++s) CHK(hals_sweep(c, f, N, G, 0.0, l2));
+    return CMF_OK;
+}
+
+// sweeps == 0: the solved rows of the factors in nn_mask are projected; sweeps > 0: those factors are swept by coordinate descent
+static int als_step(cmf_ctx *c, double l2, int nn_mask, int mask, int sweeps) {
     DeviceGuard dg(c->device);
     const int bits[3] = {CMF_UPD_V, CMF_UPD_U, CMF_UPD_Z}, fs[3] = {CMF_V, CMF_U, CMF_Z}; // sweep order V, U, Z (cmf_solvers.py:248-263)
     const int nnb[3] = {CMF_NN_V, CMF_NN_U, CMF_NN_Z};
@@ -485,12 +524,55 @@ extern "C" int cmf_als_step(cmf_ctx *c, double l2, int nn_mask, int mask) {
         const bool nn = (nn_mask & nnb[s]) != 0;
         if (c->frows[f] <= 0) continue;
         if (!als_observed(c, f)) {
-            CHK(als_sweep_shared(c, f, l2, nn));
+            if (nn && sweeps) CHK(als_nnls_sweep_shared(c, f, l2, sweeps));
+            else CHK(als_sweep_shared(c, f, l2, nn));
+            continue;
+        }
+        if (nn && sweeps) {
+            CHK(als_rows(c, f, l2, 0, c->frows[f], true, nullptr, nullptr, sweeps));
             continue;
         }
         CHK(als_rows(c, f, l2, 0, c->frows[f], true, nullptr, nullptr));
         CHK(als_apply(c, f, (const float *)c->als_sol.p, nn));
     }
+    return CMF_OK;
+}
+
+extern "C" int cmf_als_step(cmf_ctx *c, double l2, int nn_mask, int mask) {
+    NEED_PROBLEM(c);
+    CHK(als_check(c, "cmf_als_step", l2, mask));
+    return als_step(c, l2, nn_mask, mask, 0);
+}
+
+static int als_nnls_sweeps_ok(const char *what, int sweeps) {
+    if (sweeps < 1 || sweeps > 1024) return fail(CMF_EINVAL, "%s: sweeps must be 1 .. 1024, got %d", what, sweeps);
+    return CMF_OK;
+}
+
+extern "C" int cmf_als_nnls_step(cmf_ctx *c, double l2, int nn_mask, int mask, int sweeps) {
+    NEED_PROBLEM(c);
+    CHK(als_check(c, "cmf_als_nnls_step", l2, mask));
+    CHK(als_nnls_sweeps_ok("cmf_als_nnls_step", sweeps));
+    return als_step(c, l2, nn_mask, mask, sweeps);
+}
+
+// test entry: the kernel on the caller's systems (cmf_als_normal's layout), f in / out
+extern "C" int cmf_als_nnls_rows(cmf_ctx *c, int64_t nrows, const float *host_H, const float *host_g, float *host_f, int sweeps) {
+    NEED_PROBLEM(c);
+    if (!host_H || !host_g || !host_f || nrows < 0) return fail(CMF_EINVAL, "cmf_als_nnls_rows: null pointer or negative row count");
+    CHK(als_nnls_sweeps_ok("cmf_als_nnls_rows", sweeps));
+    if (c->kp > 256) return fail(CMF_EUNSUPPORTED, "cmf_als_nnls_rows: n_components <= 256 only (k_pad = %d)", c->kp);
+    if (nrows == 0) return CMF_OK;
+    DeviceGuard dg(c->device);
+    const int64_t kp = c->kp, nh = nrows * kp * kp, nv = nrows * kp;
+    CHK(kl_ensure(c, c->als_nnls_ws, (size_t)(nh + 2 * nv) * sizeof(float)));
+    float *H = (float *)c->als_nnls_ws.p, *g = H + nh, *f = g + nv;
+    HIPCHK(hipMemcpyAsync(H, host_H, (size_t)nh * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(g, host_g, (size_t)nv * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(f, host_f, (size_t)nv * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    CHK(als_nnls_launch(c, H, g, f, nullptr, nrows, sweeps));
+    HIPCHK(hipMemcpyAsync(host_f, f, (size_t)nv * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return CMF_OK;
 }
 

@@ -142,6 +142,7 @@ struct cmf_ctx {
     DevBuf hals_ws;                       // cmf_hals_sweep (test entry of cmf_hals.hip.h): the caller's numerator and Gram
     int opt_als_piece = 0;                // ALS normal equations (cmf_als.hip.h): stored entries per piece of a row (<= 0: 4096; rounded up to 32)
     DevBuf als_h, als_part, als_g, als_sol, als_desc; // ... a chunk of per-row matrices, the pieces' partial sums, right-hand sides, solved rows, piece lists
+    DevBuf als_nnls_ws;                   // cmf_als_nnls_rows (test entry): the caller's systems and rows
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
     int opt_chol = 1;      // Cholesky fast path of the safe inverse (0: always Jacobi)
     int opt_chol_mfma = 1; // k_pad = 256 per-row solves: blocked Cholesky on the matrix pipe (0: the rank-1 register kernel chol_solve_kernel<16>)
@@ -751,7 +752,7 @@ static void release_problem(cmf_ctx *c) {
     c->kl_slab = DevBuf(); c->kl_small = DevBuf(); c->kl_part = DevBuf();
     c->wm_slab = DevBuf(); c->wm_small = DevBuf(); c->wm_part = DevBuf();
     c->hals_ws = DevBuf();
-    c->als_h = DevBuf(); c->als_part = DevBuf(); c->als_g = DevBuf(); c->als_sol = DevBuf(); c->als_desc = DevBuf();
+    c->als_h = DevBuf(); c->als_part = DevBuf(); c->als_g = DevBuf(); c->als_sol = DevBuf(); c->als_desc = DevBuf(); c->als_nnls_ws = DevBuf();
     for (int w = 0; w < 2; ++w) {
         c->wm_kind[w] = 0; c->wm_w[w] = c->wm_p[w] = nullptr;
         c->wm_sp[w][0] = WCsrDev(); c->wm_sp[w][1] = WCsrDev();

@@ -13,7 +13,7 @@ from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
 from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_entry_weights, check_hals,
-                           check_als)
+                           check_als, check_als_nn_sweeps)
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -41,7 +41,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                     x_link="linear", y_link="linear",
                                     hessian_pertubation=0.2, sg_sample_ratio=1.,
                                     device=0, sg_sampler="numpy", n_gpus=1, _return_solver=False, loss="frobenius",
-                                    x_entry_weights=None, y_entry_weights=None):
+                                    x_entry_weights=None, y_entry_weights=None, als_nn_sweeps=0):
     """Factorise X ~ f(U V^T) and Y ~ f(V Z^T) with a shared V on an MI355X.
 
     Same contract as the reference function (pycmf/cmf.py:215-456): returns
@@ -70,14 +70,19 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     ``solver='als'``: alternating least squares on that weighted objective plus l2/2 (|U|^2 + |V|^2 + |Z|^2) -- every factor row the
     exact minimiser of its own normal equations over the observed entries (``HipALSSolver``).  Needs ``l2_reg > 0``,
     ``l1_reg == 0``, ``loss='frobenius'`` and ``n_gpus=1`` (``ValueError`` otherwise, before any device is touched).  Exact
-    minimisation and monotone descent hold for signed factors (``U/V/Z_non_negative=False``); with ``*_non_negative=True`` the
-    solved rows are only projected, which is much weaker -- ``'hals'`` and ``'mu'`` are the solvers built for non-negative factors.
+    minimisation and monotone descent hold for signed factors (``U/V/Z_non_negative=False``); with ``*_non_negative=True`` and
+    ``als_nn_sweeps=0`` (default) the solved rows are only projected, which is much weaker.
+
+    ``als_nn_sweeps``: 0 | n in 1 .. 1024 (``solver='als'`` only; ``ValueError`` otherwise, before any device is touched).  n >= 1:
+    the rows of a non-negative factor run n passes of cyclic coordinate descent on their own non-negative least-squares problems
+    instead of solve-and-project -- monotone descent with non-negative factors; 4 is the documented choice (``HipALSSolver``).
     """
     if n_components is None:
         n_components = max(X.shape[1], Y.shape[1])
     _check_beta_loss(beta_loss)
     check_loss(loss, solver, n_gpus)
     check_entry_weights(x_entry_weights, y_entry_weights, solver, loss, n_gpus)
+    check_als_nn_sweeps(als_nn_sweeps, solver)
 
     if update_U or update_V:
         X = check_array(X, accept_sparse=('csr', 'csc'), dtype=float)
@@ -124,7 +129,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
             warnings.warn("als solver does not accept link functions other than linear, "
                           "link arguments will be ignored")
         solver_object = HipALSSolver(U_non_negative=U_non_negative, V_non_negative=V_non_negative, Z_non_negative=Z_non_negative,
-                                     x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, **common)
+                                     x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, nn_sweeps=als_nn_sweeps, **common)
         solver_object.check_weights(X, Y)
     else:
         raise ValueError("No such solver: %s" % solver)
@@ -249,6 +254,10 @@ class CMF(BaseEstimator, TransformerMixin):
     implement it; ``beta_loss`` stays parsed-and-ignored here too).  Needs ``solver='mu'``, ``n_gpus=1`` and non-negative X, Y.
     ``reconstruction_err_`` is then sqrt(2 D_x) + sqrt(2 D_y), the stopping test the reference's on
     alpha sqrt(2 D_x) + (1 - alpha) sqrt(2 D_y).
+
+    ``als_nn_sweeps`` (``solver='als'`` only, default 0): n >= 1 fits the rows of a non-negative factor by n passes of cyclic
+    coordinate descent on their non-negative least-squares problems instead of projecting the unconstrained solution
+    (``collective_matrix_factorization``); ``CMF(solver="als", l2_reg=0.05, als_nn_sweeps=4)`` is the documented choice.
     """
 
     def __init__(self, n_components=None, x_init=None, y_init=None, solver='mu', alpha='auto',
@@ -256,7 +265,7 @@ class CMF(BaseEstimator, TransformerMixin):
                  random_state=None, l1_reg=0., l2_reg=0., verbose=0,
                  U_non_negative=True, V_non_negative=True, Z_non_negative=True,
                  x_link="linear", y_link="linear", hessian_pertubation=0.2, sg_sample_ratio=1.,
-                 device=0, sg_sampler="numpy", n_gpus=1, loss="frobenius"):
+                 device=0, sg_sampler="numpy", n_gpus=1, loss="frobenius", als_nn_sweeps=0):
         self.n_components = n_components
         self.x_init = x_init
         self.y_init = y_init
@@ -280,6 +289,7 @@ class CMF(BaseEstimator, TransformerMixin):
         self.sg_sampler = sg_sampler
         self.n_gpus = n_gpus
         self.loss = loss
+        self.als_nn_sweeps = als_nn_sweeps
 
     def _kwargs(self):
         return dict(solver=self.solver, beta_loss=self.beta_loss, tol=self.tol, max_iter=self.max_iter,
@@ -289,7 +299,7 @@ class CMF(BaseEstimator, TransformerMixin):
                     x_link=self.x_link, y_link=self.y_link,
                     hessian_pertubation=self.hessian_pertubation,
                     sg_sample_ratio=self.sg_sample_ratio, device=self.device, sg_sampler=self.sg_sampler,
-                    loss=self.loss)
+                    loss=self.loss, als_nn_sweeps=self.als_nn_sweeps)
 
     def fit_transform(self, X, Y, U=None, V=None, Z=None, x_entry_weights=None, y_entry_weights=None):
         """``x_entry_weights`` / ``y_entry_weights``: per-entry weights of X / Y for this fit (``collective_matrix_factorization``);

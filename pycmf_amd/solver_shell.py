@@ -18,6 +18,7 @@ Semantics kept from the reference:
   the reference's order so that results are reproducible against it.
 * MU ignores alpha (its error metric uses the constructor default 0.5, :99).
 """
+import numbers
 import os
 import time
 
@@ -489,28 +490,48 @@ def check_als(l1_reg=0, l2_reg=1.0, n_gpus=1, loss="frobenius", n_components=Non
         raise NotImplementedError("solver='als' is built for n_components <= 256, got %d" % (n_components,))
 
 
+def check_als_nn_sweeps(als_nn_sweeps, solver="als"):
+    """``als_nn_sweeps``: an integer 0 .. 1024, non-zero with solver='als' only (no device is touched)."""
+    if isinstance(als_nn_sweeps, (bool, np.bool_)) or not isinstance(als_nn_sweeps, (numbers.Integral, np.integer)):
+        raise ValueError("als_nn_sweeps must be an integer 0 .. 1024, got %r" % (als_nn_sweeps,))
+    if als_nn_sweeps < 0 or als_nn_sweeps > 1024:
+        raise ValueError("als_nn_sweeps must be an integer 0 .. 1024, got %r" % (als_nn_sweeps,))
+    if als_nn_sweeps and solver != "als":
+        raise ValueError("als_nn_sweeps is the non-negative row solve of solver='als': it must be 0 with solver=%r, got %r" % (solver, als_nn_sweeps))
+
+
 class HipALSSolver(HipMUSolver):
-    """Alternating least squares in MU's sweep order V -> U -> Z (``cmf_als_step``) on
+    """Alternating least squares in MU's sweep order V -> U -> Z (``cmf_als_step`` / ``cmf_als_nnls_step``) on
 
         1/2 sum_{Ox} wx (x - u.v)^2 + 1/2 sum_{Oy} wy (y - v.z)^2 + l2/2 (|U|^2 + |V|^2 + |Z|^2),     l2 > 0, no l1 term.
 
-    Every row of a swept factor becomes the exact minimiser of its own k x k normal equations.  A relation with entry weights
+    Every row of a swept factor is fitted through its own k x k normal equations.  A relation with entry weights
     (``x_entry_weights`` / ``y_entry_weights``: a SciPy sparse W, ``'observed'``, or a dense W, which is converted to the CSR
     pattern of its non-zeros) counts over that pattern only; a relation without weights counts in every cell with weight 1, dense
     or sparse.  The weights are resolved as ``HipMUSolver`` resolves them.
 
-    EXACT MINIMISATION, AND WITH IT THE MONOTONE DESCENT OF THE OBJECTIVE, HOLDS FOR SIGNED FACTORS ONLY
-    (``U/V/Z_non_negative=False``).  ``*_non_negative=True`` is honoured the way the Newton solver honours it -- the solved row is
-    projected, max(0, .) -- which is not the constrained minimiser and is much weaker (planted rank 3, 30 % observed: RMSE on the
-    unobserved cells 0.152 projected against 0.066 signed after 10 iterations); ``solver='hals'`` and ``solver='mu'`` are the
-    solvers built for non-negative factors.  Like MU it ignores alpha and the links.  The error metric is the one of a weighted MU
-    fit, sqrt(sum wx e^2) + sqrt(sum wy e^2); the loop stays on the host (``cmf_run`` knows the MU and Newton steps only)."""
+    Signed factors (``U/V/Z_non_negative=False``): the row becomes the exact minimiser of its system, the objective descends
+    monotonically.  Non-negative factors are handled as ``nn_sweeps`` says:
+
+    ``nn_sweeps=n`` (1 .. 1024; 4 is the documented choice): each row of a non-negative factor runs n passes of cyclic coordinate
+    descent on its own non-negative least-squares problem, from the row it has.  Every coordinate step is an exact minimisation, so
+    the objective descends monotonically WITH non-negative factors; one pass is a weighted HALS sweep (each row under its own
+    Gram), many passes approach alternating non-negative least squares.  Planted rank 3, 30 % observed, 10 iterations: RMSE on the
+    unobserved cells 0.068 with n = 4 against 0.066 signed and 0.084 for the weighted MU after 300 iterations.
+
+    ``nn_sweeps=0`` (default): WITH ``*_non_negative=True`` THE SOLVED ROW IS ONLY PROJECTED, max(0, .), the way the Newton solver
+    honours the keyword -- NOT THE CONSTRAINED MINIMISER, NO MONOTONE DESCENT, and much weaker (the same problem: RMSE 0.152).
+
+    Like MU it ignores alpha and the links.  The error metric is the one of a weighted MU fit, sqrt(sum wx e^2) +
+    sqrt(sum wy e^2); the loop stays on the host (``cmf_run`` knows the MU and Newton steps only)."""
 
     _densify_unweighted = False
 
-    def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, **kwargs):
+    def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, **kwargs):
+        check_als_nn_sweeps(nn_sweeps)
         super().__init__(*args, loss="frobenius", x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, **kwargs)
         check_als(self.l1_reg, self.l2_reg)
+        self.nn_sweeps = int(nn_sweeps)
 
     def _resolve_weights(self, X, Y):
         key = (id(X), id(Y))
@@ -525,7 +546,10 @@ class HipALSSolver(HipMUSolver):
 
     def _device_step(self, l1_reg, l2_reg, alpha):
         check_als(l1_reg, l2_reg)
-        self._ctx.als_step(l2_reg, self._nn_mask(), self._update_mask())
+        if self.nn_sweeps:
+            self._ctx.als_nnls_step(l2_reg, self._nn_mask(), self._update_mask(), self.nn_sweeps)
+        else:
+            self._ctx.als_step(l2_reg, self._nn_mask(), self._update_mask())
 
     def _device_error(self):
         X, Y = self._XY
