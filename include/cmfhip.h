@@ -322,12 +322,32 @@ int cmf_hals_sweep(cmf_ctx *ctx, int which, const double *N, const double *G, do
  * and CMF_EINVAL for sweeps outside 1 .. 1024.  Kernel time of the passes: class CMF_K_HALS, 2 rows k^2 sweeps flops.
  *   cmf_als_nnls_rows (tests): the kernel on the caller's nrows systems in cmf_als_normal's layout (k / k_pad of the bound
  *   problem; positive diagonals), host_f[nrows x k_pad] the start and the result.  CMF_EINVAL: a null pointer, nrows < 0, sweeps
- *   outside 1 .. 1024, no problem bound; CMF_EUNSUPPORTED: k_pad > 256.                                                        */
+ *   outside 1 .. 1024, no problem bound; CMF_EUNSUPPORTED: k_pad > 256.
+ * SIGNED ROWS BY CONJUGATE GRADIENTS, cmf_als_cg_step: the step above, except that a swept factor that is SIGNED (outside nn_mask)
+ * and has an OBSERVED relation never forms H_i: each of its rows runs cg_steps (1 .. 1024) steps of plain conjugate gradients on
+ * H_i f = g_i from the row it has,
+ *   r = g - H f, p = r;  per step: q = H p, alpha = (r.r)/(p.q), f += alpha p, r -= alpha q, beta = (r'.r')/(r.r), p = r' + beta p,
+ * one product H_i x = sum_e w_e b_e (b_e . x) + S x + l2 x being one pass over the row's gathered factor rows (csrc/
+ * cmf_als_cg.hip.h: one workgroup per row, all steps in one launch, O(nnz k) per step instead of O(nnz k^2) + k^3 / 3; no
+ * normal equations, no Cholesky, the state of the Newton solves untouched).  Every step from a warm start lowers the row's
+ * quadratic, so the objective still descends monotonically; the rows are no longer exact minimisers (6 steps is the documented
+ * choice).  A row stops early when r.r or p.q is not a positive finite number and keeps what it has; a row without information
+ * becomes exact zeros.  Rows short enough keep their gathered rows in LDS between the passes (option "als_cg_lds" n: the most
+ * bytes of LDS a row may use for that; 0: every row gathers again each pass; < 0: the default, a quarter of the LDS) -- the result does
+ * not depend on it, nor on anything but the row itself: a repeated call from the same state is bit-identical.
+ * Everything else keeps its route and its bits: a factor in nn_mask is projected (nn_sweeps = 0) or swept by coordinate descent
+ * (nn_sweeps 1 .. 1024, as cmf_als_nnls_step); a sweep whose relations are all full takes the shared float64 inverse.
+ * Validation as cmf_als_step, and CMF_EINVAL for cg_steps outside 1 .. 1024 or nn_sweeps outside 0 .. 1024.  Kernel time: class
+ * CMF_K_ROWHESS, 4 nnz k (cg_steps + 1) flops, plus 2 rows k^2 (cg_steps + 1) with a full side.
+ *   cmf_als_cg_rows (tests): host_f[nrows x k_pad] = the rows the CG route would write for rows [row0, row0 + nrows) of the sweep
+ *   of factor `which`, from the current factors, which are left unchanged.  CMF_EINVAL for a sweep without an observed relation. */
 int cmf_als_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask);
 int cmf_als_normal(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, double l2, float *host_H, float *host_g);
 int cmf_als_layout(cmf_ctx *ctx, int64_t *out4);
 int cmf_als_nnls_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask, int sweeps);
 int cmf_als_nnls_rows(cmf_ctx *ctx, int64_t nrows, const float *host_H, const float *host_g, float *host_f, int sweeps);
+int cmf_als_cg_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask, int cg_steps, int nn_sweeps);
+int cmf_als_cg_rows(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, double l2, int cg_steps, float *host_f);
 
 /* sharded form: rank g holds rows of X/U and columns of
  * Y/Z, V replicated.  buf is a DEVICE buffer of cmf_v_buf_elems() floats:

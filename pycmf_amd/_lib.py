@@ -79,6 +79,8 @@ PROTOTYPES = {
     "cmf_als_layout": [_vp, _pi64],
     "cmf_als_nnls_step": [_vp, _dbl, _i32, _i32, _i32],
     "cmf_als_nnls_rows": [_vp, _i64, _pf, _pf, _pf, _i32],
+    "cmf_als_cg_step": [_vp, _dbl, _i32, _i32, _i32, _i32],
+    "cmf_als_cg_rows": [_vp, _i32, _i64, _i64, _dbl, _i32, _pf],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_mu_v_partials": [_vp, _vp],
     "cmf_mu_v_apply": [_vp, _vp, _dbl, _dbl],
@@ -568,6 +570,20 @@ class Context:
             raise ValueError("als_nnls_rows: H must be (n, %d, %d), g and f (n, %d), got %s, %s and %s" % (kp, kp, kp, H.shape, g.shape, f.shape))
         check(self._lib.cmf_als_nnls_rows(self._h, n, H.ctypes.data_as(_pf), g.ctypes.data_as(_pf), f.ctypes.data_as(_pf), sweeps))
         return f
+
+    def als_cg_step(self, l2, nn_mask, mask, cg_steps, nn_sweeps=0):
+        """``als_step`` with every signed swept factor that has an observed relation fitted by ``cg_steps`` matrix-free
+        conjugate-gradient steps per row (from the current rows) instead of the exact solves; the factors in ``nn_mask`` are
+        projected (``nn_sweeps=0``) or swept by coordinate descent as ``als_nnls_step`` does."""
+        check(self._lib.cmf_als_cg_step(self._h, l2, nn_mask, mask, cg_steps, nn_sweeps))
+
+    def als_cg_rows(self, which, row0, nrows, l2, cg_steps):
+        """float32[nrows, k_pad]: the rows ``als_cg_step`` would write for rows [row0, row0 + nrows) of factor ``which``; the
+        factors are left unchanged."""
+        kp = self.geometry()[3]
+        out = np.zeros((max(nrows, 0), kp), dtype=np.float32)
+        check(self._lib.cmf_als_cg_rows(self._h, which, row0, nrows, l2, cg_steps, out.ctypes.data_as(_pf)))
+        return out
 
     def mu_step_error(self, l1, l2, mask=7):
         """One MU iteration and the squared residuals (ex2, ey2) of the factors it leaves, from the step's own products."""

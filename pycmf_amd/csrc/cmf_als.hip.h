@@ -29,9 +29,13 @@
 // Non-negative rows (cmf_als_nnls_step): the finished systems of a chunk go to als_nnls_kernel (cmf_als_nnls.hip.h) instead of the
 // Cholesky solves -- cyclic coordinate descent from the current rows, `sweeps` passes; a sweep whose relations are all full runs
 // hals_sweep (cmf_hals.hip.h) that many times on the one Gram.
+// Signed rows by conjugate gradients (cmf_als_cg_step): a signed swept factor with an observed relation skips the normal equations
+// and the Cholesky solves altogether -- als_cg_kernel (cmf_als_cg.hip.h) runs `cg_steps` matrix-free CG steps per row from the
+// current rows, in place.  The host sorts the rows into a few LDS capacity classes by their length (als_cg_rows).
 #pragma once
 #include "cmf_kernels.hip.h"
 #include "cmf_als_nnls.hip.h"
+#include "cmf_als_cg.hip.h"
 
 namespace cmfk {
 
@@ -513,8 +517,109 @@ static int als_nnls_sweep_shared(cmf_ctx *c, int f, double l2, int sweeps) {
     return CMF_OK;
 }
 
-// sweeps == 0: the solved rows of the factors in nn_mask are projected; sweeps > 0: those factors are swept by coordinate descent
-static int als_step(cmf_ctx *c, double l2, int nn_mask, int mask, int sweeps) {
+enum { ALS_CG_LDS_TOTAL = 156 * 1024, ALS_CG_CLASSES = 4 };   // (156 KB: the largest dynamic LDS any kernel here asks for)
+// bytes of dynamic LDS the gathered rows of one row may take ("als_cg_lds": 0 every row streams; at most what is left of 156 KB).
+// The default leaves room for four workgroups per CU: measured on C5's pattern at k_pad = 256, rows of 100 entries resident at one
+// workgroup per CU take twice the time of the same rows gathered again in every pass at eight.
+static int64_t als_cg_lds_bytes(const cmf_ctx *c) {
+    const int64_t fixed = 4 * (int64_t)cmfk::als_cg_fixed_floats(c->kp);
+    return c->opt_als_cg_lds < 0 ? ALS_CG_LDS_TOTAL / 4 - fixed : std::min<int64_t>(c->opt_als_cg_lds, ALS_CG_LDS_TOTAL - fixed);
+}
+
+static int als_cg_launch(cmf_ctx *c, const cmfk::AlsCgArgs &a, int64_t nrows) {
+    if (nrows <= 0) return CMF_OK;
+    const size_t lds = 4 * (size_t)cmfk::als_cg_fixed_floats(c->kp) + (size_t)a.cap * cmfk::als_cg_entry_bytes(c->kp);
+    const dim3 grid((unsigned)nrows), block(256);
+#define ALS_CG_CASE(KP)                                                                                   \
+    case KP:                                                                                              \
+        CHK(allow_big_lds(c, (const void *)cmfk::als_cg_kernel<KP>, ALS_CG_LDS_TOTAL));                   \
+        hipLaunchKernelGGL((cmfk::als_cg_kernel<KP>), grid, block, lds, c->stream, a);                    \
+        break;
+    switch (c->kp) {
+    ALS_CG_CASE(32)
+    ALS_CG_CASE(64)
+    ALS_CG_CASE(128)
+    ALS_CG_CASE(256)
+    default: return fail(CMF_EUNSUPPORTED, "the conjugate-gradient row solve is built for n_components <= 256 (k_pad = %d)", c->kp);
+    }
+#undef ALS_CG_CASE
+    HIPCHK(hipGetLastError());
+    return CMF_OK;
+}
+
+// Rows [r_begin, r_end) of the sweep of factor f (which has an observed relation) by `steps` CG steps from the rows of c->F[f];
+// row r goes to Fout + (r - out_row0) * k_pad (in place: Fout = c->F[f], out_row0 = 0 -- the gathered factors are the other ones).
+// The rows are sorted into capacity classes by their stored entries: capacity / 8, / 4, / 2 and the whole capacity keep the
+// gathered rows in LDS (shorter rows: more workgroups per CU), longer rows stream; one launch per class.
+static int als_cg_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end, int steps, float *Fout, int64_t out_row0) {
+    using namespace cmfk;
+    AlsRel rel[2], obs[2];
+    const int nrel = als_rels(f, rel);
+    int nobs = 0;
+    const AlsRel *full = nullptr;
+    for (int s = 0; s < nrel; ++s) {
+        if (c->wm_kind[rel[s].which] == WM_CSR) obs[nobs++] = rel[s];
+        else full = &rel[s];
+    }
+    const int kp = c->kp;
+    const int64_t nrows = r_end - r_begin;
+    AlsCgArgs a;
+    memset(&a, 0, sizeof a);
+    if (full) { // as als_rows: the Gram of the full relation's factor and its product with the data
+        CHK(gram32(c, c->F[full->fb], c->frows_pad[full->fb], c->G2));
+        CHK(data_times(c, full->which, full->data_trans, c->F[full->fb], c->num));
+        a.S = c->G2;
+        a.N = c->num;
+    }
+    std::vector<int64_t> ip[2];
+    for (int s = 0; s < nobs; ++s) {
+        const WCsrDev &M = c->wm_sp[obs[s].which][obs[s].t];
+        CHK(als_fetch_indptr(c, M, r_begin, r_end, ip[s]));
+        AlsCgSide sd{M.indptr, M.idx, M.pv, M.wv, c->F[obs[s].fb]};
+        if (s == 0) a.s0 = sd; else a.s1 = sd;
+    }
+    const int64_t cap_max = als_cg_lds_bytes(c) / als_cg_entry_bytes(kp);
+    int64_t caps[ALS_CG_CLASSES + 1];
+    for (int q = 0; q < ALS_CG_CLASSES; ++q) caps[q] = cap_max >> (ALS_CG_CLASSES - 1 - q);
+    caps[ALS_CG_CLASSES] = 0;                                   // the streamed class
+    std::vector<int64_t> list[ALS_CG_CLASSES + 1];
+    int64_t nnz = 0;
+    for (int64_t r = 0; r < nrows; ++r) {
+        int64_t len = 0;
+        for (int s = 0; s < nobs; ++s) len += ip[s][(size_t)r + 1] - ip[s][(size_t)r];
+        if (len > INT32_MAX) return fail(CMF_EUNSUPPORTED, "cmf_als_cg_step: a row with more than 2^31 - 1 stored entries");
+        nnz += len;
+        int q = 0;
+        while (q < ALS_CG_CLASSES && len > caps[q]) ++q;
+        list[q].push_back(r_begin + r);
+    }
+    std::vector<int64_t> all;
+    all.reserve((size_t)nrows);
+    for (int q = 0; q <= ALS_CG_CLASSES; ++q) all.insert(all.end(), list[q].begin(), list[q].end());
+    CHK(kl_ensure(c, c->als_desc, std::max<size_t>(16, all.size() * sizeof(int64_t))));
+    int64_t *drows = (int64_t *)c->als_desc.p;
+    if (!all.empty()) HIPCHK(hipMemcpyAsync(drows, all.data(), all.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream)); // the host vector may go
+    a.Fin = c->F[f];
+    a.Fout = Fout;
+    a.out_row0 = out_row0;
+    a.l2 = (float)l2;
+    a.k = c->k;
+    a.steps = steps;
+    Timed tm(c, CMF_K_ROWHESS, (4.0 * (double)nnz * c->k + (full ? 2.0 * (double)nrows * c->k * c->k : 0.0)) * (steps + 1));
+    int64_t done = 0;
+    for (int q = 0; q <= ALS_CG_CLASSES; ++q) {
+        a.rows = drows + done;
+        a.cap = (int)caps[q];
+        CHK(als_cg_launch(c, a, (int64_t)list[q].size()));
+        done += (int64_t)list[q].size();
+    }
+    return CMF_OK;
+}
+
+// sweeps == 0: the solved rows of the factors in nn_mask are projected; sweeps > 0: those factors are swept by coordinate descent;
+// cg_steps > 0: a signed factor with an observed relation runs that many CG steps per row instead of the exact solves
+static int als_step(cmf_ctx *c, double l2, int nn_mask, int mask, int sweeps, int cg_steps = 0) {
     DeviceGuard dg(c->device);
     const int bits[3] = {CMF_UPD_V, CMF_UPD_U, CMF_UPD_Z}, fs[3] = {CMF_V, CMF_U, CMF_Z}; // sweep order V, U, Z (cmf_solvers.py:248-263)
     const int nnb[3] = {CMF_NN_V, CMF_NN_U, CMF_NN_Z};
@@ -530,6 +635,10 @@ static int als_step(cmf_ctx *c, double l2, int nn_mask, int mask, int sweeps) {
         }
         if (nn && sweeps) {
             CHK(als_rows(c, f, l2, 0, c->frows[f], true, nullptr, nullptr, sweeps));
+            continue;
+        }
+        if (!nn && cg_steps) {
+            CHK(als_cg_rows(c, f, l2, 0, c->frows[f], cg_steps, c->F[f], 0));
             continue;
         }
         CHK(als_rows(c, f, l2, 0, c->frows[f], true, nullptr, nullptr));
@@ -554,6 +663,39 @@ extern "C" int cmf_als_nnls_step(cmf_ctx *c, double l2, int nn_mask, int mask, i
     CHK(als_check(c, "cmf_als_nnls_step", l2, mask));
     CHK(als_nnls_sweeps_ok("cmf_als_nnls_step", sweeps));
     return als_step(c, l2, nn_mask, mask, sweeps);
+}
+
+static int als_cg_steps_ok(const char *what, int cg_steps) {
+    if (cg_steps < 1 || cg_steps > 1024) return fail(CMF_EINVAL, "%s: cg_steps must be 1 .. 1024, got %d", what, cg_steps);
+    return CMF_OK;
+}
+
+extern "C" int cmf_als_cg_step(cmf_ctx *c, double l2, int nn_mask, int mask, int cg_steps, int nn_sweeps) {
+    NEED_PROBLEM(c);
+    CHK(als_check(c, "cmf_als_cg_step", l2, mask));
+    CHK(als_cg_steps_ok("cmf_als_cg_step", cg_steps));
+    if (nn_sweeps < 0 || nn_sweeps > 1024) return fail(CMF_EINVAL, "cmf_als_cg_step: nn_sweeps must be 0 .. 1024, got %d", nn_sweeps);
+    return als_step(c, l2, nn_mask, mask, nn_sweeps, cg_steps);
+}
+
+// test entry: the rows the CG route would write for rows [row0, row0 + nrows) of sweep `which`; the factors are left alone
+extern "C" int cmf_als_cg_rows(cmf_ctx *c, int which, int64_t row0, int64_t nrows, double l2, int cg_steps, float *host_f) {
+    NEED_PROBLEM(c);
+    if (which < 0 || which > 2) return fail(CMF_EINVAL, "cmf_als_cg_rows: bad factor selector");
+    CHK(als_check(c, "cmf_als_cg_rows", l2, 1 << which));
+    CHK(als_cg_steps_ok("cmf_als_cg_rows", cg_steps));
+    if (row0 < 0 || nrows < 0 || row0 + nrows > c->frows[which]) return fail(CMF_EINVAL, "cmf_als_cg_rows: rows out of range");
+    if (!als_observed(c, which)) return fail(CMF_EINVAL, "cmf_als_cg_rows: this sweep has no observed relation: one shared matrix, no per-row systems");
+    if (nrows == 0) return CMF_OK;
+    if (!host_f) return fail(CMF_EINVAL, "cmf_als_cg_rows: null output");
+    DeviceGuard dg(c->device);
+    const size_t bytes = (size_t)nrows * c->kp * sizeof(float);
+    CHK(kl_ensure(c, c->als_cg_ws, bytes));
+    HIPCHK(hipMemsetAsync(c->als_cg_ws.p, 0, bytes, c->stream));
+    CHK(als_cg_rows(c, which, l2, row0, row0 + nrows, cg_steps, (float *)c->als_cg_ws.p, row0));
+    HIPCHK(hipMemcpyAsync(host_f, c->als_cg_ws.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CMF_OK;
 }
 
 // test entry: the kernel on the caller's systems (cmf_als_normal's layout), f in / out

@@ -1,0 +1,206 @@
+// cmf_als_cg.hip.h -- matrix-free conjugate-gradient row solves of the ALS solver (cmf_als_cg_step, cmf_als.hip.h)
+// Every row f_i of a signed swept factor with an observed relation runs `steps` steps of plain CG on the system of cmf_als.hip.h
+//   H_i f = g_i,    H_i = sum_{e in O_i} w_e b_e b_e^T + S + l2 I,    g_i = sum_{e in O_i} w_e t_e b_e + N_i
+// from the row it has, without ever forming H_i: one product is one pass over the row's gathered factor rows,
+//   H_i x = sum_e w_e b_e (b_e . x) + S x + l2 x,
+// O(nnz k) per step instead of O(nnz k^2) for the normal equations plus k^3 / 3 for the Cholesky solve.
+//     r = g - H f,  p = r;   per step:  q = H p,  alpha = (r.r) / (p.q),  f += alpha p,  r -= alpha q,  beta = (r'.r') / (r.r),  p = r' + beta p
+// with true divisions.  A row stops when r.r or p.q is not a positive finite number and keeps what it has.
+//
+// als_cg_kernel<KP>: one 256-thread workgroup per row, all steps inside the one launch, nothing shared between workgroups, no
+// atomics: the result of a row depends on that row alone and is deterministic to the bit.
+//   * A pass with vector x: the entries of side 0, then of side 1, in stored order.  Wave (e mod 4) takes entry e and holds b_e in
+//     registers, KP / 64 consecutive floats per lane (k_pad = 32: the upper half-wave holds zeros).  d_e = b_e . x by in-lane FMAs
+//     and a butterfly over the 64 lanes (offsets 32 .. 1: every lane ends with the same bits); acc += (w_e d_e) b_e goes into
+//     the wave's own accumulator.  The four accumulators are added through LDS in wave order by thread j < KP,
+//     which then adds (S x)_j = sum_c S[c][j] x_c for c ascending (x broadcast from LDS, the row of S coalesced and served by L2)
+//     and l2 x_j on the first k coordinates.  Padding coordinates stay exact zeros and are never written to the factor.
+//   * The first pass fuses the right-hand side: its coefficient is pv_e - w_e (b_e . f), so it yields r = g - H f directly.  A row
+//     is read steps + 1 times.
+//   * r.r and p.q: a butterfly inside each wave, the four wave sums added in wave order.
+//   * LDS residency: a row of at most `cap` entries keeps its gathered rows (and weights) in dynamic LDS after the first pass; a
+//     longer one gathers them again every pass.  Both forms run the same arithmetic in the same order on the same values, so the
+//     capacity class the host sorts a row into changes no bit of its result.
+// Vector stores only; no scratch.
+#pragma once
+#include "cmf_kernels.hip.h"
+
+namespace cmfk {
+
+struct AlsCgSide {
+    const int64_t *indptr;  // of the whole image (indexed by the row of the swept factor)
+    const int32_t *idx;
+    const float *pv, *wv;   // p = w t, w
+    const float *B;         // the gathered factor, pitch KP
+};
+struct AlsCgArgs {
+    AlsCgSide s0, s1;       // s1.indptr == nullptr: one side
+    const int64_t *rows;    // the rows of this launch (one per workgroup)
+    const float *S, *N;     // full side: Gram [KP][KP] and T B [rows][KP]; or null
+    const float *Fin;       // the swept factor, pitch KP (start of the iteration)
+    float *Fout;            // where row r goes: Fout + (r - out_row0) * KP
+    int64_t out_row0;
+    float l2;
+    int k, steps;
+    int cap;                // entries a row may keep resident in this launch's dynamic LDS (0: every row streams)
+};
+
+enum { ALS_CG_U = 4 };      // entries in flight per wave
+
+// dynamic LDS: x [KP] | wave accumulators [4][KP] | wave sums [16] | resident rows [cap][KP] | resident weights [cap]
+__host__ __device__ constexpr int als_cg_fixed_floats(int kp) { return 5 * kp + 16; }
+__host__ __device__ constexpr int als_cg_entry_bytes(int kp) { return 4 * kp + 4; }
+
+__device__ __forceinline__ float als_cg_wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void als_cg_kernel(AlsCgArgs g) {
+    constexpr int VPL = KP >= 64 ? KP / 64 : 1;     // floats of a gathered row per lane
+    extern __shared__ __attribute__((aligned(16))) float als_cg_lds[];
+    float *xs = als_cg_lds, *part = xs + KP, *wsum = part + 4 * KP, *res = wsum + 16;
+    const int t = threadIdx.x, lane = t & 63;
+    const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
+    const bool holds = lane * VPL < KP;              // k_pad = 32: lanes 32 .. 63 carry zeros
+    const int64_t row = g.rows[blockIdx.x];
+    const int64_t b0 = g.s0.indptr[row], b1 = g.s1.indptr ? g.s1.indptr[row] : 0;
+    const int n0 = (int)(g.s0.indptr[row + 1] - b0), n1 = g.s1.indptr ? (int)(g.s1.indptr[row + 1] - b1) : 0;
+    const int n = n0 + n1;
+    float *out = g.Fout + (row - g.out_row0) * KP;
+    if (n == 0 && !g.S) {                            // a row without information
+        if (t < g.k) out[t] = 0.f;
+        return;
+    }
+    const bool resident = n <= g.cap;
+    float *resw = res + (int64_t)g.cap * KP;
+    const int k = g.k;
+
+    // one pass: thread j < KP returns (sum_e coef_e b_e)_j + (S x)_j + l2 x_j with coef_e = w_e (b_e . x), or on the first pass
+    // (x = f) the negative of that plus sum_e pv_e b_e: coef_e = pv_e - w_e (b_e . f)
+    auto pass = [&](bool first) -> float {
+        float xr[VPL], acc[VPL];
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) {
+            xr[v] = holds ? xs[lane * VPL + v] : 0.f;
+            acc[v] = 0.f;
+        }
+        for (int e0 = uw; e0 < n; e0 += 4 * ALS_CG_U) {
+            float b[ALS_CG_U][VPL], w[ALS_CG_U], pv[ALS_CG_U];
+#pragma unroll
+            for (int u = 0; u < ALS_CG_U; ++u) {
+                const int e = e0 + 4 * u;            // wave-uniform
+#pragma unroll
+                for (int v = 0; v < VPL; ++v) b[u][v] = 0.f;
+                w[u] = pv[u] = 0.f;
+                if (e >= n) continue;
+                if (first || !resident) {
+                    const bool second = e >= n0;
+                    const int64_t q = second ? b1 + (e - n0) : b0 + e;
+                    w[u] = (second ? g.s1.wv : g.s0.wv)[q];
+                    if (first) pv[u] = (second ? g.s1.pv : g.s0.pv)[q];
+                    if (holds) {
+                        const float *src = (second ? g.s1.B : g.s0.B) + (int64_t)(second ? g.s1.idx : g.s0.idx)[q] * KP + lane * VPL;
+                        if constexpr (VPL == 4) {
+                            const f32x4 x4 = *reinterpret_cast<const f32x4 *>(src);
+                            b[u][0] = x4[0]; b[u][1] = x4[1]; b[u][2] = x4[2]; b[u][3] = x4[3];
+                        } else if constexpr (VPL == 2) {
+                            const float2 x2 = *reinterpret_cast<const float2 *>(src);
+                            b[u][0] = x2.x; b[u][1] = x2.y;
+                        } else {
+                            b[u][0] = src[0];
+                        }
+                    }
+                    if (first && resident) {
+                        if (holds) {
+                            float *dst = res + (int64_t)e * KP + lane * VPL;
+                            if constexpr (VPL == 4) *reinterpret_cast<f32x4 *>(dst) = f32x4{b[u][0], b[u][1], b[u][2], b[u][3]};
+                            else if constexpr (VPL == 2) *reinterpret_cast<float2 *>(dst) = make_float2(b[u][0], b[u][1]);
+                            else dst[0] = b[u][0];
+                        }
+                        if (lane == 0) resw[e] = w[u];
+                    }
+                } else {                             // written by this same wave in the first pass
+                    w[u] = resw[e];
+                    if (holds) {
+                        const float *src = res + (int64_t)e * KP + lane * VPL;
+                        if constexpr (VPL == 4) {
+                            const f32x4 x4 = *reinterpret_cast<const f32x4 *>(src);
+                            b[u][0] = x4[0]; b[u][1] = x4[1]; b[u][2] = x4[2]; b[u][3] = x4[3];
+                        } else if constexpr (VPL == 2) {
+                            const float2 x2 = *reinterpret_cast<const float2 *>(src);
+                            b[u][0] = x2.x; b[u][1] = x2.y;
+                        } else {
+                            b[u][0] = src[0];
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < ALS_CG_U; ++u) {
+                float d = 0.f;
+#pragma unroll
+                for (int v = 0; v < VPL; ++v) d = fmaf(b[u][v], xr[v], d);
+                d = als_cg_wave_sum(d);
+                const float coef = first ? pv[u] - w[u] * d : w[u] * d;
+#pragma unroll
+                for (int v = 0; v < VPL; ++v) acc[v] = fmaf(coef, b[u][v], acc[v]);
+            }
+        }
+        if (holds) {
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) part[uw * KP + lane * VPL + v] = acc[v];
+        }
+        __syncthreads();
+        float o = 0.f;
+        if (t < KP) {
+            o = ((part[t] + part[KP + t]) + part[2 * KP + t]) + part[3 * KP + t];
+            float sx = 0.f;
+            if (g.S) {
+                for (int c = 0; c < k; ++c) sx = fmaf(g.S[c * KP + t], xs[c], sx);
+            }
+            if (t < k) sx += g.l2 * xs[t];
+            o = first ? o - sx : o + sx;
+        }
+        return o;
+    };
+    // sum over the workgroup of v (zero in threads >= KP), the same bits in every thread; `slot` 0 | 1 alternates so that a
+    // buffer is rewritten only after a barrier has passed since its last read
+    auto dot = [&](float v, int slot) -> float {
+        v = als_cg_wave_sum(v);
+        if (lane == 0) wsum[4 * slot + uw] = v;
+        __syncthreads();
+        return ((wsum[4 * slot] + wsum[4 * slot + 1]) + wsum[4 * slot + 2]) + wsum[4 * slot + 3];
+    };
+
+    float f = 0.f, r = 0.f, p = 0.f;
+    if (t < KP) {
+        f = g.Fin[row * KP + t];
+        xs[t] = f;
+    }
+    __syncthreads();
+    r = pass(true);
+    if (t < KP && g.N) r += g.N[row * KP + t];
+    p = r;
+    float rr = dot(r * r, 0);
+    for (int s = 0; s < g.steps; ++s) {
+        if (!(rr > 0.f) || !(rr <= 3.402823466e38f)) break;     // zero, or not finite: the row keeps what it has
+        if (t < KP) xs[t] = p;
+        __syncthreads();
+        const float q = pass(false);
+        const float pq = dot(p * q, 1);
+        if (!(pq > 0.f) || !(pq <= 3.402823466e38f)) break;
+        const float alpha = rr / pq;
+        f = fmaf(alpha, p, f);
+        r = fmaf(-alpha, q, r);
+        const float rn = dot(r * r, 0);
+        const float beta = rn / rr;
+        p = fmaf(beta, p, r);
+        rr = rn;
+    }
+    if (t < k) out[t] = f;
+}
+
+} // namespace cmfk

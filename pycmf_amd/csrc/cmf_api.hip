@@ -143,6 +143,8 @@ struct cmf_ctx {
     int opt_als_piece = 0;                // ALS normal equations (cmf_als.hip.h): stored entries per piece of a row (<= 0: 4096; rounded up to 32)
     DevBuf als_h, als_part, als_g, als_sol, als_desc; // ... a chunk of per-row matrices, the pieces' partial sums, right-hand sides, solved rows, piece lists
     DevBuf als_nnls_ws;                   // cmf_als_nnls_rows (test entry): the caller's systems and rows
+    int opt_als_cg_lds = -1;              // CG row solves (cmf_als_cg.hip.h): most bytes of LDS a row's gathered rows may take (< 0: the default, a quarter of the LDS; 0: every row streams)
+    DevBuf als_cg_ws;                     // cmf_als_cg_rows (test entry): the rows it returns
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
     int opt_chol = 1;      // Cholesky fast path of the safe inverse (0: always Jacobi)
     int opt_chol_mfma = 1; // k_pad = 256 per-row solves: blocked Cholesky on the matrix pipe (0: the rank-1 register kernel chol_solve_kernel<16>)
@@ -752,7 +754,7 @@ static void release_problem(cmf_ctx *c) {
     c->kl_slab = DevBuf(); c->kl_small = DevBuf(); c->kl_part = DevBuf();
     c->wm_slab = DevBuf(); c->wm_small = DevBuf(); c->wm_part = DevBuf();
     c->hals_ws = DevBuf();
-    c->als_h = DevBuf(); c->als_part = DevBuf(); c->als_g = DevBuf(); c->als_sol = DevBuf(); c->als_desc = DevBuf(); c->als_nnls_ws = DevBuf();
+    c->als_h = DevBuf(); c->als_part = DevBuf(); c->als_g = DevBuf(); c->als_sol = DevBuf(); c->als_desc = DevBuf(); c->als_nnls_ws = DevBuf(); c->als_cg_ws = DevBuf();
     for (int w = 0; w < 2; ++w) {
         c->wm_kind[w] = 0; c->wm_w[w] = c->wm_p[w] = nullptr;
         c->wm_sp[w][0] = WCsrDev(); c->wm_sp[w][1] = WCsrDev();
@@ -907,6 +909,8 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
         c->opt_wmu_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "als_piece")) {
         c->opt_als_piece = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
+    } else if (!strcmp(name, "als_cg_lds")) {
+        c->opt_als_cg_lds = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "topk_split")) {
         c->opt_topk_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "sparse_mode")) {

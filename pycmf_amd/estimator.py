@@ -13,7 +13,7 @@ from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
 from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_entry_weights, check_hals,
-                           check_als, check_als_nn_sweeps)
+                           check_als, check_als_nn_sweeps, check_als_cg_steps)
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -41,7 +41,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                     x_link="linear", y_link="linear",
                                     hessian_pertubation=0.2, sg_sample_ratio=1.,
                                     device=0, sg_sampler="numpy", n_gpus=1, _return_solver=False, loss="frobenius",
-                                    x_entry_weights=None, y_entry_weights=None, als_nn_sweeps=0):
+                                    x_entry_weights=None, y_entry_weights=None, als_nn_sweeps=0, als_cg_steps=0):
     """Factorise X ~ f(U V^T) and Y ~ f(V Z^T) with a shared V on an MI355X.
 
     Same contract as the reference function (pycmf/cmf.py:215-456): returns
@@ -76,6 +76,12 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     ``als_nn_sweeps``: 0 | n in 1 .. 1024 (``solver='als'`` only; ``ValueError`` otherwise, before any device is touched).  n >= 1:
     the rows of a non-negative factor run n passes of cyclic coordinate descent on their own non-negative least-squares problems
     instead of solve-and-project -- monotone descent with non-negative factors; 4 is the documented choice (``HipALSSolver``).
+
+    ``als_cg_steps``: 0 | n in 1 .. 1024 (``solver='als'`` only; ``ValueError`` otherwise, and when every factor the call updates
+    is non-negative, before any device is touched).  n >= 1: the rows of a SIGNED factor (``*_non_negative=False``) with entry
+    weights on one of its relations run n matrix-free conjugate-gradient steps from the rows they have instead of forming and
+    factorising their k x k systems -- still a monotone descent, far cheaper per iteration; 6 is the documented choice
+    (``HipALSSolver``).  Non-negative factors keep the route ``als_nn_sweeps`` names, unweighted sweeps the shared inverse.
     """
     if n_components is None:
         n_components = max(X.shape[1], Y.shape[1])
@@ -83,6 +89,8 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     check_loss(loss, solver, n_gpus)
     check_entry_weights(x_entry_weights, y_entry_weights, solver, loss, n_gpus)
     check_als_nn_sweeps(als_nn_sweeps, solver)
+    check_als_cg_steps(als_cg_steps, solver, [nn for nn, upd in ((U_non_negative, update_U), (V_non_negative, update_V),
+                                                                 (Z_non_negative, update_Z)) if upd])
 
     if update_U or update_V:
         X = check_array(X, accept_sparse=('csr', 'csc'), dtype=float)
@@ -129,7 +137,8 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
             warnings.warn("als solver does not accept link functions other than linear, "
                           "link arguments will be ignored")
         solver_object = HipALSSolver(U_non_negative=U_non_negative, V_non_negative=V_non_negative, Z_non_negative=Z_non_negative,
-                                     x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, nn_sweeps=als_nn_sweeps, **common)
+                                     x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, nn_sweeps=als_nn_sweeps, cg_steps=als_cg_steps,
+                                     **common)
         solver_object.check_weights(X, Y)
     else:
         raise ValueError("No such solver: %s" % solver)
@@ -258,6 +267,11 @@ class CMF(BaseEstimator, TransformerMixin):
     ``als_nn_sweeps`` (``solver='als'`` only, default 0): n >= 1 fits the rows of a non-negative factor by n passes of cyclic
     coordinate descent on their non-negative least-squares problems instead of projecting the unconstrained solution
     (``collective_matrix_factorization``); ``CMF(solver="als", l2_reg=0.05, als_nn_sweeps=4)`` is the documented choice.
+
+    ``als_cg_steps`` (``solver='als'`` only, default 0): n >= 1 fits the rows of a signed factor that has entry weights by n
+    matrix-free conjugate-gradient steps instead of exact k x k solves (``collective_matrix_factorization``);
+    ``CMF(solver="als", l2_reg=0.05, als_cg_steps=6, U_non_negative=False, V_non_negative=False, Z_non_negative=False)`` is the
+    documented choice.
     """
 
     def __init__(self, n_components=None, x_init=None, y_init=None, solver='mu', alpha='auto',
@@ -265,7 +279,7 @@ class CMF(BaseEstimator, TransformerMixin):
                  random_state=None, l1_reg=0., l2_reg=0., verbose=0,
                  U_non_negative=True, V_non_negative=True, Z_non_negative=True,
                  x_link="linear", y_link="linear", hessian_pertubation=0.2, sg_sample_ratio=1.,
-                 device=0, sg_sampler="numpy", n_gpus=1, loss="frobenius", als_nn_sweeps=0):
+                 device=0, sg_sampler="numpy", n_gpus=1, loss="frobenius", als_nn_sweeps=0, als_cg_steps=0):
         self.n_components = n_components
         self.x_init = x_init
         self.y_init = y_init
@@ -290,6 +304,7 @@ class CMF(BaseEstimator, TransformerMixin):
         self.n_gpus = n_gpus
         self.loss = loss
         self.als_nn_sweeps = als_nn_sweeps
+        self.als_cg_steps = als_cg_steps
 
     def _kwargs(self):
         return dict(solver=self.solver, beta_loss=self.beta_loss, tol=self.tol, max_iter=self.max_iter,
@@ -299,7 +314,7 @@ class CMF(BaseEstimator, TransformerMixin):
                     x_link=self.x_link, y_link=self.y_link,
                     hessian_pertubation=self.hessian_pertubation,
                     sg_sample_ratio=self.sg_sample_ratio, device=self.device, sg_sampler=self.sg_sampler,
-                    loss=self.loss, als_nn_sweeps=self.als_nn_sweeps)
+                    loss=self.loss, als_nn_sweeps=self.als_nn_sweeps, als_cg_steps=self.als_cg_steps)
 
     def fit_transform(self, X, Y, U=None, V=None, Z=None, x_entry_weights=None, y_entry_weights=None):
         """``x_entry_weights`` / ``y_entry_weights``: per-entry weights of X / Y for this fit (``collective_matrix_factorization``);

@@ -500,6 +500,21 @@ def check_als_nn_sweeps(als_nn_sweeps, solver="als"):
         raise ValueError("als_nn_sweeps is the non-negative row solve of solver='als': it must be 0 with solver=%r, got %r" % (solver, als_nn_sweeps))
 
 
+def check_als_cg_steps(als_cg_steps, solver="als", updated_non_negative=None):
+    """``als_cg_steps``: an integer 0 .. 1024, non-zero with solver='als' only and only when some updated factor is signed
+    (``updated_non_negative``: the ``*_non_negative`` flags of the factors the call updates; None skips that test).  No device is
+    touched."""
+    if isinstance(als_cg_steps, (bool, np.bool_)) or not isinstance(als_cg_steps, (numbers.Integral, np.integer)):
+        raise ValueError("als_cg_steps must be an integer 0 .. 1024, got %r" % (als_cg_steps,))
+    if als_cg_steps < 0 or als_cg_steps > 1024:
+        raise ValueError("als_cg_steps must be an integer 0 .. 1024, got %r" % (als_cg_steps,))
+    if als_cg_steps and solver != "als":
+        raise ValueError("als_cg_steps is the conjugate-gradient row solve of solver='als': it must be 0 with solver=%r, got %r" % (solver, als_cg_steps))
+    if als_cg_steps and updated_non_negative is not None and all(updated_non_negative):
+        raise ValueError("als_cg_steps=%r acts on signed factors only, and every factor this call updates is non-negative "
+                         "(U/V/Z_non_negative=True is the default): pass *_non_negative=False, or use als_nn_sweeps" % (als_cg_steps,))
+
+
 class HipALSSolver(HipMUSolver):
     """Alternating least squares in MU's sweep order V -> U -> Z (``cmf_als_step`` / ``cmf_als_nnls_step``) on
 
@@ -522,16 +537,25 @@ class HipALSSolver(HipMUSolver):
     ``nn_sweeps=0`` (default): WITH ``*_non_negative=True`` THE SOLVED ROW IS ONLY PROJECTED, max(0, .), the way the Newton solver
     honours the keyword -- NOT THE CONSTRAINED MINIMISER, NO MONOTONE DESCENT, and much weaker (the same problem: RMSE 0.152).
 
+    ``cg_steps=n`` (1 .. 1024; 6 is the documented choice; default 0): a SIGNED factor with an OBSERVED relation (entry weights)
+    never forms its k x k systems -- each row runs n matrix-free conjugate-gradient steps from the row it has
+    (``cmf_als_cg_step``), O(nnz k) per step instead of O(nnz k^2) + k^3 / 3.  Every step lowers the row's quadratic, so the
+    descent stays monotone; the rows are no longer exact minimisers (planted rank 12, 50 % observed, 20 iterations: objective
+    50.05 with 6 steps against 50.46 exact, 51.45 with 4, 55.3 with 3, 60.8 with 2, 144.7 with 1).  A non-negative factor keeps the route ``nn_sweeps`` names,
+    a factor whose relations are all unweighted the one shared inverse; refused when every updated factor is non-negative.
+
     Like MU it ignores alpha and the links.  The error metric is the one of a weighted MU fit, sqrt(sum wx e^2) +
     sqrt(sum wy e^2); the loop stays on the host (``cmf_run`` knows the MU and Newton steps only)."""
 
     _densify_unweighted = False
 
-    def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, **kwargs):
+    def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, cg_steps=0, **kwargs):
         check_als_nn_sweeps(nn_sweeps)
+        check_als_cg_steps(cg_steps)
         super().__init__(*args, loss="frobenius", x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, **kwargs)
         check_als(self.l1_reg, self.l2_reg)
         self.nn_sweeps = int(nn_sweeps)
+        self.cg_steps = int(cg_steps)
 
     def _resolve_weights(self, X, Y):
         key = (id(X), id(Y))
@@ -546,7 +570,9 @@ class HipALSSolver(HipMUSolver):
 
     def _device_step(self, l1_reg, l2_reg, alpha):
         check_als(l1_reg, l2_reg)
-        if self.nn_sweeps:
+        if self.cg_steps:
+            self._ctx.als_cg_step(l2_reg, self._nn_mask(), self._update_mask(), self.cg_steps, self.nn_sweeps)
+        elif self.nn_sweeps:
             self._ctx.als_nnls_step(l2_reg, self._nn_mask(), self._update_mask(), self.nn_sweeps)
         else:
             self._ctx.als_step(l2_reg, self._nn_mask(), self._update_mask())
