@@ -349,6 +349,42 @@ int cmf_als_nnls_rows(cmf_ctx *ctx, int64_t nrows, const float *host_H, const fl
 int cmf_als_cg_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask, int cg_steps, int nn_sweeps);
 int cmf_als_cg_rows(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, double l2, int cg_steps, float *host_f);
 
+/* ---- ALS for implicit feedback: a background weight on the cells outside the pattern ----------------------------------------
+ * Clicks, plays, purchases: every stored target is 1, so a fit over the pattern alone is degenerate, and a fit with every cell at
+ * weight 1 lets a click count no more than a non-click.  The standard model (Hu, Koren, Volinsky: "Collaborative Filtering for
+ * Implicit Feedback Datasets") lies between the two.  For a relation with CSR weights w on its pattern O and a background weight
+ * c0 >= 0 the term of the objective is
+ *   1/2 sum_{O} w_ic (t_ic - a_i . b_c)^2  +  1/2 c0 sum_{(i,c) not in O} (a_i . b_c)^2,       w_ic >= c0 ON EVERY STORED ENTRY
+ * -- the dense weighted objective with W = c0 and target 0 off the pattern.  With the excess weights e = w - c0 a row's system is
+ *   H_i = sum_{c in O_i} e_ic b_c b_c^T + c0 B^T B + (Gram of a full side) + l2 I,    g_i = sum_{c in O_i} w_ic t_ic b_c + N_i,
+ * so no cell outside the pattern is ever visited: cost O(nnz k^2) + one Gram per sweep, as without a background.  A row without
+ * stored entries is an ordinary row (as under a full side): the exact route solves it to its minimiser, exact zeros when g_i = 0.
+ *   cmf_set_background_weight(ctx, which, c0): `which` (0 = X, 1 = Y) must have CSR weights bound (cmf_set_weighted_csr), c0 must
+ *   be finite and >= 0 (it is rounded to float32), and every stored weight must be >= c0 in float32 (a minimum taken on the
+ *   device) -- CMF_EINVAL otherwise, the state unchanged.  Builds the excess weights of both orientations of the pattern next to
+ *   the weights.  c0 = 0 frees them: the state of a context that never had a background.  cmf_set_weighted_csr, cmf_clear_weight,
+ *   cmf_set_weight_f32 / _f64 and cmf_set_problem reset the background of the relation to 0.
+ *   cmf_get_background_weight: the value in effect (0: none).
+ * HONOURED BY cmf_als_step, cmf_als_nnls_step and cmf_als_cg_step on every route a sweep with an observed side takes, and by
+ * cmf_als_normal / cmf_als_cg_rows (the systems and rows they return include it).  The kernels and their arithmetic are the
+ * ones above: they read e where they read w, and the shared matrix S becomes sum_sides coef Gram(B_side), coef = c0 for a side
+ * with a background, 1 for a full side (a V sweep can have two), each product and the sum rounded once, in the order X side, Y
+ * side.  With c0 = 0 every step is the step above, byte for byte.  The CG route reads S (k_pad^2 floats) once per row and pass,
+ * as a V sweep beside a full Y does; on patterns with a few very long columns (hot items) keep the exact route for V, as
+ * without a background (a CG row is one workgroup however long it is).
+ *   cmf_als_residual_sq: for a relation with CSR weights, with or without a background (CMF_EINVAL for a requested side without
+ *   CSR weights; either pointer may be NULL),
+ *     E = sum_O w (t - s)^2 + c0 (<A^T A, B^T B>_F - sum_O s^2),    s = a_i . b_c in float32,
+ *   both sums over the pattern from ONE pass in float64, the trace term from float64 Grams, clamped at 0; no atomics, a repeated
+ *   call is bit-identical.  With c0 = 0 it returns the bits of cmf_weighted_residual_sq, which is unchanged (pattern term only).
+ * NOT HONOURED by cmf_mu_weighted_step: with a background bound on a relation it reads it returns CMF_EUNSUPPORTED (clear it
+ * with cmf_set_background_weight(ctx, which, 0)).  cmf_mu_step, cmf_hals_step, cmf_newton_step and cmf_residual_sq ignore
+ * weights and background alike.  Kernel time: the excess weights and S go to CMF_K_ELEMWISE, the error's pass to CMF_K_KLMU, its
+ * Grams to CMF_K_GEMM_SMALL.                                                                                                 */
+int cmf_set_background_weight(cmf_ctx *ctx, int which, double c0);
+int cmf_get_background_weight(cmf_ctx *ctx, int which, double *c0);
+int cmf_als_residual_sq(cmf_ctx *ctx, double *ex, double *ey);
+
 /* sharded form: rank g holds rows of X/U and columns of
  * Y/Z, V replicated.  buf is a DEVICE buffer of cmf_v_buf_elems() floats:
  *   [ X_g^T U_g + Y_g Z_g  (d_pad x k_pad) | U_g^T U_g + Z_g^T Z_g (k_pad x k_pad) ]

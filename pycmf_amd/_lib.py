@@ -81,6 +81,9 @@ PROTOTYPES = {
     "cmf_als_nnls_rows": [_vp, _i64, _pf, _pf, _pf, _i32],
     "cmf_als_cg_step": [_vp, _dbl, _i32, _i32, _i32, _i32],
     "cmf_als_cg_rows": [_vp, _i32, _i64, _i64, _dbl, _i32, _pf],
+    "cmf_set_background_weight": [_vp, _i32, _dbl],
+    "cmf_get_background_weight": [_vp, _i32, _pd],
+    "cmf_als_residual_sq": [_vp, _pd, _pd],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_mu_v_partials": [_vp, _vp],
     "cmf_mu_v_apply": [_vp, _vp, _dbl, _dbl],
@@ -584,6 +587,24 @@ class Context:
         out = np.zeros((max(nrows, 0), kp), dtype=np.float32)
         check(self._lib.cmf_als_cg_rows(self._h, which, row0, nrows, l2, cg_steps, out.ctypes.data_as(_pf)))
         return out
+
+    # ---- ALS for implicit feedback (csrc/cmf_als_bg.hip.h)
+    def set_background_weight(self, which, c0):
+        """Background weight ``c0`` >= 0 on the cells outside the CSR pattern of relation ``which`` (0 X | 1 Y), honoured by the
+        ALS steps; every stored weight must be >= c0.  0 clears it."""
+        check(self._lib.cmf_set_background_weight(self._h, which, float(c0)))
+
+    def get_background_weight(self, which):
+        c0 = C.c_double(0)
+        check(self._lib.cmf_get_background_weight(self._h, which, C.byref(c0)))
+        return c0.value
+
+    def als_residual_sq(self, want_x=True, want_y=True):
+        """(E_x, E_y), E = sum_O w (t - s)^2 + c0 (<A^T A, B^T B> - sum_O s^2), of the relations with CSR weights; a side that is
+        not asked for comes back as 0.0."""
+        ex, ey = C.c_double(0), C.c_double(0)
+        check(self._lib.cmf_als_residual_sq(self._h, C.byref(ex) if want_x else None, C.byref(ey) if want_y else None))
+        return ex.value, ey.value
 
     def mu_step_error(self, l1, l2, mask=7):
         """One MU iteration and the squared residuals (ex2, ey2) of the factors it leaves, from the step's own products."""

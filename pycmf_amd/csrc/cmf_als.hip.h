@@ -32,10 +32,14 @@
 // Signed rows by conjugate gradients (cmf_als_cg_step): a signed swept factor with an observed relation skips the normal equations
 // and the Cholesky solves altogether -- als_cg_kernel (cmf_als_cg.hip.h) runs `cg_steps` matrix-free CG steps per row from the
 // current rows, in place.  The host sorts the rows into a few LDS capacity classes by their length (als_cg_rows).
+// Background weights (cmf_als_bg.hip.h, implicit feedback): an observed relation may count the cells outside its pattern with a
+// weight c0 -- the kernels above then read the excess weights w - c0 where they read w, and S becomes sum_sides coef Gram(B_side)
+// (als_shared_terms); everything that depended on "a full side exists" depends on "S is set".
 #pragma once
 #include "cmf_kernels.hip.h"
 #include "cmf_als_nnls.hip.h"
 #include "cmf_als_cg.hip.h"
+#include "cmf_als_bg.hip.h"
 
 namespace cmfk {
 
@@ -290,6 +294,8 @@ static int als_rels(int f, AlsRel out[2]) {
     out[1] = AlsRel{1, 0, CMF_Z, false};
     return 2;
 }
+#define CMF_ALS_BG_HOST
+#include "cmf_als_bg.hip.h"   // background weights: als_shared_terms, als_side_weights and the entry points of its own
 static int64_t als_piece_len(const cmf_ctx *c) { return c->opt_als_piece > 0 ? rup(c->opt_als_piece, 32) : (int64_t)ALS_PIECE_DEFAULT; }
 
 static int als_relation_ok(cmf_ctx *c, const char *what, int which) {
@@ -372,20 +378,13 @@ static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end
     AlsRel rel[2], obs[2];
     const int nrel = als_rels(f, rel);
     int nobs = 0;
-    const AlsRel *full = nullptr;
-    for (int s = 0; s < nrel; ++s) {
+    for (int s = 0; s < nrel; ++s)
         if (c->wm_kind[rel[s].which] == WM_CSR) obs[nobs++] = rel[s];
-        else full = &rel[s];
-    }
     const int kp = c->kp;
     const int64_t kk = (int64_t)kp * kp, rows_pad = c->frows_pad[f];
+    // the full relation: its Gram into every row's matrix, its product into the right-hand sides; a background: c0 times the Gram
     const float *S = nullptr, *N = nullptr;
-    if (full) { // the full relation: its Gram into every row's matrix, its product into the right-hand sides
-        CHK(gram32(c, c->F[full->fb], c->frows_pad[full->fb], c->G2));
-        CHK(data_times(c, full->which, full->data_trans, c->F[full->fb], c->num));
-        S = c->G2;
-        N = c->num;
-    }
+    CHK(als_shared_terms(c, rel, nrel, &S, &N));
     AlsPlan pl;
     CHK(als_plan(c, obs, nobs, r_begin, r_end, pl));
     const int64_t nrows = r_end - r_begin;
@@ -417,7 +416,7 @@ static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end
     memset(&a, 0, sizeof a);
     for (int s = 0; s < nobs; ++s) {
         const WCsrDev &M = c->wm_sp[obs[s].which][obs[s].t];
-        AlsSide sd{M.idx, M.pv, M.wv, c->F[obs[s].fb]};
+        AlsSide sd{M.idx, M.pv, als_side_weights(M), c->F[obs[s].fb]};
         if (s == 0) a.s0 = sd; else a.s1 = sd;
     }
     float *Hc = (float *)c->als_h.p, *Hp = (float *)c->als_part.p;
@@ -442,7 +441,7 @@ static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end
         }
         if (solve && nnls_sweeps) {
             // the gathered factors are the other ones: the chunks to come do not read the rows written here
-            CHK(als_nnls_launch(c, Hc, grad + row0 * kp, c->F[f] + row0 * kp, full ? nullptr : dfirst + c0, nr, nnls_sweeps));
+            CHK(als_nnls_launch(c, Hc, grad + row0 * kp, c->F[f] + row0 * kp, S ? nullptr : dfirst + c0, nr, nnls_sweeps));
         } else if (solve) {
             // the plain Cholesky route of the per-row Newton sweeps; what it reads of the Newton step's state is put back
             const bool save_psd = c->hess_psd;
@@ -556,26 +555,18 @@ static int als_cg_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_
     AlsRel rel[2], obs[2];
     const int nrel = als_rels(f, rel);
     int nobs = 0;
-    const AlsRel *full = nullptr;
-    for (int s = 0; s < nrel; ++s) {
+    for (int s = 0; s < nrel; ++s)
         if (c->wm_kind[rel[s].which] == WM_CSR) obs[nobs++] = rel[s];
-        else full = &rel[s];
-    }
     const int kp = c->kp;
     const int64_t nrows = r_end - r_begin;
     AlsCgArgs a;
     memset(&a, 0, sizeof a);
-    if (full) { // as als_rows: the Gram of the full relation's factor and its product with the data
-        CHK(gram32(c, c->F[full->fb], c->frows_pad[full->fb], c->G2));
-        CHK(data_times(c, full->which, full->data_trans, c->F[full->fb], c->num));
-        a.S = c->G2;
-        a.N = c->num;
-    }
+    CHK(als_shared_terms(c, rel, nrel, &a.S, &a.N)); // as als_rows
     std::vector<int64_t> ip[2];
     for (int s = 0; s < nobs; ++s) {
         const WCsrDev &M = c->wm_sp[obs[s].which][obs[s].t];
         CHK(als_fetch_indptr(c, M, r_begin, r_end, ip[s]));
-        AlsCgSide sd{M.indptr, M.idx, M.pv, M.wv, c->F[obs[s].fb]};
+        AlsCgSide sd{M.indptr, M.idx, M.pv, als_side_weights(M), c->F[obs[s].fb]};
         if (s == 0) a.s0 = sd; else a.s1 = sd;
     }
     const int64_t cap_max = als_cg_lds_bytes(c) / als_cg_entry_bytes(kp);
@@ -606,7 +597,7 @@ static int als_cg_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_
     a.l2 = (float)l2;
     a.k = c->k;
     a.steps = steps;
-    Timed tm(c, CMF_K_ROWHESS, (4.0 * (double)nnz * c->k + (full ? 2.0 * (double)nrows * c->k * c->k : 0.0)) * (steps + 1));
+    Timed tm(c, CMF_K_ROWHESS, (4.0 * (double)nnz * c->k + (a.S ? 2.0 * (double)nrows * c->k * c->k : 0.0)) * (steps + 1));
     int64_t done = 0;
     for (int q = 0; q <= ALS_CG_CLASSES; ++q) {
         a.rows = drows + done;

@@ -1,0 +1,295 @@
+// cmf_als_bg.hip.h -- ALS for implicit feedback: a background weight c0 >= 0 on the cells OUTSIDE the stored pattern of a relation
+// whose weights are bound as CSR (Hu, Koren, Volinsky: "Collaborative Filtering for Implicit Feedback Datasets").  Its term is
+//   1/2 sum_{O} w_ic (t_ic - a_i . b_c)^2  +  1/2 c0 sum_{(i, c) not in O} (a_i . b_c)^2,        w_ic >= c0 on every stored entry
+// -- the dense weighted objective with W = c0 and target 0 off the pattern.  With the EXCESS weights e_ic = w_ic - c0 >= 0 a row's
+// system is the one of cmf_als.hip.h with two substitutions:
+//   H_i = sum_{c in O_i} e_ic b_c b_c^T + c0 B^T B + (Gram of a full side) + l2 I,     g_i = sum_{c in O_i} w_ic t_ic b_c + N_i.
+// So the row kernels (als_normal_kernel, als_nnls_kernel, als_cg_kernel) run unchanged: they read the excess array where they read
+// wv, keep pv = w t, and the shared matrix S they already take becomes  sum_sides coef Gram(B_side),  coef = c0 for a side with a
+// background and 1 for a full side.  What this file adds:
+//   als_bg_excess_kernel   ev = wv - c0 (16-byte accesses) and the minimum of wv per workgroup -- the test w >= c0 runs where the
+//                          values live; 16 bytes of static LDS
+//   als_bg_combine_kernel  S = coef G, or S = S + coef G for the second side of a V sweep: products and sums rounded one by one (no
+//                          fma), so the result does not depend on how a compiler pairs them and a repeated call is bit-identical
+//   als_bg_res_csr_kernel<GL, CH>  wmu_res_csr_kernel with a second sum: one pass over the row image forms s = a_i . b_c in float32
+//                          and accumulates sum w (t - s)^2 AND sum s^2 in float64, one partial of each per workgroup in fixed
+//                          slots (summed in slot order by sum_doubles_kernel); 64 bytes of static LDS
+//   als_bg_dot64_kernel    <G_a, G_b>_F of two float64 Grams in one workgroup, fixed order; 2 KB of static LDS
+// The error of such a relation:  E = sum_O w (t - s)^2 + c0 (<A^T A, B^T B>_F - sum_O s^2),  clamped at 0.
+// No atomics; nothing here writes through a scalar path.  c0 = 0 frees the excess arrays: every route is then the code without
+// this file, byte for byte.
+#ifndef CMF_ALS_BG_KERNELS
+#define CMF_ALS_BG_KERNELS
+#include "cmf_kernels.hip.h"
+#include "cmf_wmu.hip.h"
+
+namespace cmfk {
+
+__global__ __launch_bounds__(256) void als_bg_excess_kernel(const float *wv, float c0, float *ev, int64_t n, float *minpart) {
+    const int64_t n4 = n >> 2;
+    float mn = INFINITY;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const f32x4 w = reinterpret_cast<const f32x4 *>(wv)[i];
+        mn = fminf(mn, fminf(fminf(w[0], w[1]), fminf(w[2], w[3])));
+        reinterpret_cast<f32x4 *>(ev)[i] = f32x4{w[0] - c0, w[1] - c0, w[2] - c0, w[3] - c0};
+    }
+    if (blockIdx.x == 0 && (int64_t)threadIdx.x < (n & 3)) { // the last n mod 4 entries
+        const int64_t q = 4 * n4 + threadIdx.x;
+        const float w = wv[q];
+        mn = fminf(mn, w);
+        ev[q] = w - c0;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_down(mn, off, 64));
+    __shared__ float red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
+    __syncthreads();
+    if (threadIdx.x == 0) minpart[blockIdx.x] = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+}
+
+__global__ void als_bg_combine_kernel(float *S, const float *G, float coef, int add, int n4) {
+#pragma clang fp contract(off)
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
+        const f32x4 g = reinterpret_cast<const f32x4 *>(G)[i];
+        f32x4 v{coef * g[0], coef * g[1], coef * g[2], coef * g[3]};
+        if (add) {
+            const f32x4 s = reinterpret_cast<const f32x4 *>(S)[i];
+            v = f32x4{s[0] + v[0], s[1] + v[1], s[2] + v[2], s[3] + v[3]};
+        }
+        reinterpret_cast<f32x4 *>(S)[i] = v;
+    }
+}
+
+// partials[b] = this workgroup's share of sum w (t - s)^2, partials[gridDim.x + b] = of sum s^2, both over the stored entries
+template <int GL, int CH>
+__global__ __launch_bounds__(256) void als_bg_res_csr_kernel(WCsrView T, const float *A, const float *B, int kp, double *partials) {
+    constexpr int RPW = 64 / GL;
+    const int lane = threadIdx.x & 63;
+    const int gl = lane % GL, gsub = lane / GL;
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t row = wave * RPW + gsub;
+    double acc = 0.0, acs = 0.0;
+    if (row < T.rows) {
+        f32x4 a[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) a[c] = *reinterpret_cast<const f32x4 *>(A + row * kp + 4 * (gl + GL * c));
+        const int64_t beg = T.indptr[row], end = T.indptr[row + 1];
+        for (int64_t q = beg; q < end; ++q) {
+            const int32_t j = T.idx[q];
+            const float t = T.tv[q], w = T.wv[q];
+            float d = 0.f;
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                const f32x4 b = *reinterpret_cast<const f32x4 *>(B + (int64_t)j * kp + 4 * (gl + GL * c));
+                d += a[c][0] * b[0] + a[c][1] * b[1] + a[c][2] * b[2] + a[c][3] * b[3];
+            }
+            d = group_sum<GL>(d);
+            const float e = t - d;
+            if (gl == 0) {
+                acc += (double)(w * (e * e));
+                acs += (double)(d * d);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        acc += __shfl_down(acc, off, 64);
+        acs += __shfl_down(acs, off, 64);
+    }
+    __shared__ double red[2][4];
+    if (lane == 0) {
+        red[0][threadIdx.x >> 6] = acc;
+        red[1][threadIdx.x >> 6] = acs;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        partials[gridDim.x + blockIdx.x] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    }
+}
+
+__global__ __launch_bounds__(256) void als_bg_dot64_kernel(const double *a, const double *b, int64_t n, double *out) {
+    __shared__ double red[256];
+    double v = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) v += a[i] * b[i];
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = red[0];
+}
+
+} // namespace cmfk
+#endif // CMF_ALS_BG_KERNELS
+
+// ------------------------------------------------------------------ host side (included by cmf_als.hip.h behind als_rels)
+#if defined(CMF_ALS_BG_HOST) && !defined(CMF_ALS_BG_HOST_DONE)
+#define CMF_ALS_BG_HOST_DONE
+
+// the weights the row kernels read for an observed side: the excess w - c0 under a background, w itself otherwise
+static const float *als_side_weights(const WCsrDev &M) { return M.ev ? M.ev : M.wv; }
+
+// The part of a sweep's systems that all its rows share: *S = sum_sides coef Gram(B_side) (coef: c0 of a side with a background,
+// 1 of a full side; null when no side has either) and *N = T B of the full side (or null).  Without a background this is the
+// code cmf_als.hip.h had in its place: the Gram of the full side in c->G2, nothing else launched.
+static int als_shared_terms(cmf_ctx *c, const AlsRel *rel, int nrel, const float **S, const float **N) {
+    *S = *N = nullptr;
+    bool bg = false;
+    for (int s = 0; s < nrel; ++s) bg = bg || (c->wm_kind[rel[s].which] == WM_CSR && c->wm_bg[rel[s].which] > 0.0);
+    if (!bg) {
+        for (int s = 0; s < nrel; ++s) {
+            if (c->wm_kind[rel[s].which] == WM_CSR) continue;
+            CHK(gram32(c, c->F[rel[s].fb], c->frows_pad[rel[s].fb], c->G2));
+            CHK(data_times(c, rel[s].which, rel[s].data_trans, c->F[rel[s].fb], c->num));
+            *S = c->G2;
+            *N = c->num;
+        }
+        return CMF_OK;
+    }
+    const int n4 = c->kp * c->kp / 4;
+    CHK(kl_ensure(c, c->als_bg_s, (size_t)n4 * 16));
+    int have = 0;
+    for (int s = 0; s < nrel; ++s) {   // the order of als_rels: the sum of a V sweep is (coef_x G_u) + (coef_y G_z)
+        const bool obs = c->wm_kind[rel[s].which] == WM_CSR;
+        if (obs && !(c->wm_bg[rel[s].which] > 0.0)) continue;
+        CHK(gram32(c, c->F[rel[s].fb], c->frows_pad[rel[s].fb], c->G2));
+        {
+            Timed tm(c, CMF_K_ELEMWISE);
+            hipLaunchKernelGGL(cmfk::als_bg_combine_kernel, dim3((unsigned)std::min(64, (n4 + 255) / 256)), dim3(256), 0, c->stream, (float *)c->als_bg_s.p,
+                               (const float *)c->G2, obs ? (float)c->wm_bg[rel[s].which] : 1.0f, have, n4);
+            HIPCHK(hipGetLastError());
+        }
+        have = 1;
+        if (!obs) {
+            CHK(data_times(c, rel[s].which, rel[s].data_trans, c->F[rel[s].fb], c->num));
+            *N = c->num;
+        }
+    }
+    *S = (const float *)c->als_bg_s.p;
+    return CMF_OK;
+}
+
+static void als_bg_drop(cmf_ctx *c, int which) {
+    for (int t = 0; t < 2; ++t) {
+        dev_free(c, c->wm_sp[which][t].ev);
+        c->wm_sp[which][t].ev = nullptr;
+    }
+    c->wm_bg[which] = 0.0;
+}
+
+extern "C" int cmf_set_background_weight(cmf_ctx *c, int which, double c0) {
+    NEED_PROBLEM(c);
+    if (which != 0 && which != 1) return fail(CMF_EINVAL, "cmf_set_background_weight: which must be 0 (X) or 1 (Y)");
+    const char *nm = which == 0 ? "X" : "Y";
+    if (c->wm_kind[which] != WM_CSR)
+        return fail(CMF_EINVAL, "cmf_set_background_weight: %s has no CSR weights bound (cmf_set_weighted_csr first)", nm);
+    const float cf = (float)c0;
+    if (!(c0 >= 0.0) || !std::isfinite(c0) || !std::isfinite(cf))
+        return fail(CMF_EINVAL, "cmf_set_background_weight: the background weight must be finite and >= 0 (in float32), got %g", c0);
+    DeviceGuard dg(c->device);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (cf == 0.f) {
+        als_bg_drop(c, which);
+        return CMF_OK;
+    }
+    float *ev[2] = {nullptr, nullptr};
+    unsigned blocks0 = 1;
+    for (int t = 0; t < 2; ++t) {
+        const WCsrDev &M = c->wm_sp[which][t];
+        const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(1024, ((M.nnz >> 2) + 255) / 256));
+        if (t == 0) blocks0 = blocks;
+        int rc = dev_alloc(c, (void **)&ev[t], std::max<size_t>((size_t)M.nnz * sizeof(float), 16), false);
+        if (rc == CMF_OK) rc = kl_ensure(c, c->wm_part, 2 * 1024 * sizeof(float));
+        if (rc != CMF_OK) {
+            dev_free(c, ev[0]); dev_free(c, ev[1]);
+            return rc;
+        }
+        Timed tm(c, CMF_K_ELEMWISE);
+        hipLaunchKernelGGL(cmfk::als_bg_excess_kernel, dim3(blocks), dim3(256), 0, c->stream, (const float *)M.wv, cf, ev[t], M.nnz,
+                           (float *)c->wm_part.p + 1024 * t);
+    }
+    float mins[1024];
+    hipError_t he = hipGetLastError();
+    if (he == hipSuccess) he = hipMemcpyAsync(mins, c->wm_part.p, blocks0 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    float mn = INFINITY;
+    for (unsigned b = 0; he == hipSuccess && b < blocks0; ++b) mn = std::min(mn, mins[b]);
+    if (he != hipSuccess || mn < cf) {
+        (void)hipStreamSynchronize(c->stream);
+        dev_free(c, ev[0]); dev_free(c, ev[1]);
+        if (he != hipSuccess) return fail(CMF_EHIP, "cmf_set_background_weight: %s", hipGetErrorString(he));
+        return fail(CMF_EINVAL, "cmf_set_background_weight: a stored weight of %s (%g) lies below the background weight %g: every stored entry must "
+                                "count at least as much as an unobserved cell", nm, (double)mn, (double)cf);
+    }
+    als_bg_drop(c, which);
+    c->wm_sp[which][0].ev = ev[0];
+    c->wm_sp[which][1].ev = ev[1];
+    c->wm_bg[which] = (double)cf;
+    return CMF_OK;
+}
+
+extern "C" int cmf_get_background_weight(cmf_ctx *c, int which, double *c0) {
+    NEED_PROBLEM(c);
+    if ((which != 0 && which != 1) || !c0) return fail(CMF_EINVAL, "cmf_get_background_weight: which must be 0 (X) or 1 (Y) and the output non-null");
+    *c0 = c->wm_bg[which];
+    return CMF_OK;
+}
+
+// E of one relation with CSR weights into *out (file header); without a background: the weighted residual, the same launches
+static int als_bg_residual_side(cmf_ctx *c, int which, double *out) {
+    if (!(c->wm_bg[which] > 0.0)) return wm_residual_side(c, which, out);
+    const int fa = which == 0 ? CMF_U : CMF_V, fb = which == 0 ? CMF_V : CMF_Z;
+    const float *A = c->F[fa], *B = c->F[fb];
+    const int64_t kk = (int64_t)c->kp * c->kp;
+    CHK(kl_ensure(c, c->wm_small, 64));
+    CHK(kl_ensure(c, c->als_bg64, (size_t)2 * kk * sizeof(double)));
+    double *sum = (double *)c->wm_small.p, *Ga = (double *)c->als_bg64.p, *Gb = Ga + kk;
+    const WCsrDev &M = c->wm_sp[which][0];
+    cmfk::WCsrView v{M.indptr, M.idx, M.pv, M.wv, M.tv, M.rows};
+    const int gl = c->kp / 4, rpw = 64 / gl;
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, ((M.rows + rpw - 1) / rpw + 3) / 4);
+    CHK(kl_ensure(c, c->wm_part, (size_t)2 * blocks * sizeof(double)));
+    double *part = (double *)c->wm_part.p;
+    {
+        Timed tm(c, CMF_K_KLMU, 2.0 * (double)M.nnz * (double)c->kp);
+        switch (c->kp) {
+        case 32: hipLaunchKernelGGL((cmfk::als_bg_res_csr_kernel<8, 1>), dim3(blocks), dim3(256), 0, c->stream, v, A, B, c->kp, part); break;
+        case 64: hipLaunchKernelGGL((cmfk::als_bg_res_csr_kernel<16, 1>), dim3(blocks), dim3(256), 0, c->stream, v, A, B, c->kp, part); break;
+        case 128: hipLaunchKernelGGL((cmfk::als_bg_res_csr_kernel<32, 1>), dim3(blocks), dim3(256), 0, c->stream, v, A, B, c->kp, part); break;
+        default: hipLaunchKernelGGL((cmfk::als_bg_res_csr_kernel<64, 1>), dim3(blocks), dim3(256), 0, c->stream, v, A, B, c->kp, part); break;
+        }
+        hipLaunchKernelGGL(cmfk::sum_doubles_kernel, dim3(1), dim3(256), 0, c->stream, (const double *)part, (int64_t)blocks, sum);
+        hipLaunchKernelGGL(cmfk::sum_doubles_kernel, dim3(1), dim3(256), 0, c->stream, (const double *)(part + blocks), (int64_t)blocks, sum + 1);
+        HIPCHK(hipGetLastError());
+    }
+    CHK(gram64(c, A, c->frows_pad[fa], Ga, nullptr));
+    CHK(gram64(c, B, c->frows_pad[fb], Gb, nullptr));
+    {
+        Timed tm(c, CMF_K_GEMM_SMALL, 2.0 * (double)kk);
+        hipLaunchKernelGGL(cmfk::als_bg_dot64_kernel, dim3(1), dim3(256), 0, c->stream, (const double *)Ga, (const double *)Gb, kk, sum + 2);
+        HIPCHK(hipGetLastError());
+    }
+    double h[3];
+    HIPCHK(hipMemcpyAsync(h, sum, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *out = std::max(0.0, h[0] + c->wm_bg[which] * (h[2] - h[1]));
+    return CMF_OK;
+}
+
+extern "C" int cmf_als_residual_sq(cmf_ctx *c, double *ex, double *ey) {
+    NEED_PROBLEM(c);
+    CHK(wm_check(c, "cmf_als_residual_sq"));
+    double *want[2] = {ex, ey};
+    for (int w = 0; w < 2; ++w)
+        if (want[w] && c->wm_kind[w] != WM_CSR)
+            return fail(CMF_EINVAL, "cmf_als_residual_sq: %s has no CSR weights bound (cmf_set_weighted_csr); a full relation's error is cmf_residual_sq",
+                        w == 0 ? "X" : "Y");
+    DeviceGuard dg(c->device);
+    for (int w = 0; w < 2; ++w)
+        if (want[w]) CHK(als_bg_residual_side(c, w, want[w]));
+    return CMF_OK;
+}
+
+#endif // CMF_ALS_BG_HOST

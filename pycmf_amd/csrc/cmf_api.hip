@@ -88,6 +88,7 @@ struct WCsrDev {
     int64_t *indptr = nullptr;
     int32_t *idx = nullptr;
     float *pv = nullptr, *wv = nullptr, *tv = nullptr;
+    float *ev = nullptr;   // excess weights w - c0 under a background weight (cmf_als_bg.hip.h), or null
     int64_t rows = 0, cols = 0, nnz = 0;
 };
 
@@ -145,6 +146,8 @@ struct cmf_ctx {
     DevBuf als_nnls_ws;                   // cmf_als_nnls_rows (test entry): the caller's systems and rows
     int opt_als_cg_lds = -1;              // CG row solves (cmf_als_cg.hip.h): most bytes of LDS a row's gathered rows may take (< 0: the default, a quarter of the LDS; 0: every row streams)
     DevBuf als_cg_ws;                     // cmf_als_cg_rows (test entry): the rows it returns
+    double wm_bg[2] = {0.0, 0.0};         // background weight c0 of X / Y on the cells outside a CSR pattern (cmf_als_bg.hip.h; 0: none)
+    DevBuf als_bg_s, als_bg64;            // ... the shared matrix sum coef Gram of a sweep; float64 Grams of the error's trace term
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
     int opt_chol = 1;      // Cholesky fast path of the safe inverse (0: always Jacobi)
     int opt_chol_mfma = 1; // k_pad = 256 per-row solves: blocked Cholesky on the matrix pipe (0: the rank-1 register kernel chol_solve_kernel<16>)
@@ -755,7 +758,9 @@ static void release_problem(cmf_ctx *c) {
     c->wm_slab = DevBuf(); c->wm_small = DevBuf(); c->wm_part = DevBuf();
     c->hals_ws = DevBuf();
     c->als_h = DevBuf(); c->als_part = DevBuf(); c->als_g = DevBuf(); c->als_sol = DevBuf(); c->als_desc = DevBuf(); c->als_nnls_ws = DevBuf(); c->als_cg_ws = DevBuf();
+    c->als_bg_s = DevBuf(); c->als_bg64 = DevBuf();
     for (int w = 0; w < 2; ++w) {
+        c->wm_bg[w] = 0.0;
         c->wm_kind[w] = 0; c->wm_w[w] = c->wm_p[w] = nullptr;
         c->wm_sp[w][0] = WCsrDev(); c->wm_sp[w][1] = WCsrDev();
     }

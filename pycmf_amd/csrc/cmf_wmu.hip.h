@@ -404,10 +404,11 @@ static void wm_free_side(cmf_ctx *c, int which) {
     c->wm_w[which] = c->wm_p[which] = nullptr;
     for (int t = 0; t < 2; ++t) {
         WCsrDev &M = c->wm_sp[which][t];
-        dev_free(c, M.indptr); dev_free(c, M.idx); dev_free(c, M.pv); dev_free(c, M.wv); dev_free(c, M.tv);
+        dev_free(c, M.indptr); dev_free(c, M.idx); dev_free(c, M.pv); dev_free(c, M.wv); dev_free(c, M.tv); dev_free(c, M.ev);
         M = WCsrDev();
     }
     c->wm_kind[which] = WM_NONE;
+    c->wm_bg[which] = 0.0;   // a background weight (cmf_als_bg.hip.h) goes with the weights it was set on
 }
 
 // kl_plan's share rule for the dense passes (option "wmu_split" forces the count); S = 1 for weights held as CSR
@@ -535,6 +536,10 @@ extern "C" int cmf_mu_weighted_step(cmf_ctx *c, double l1, double l2, int mask) 
     CHK(wm_check(c, "cmf_mu_weighted_step"));
     if (mask & (CMF_UPD_U | CMF_UPD_V)) CHK(wm_side_ok(c, "cmf_mu_weighted_step", 0));
     if (mask & (CMF_UPD_Z | CMF_UPD_V)) CHK(wm_side_ok(c, "cmf_mu_weighted_step", 1));
+    for (int w = 0; w < 2; ++w)
+        if (c->wm_bg[w] > 0.0 && (mask & ((w == 0 ? CMF_UPD_U : CMF_UPD_Z) | CMF_UPD_V)))
+            return fail(CMF_EUNSUPPORTED, "cmf_mu_weighted_step: %s has a background weight bound, which only the ALS steps honour; "
+                                          "clear it with cmf_set_background_weight(ctx, %d, 0)", w == 0 ? "X" : "Y", w);
     DeviceGuard dg(c->device);
     CHK(kl_ensure(c, c->wm_slab, wm_slab_bytes(c, mask)));
     float *base = (float *)c->wm_slab.p;

@@ -13,7 +13,7 @@ from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
 from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_entry_weights, check_hals,
-                           check_als, check_als_nn_sweeps, check_als_cg_steps)
+                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_background_weight)
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -41,7 +41,8 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                     x_link="linear", y_link="linear",
                                     hessian_pertubation=0.2, sg_sample_ratio=1.,
                                     device=0, sg_sampler="numpy", n_gpus=1, _return_solver=False, loss="frobenius",
-                                    x_entry_weights=None, y_entry_weights=None, als_nn_sweeps=0, als_cg_steps=0):
+                                    x_entry_weights=None, y_entry_weights=None, als_nn_sweeps=0, als_cg_steps=0,
+                                    x_background_weight=0.0, y_background_weight=0.0):
     """Factorise X ~ f(U V^T) and Y ~ f(V Z^T) with a shared V on an MI355X.
 
     Same contract as the reference function (pycmf/cmf.py:215-456): returns
@@ -82,6 +83,13 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     weights on one of its relations run n matrix-free conjugate-gradient steps from the rows they have instead of forming and
     factorising their k x k systems -- still a monotone descent, far cheaper per iteration; 6 is the documented choice
     (``HipALSSolver``).  Non-negative factors keep the route ``als_nn_sweeps`` names, unweighted sweeps the shared inverse.
+
+    ``x_background_weight`` / ``y_background_weight``: 0 | c0 > 0 (``solver='als'`` only) -- implicit feedback.  The relation's
+    entry weights must be a SciPy sparse W or ``'observed'`` with every stored weight >= c0; the cells outside that pattern then
+    count with weight c0 and target 0 instead of not at all: 1/2 sum_O w (t - a.b)^2 + 1/2 c0 sum_{not O} (a.b)^2, at the cost of
+    the stored entries alone (``HipALSSolver``; ``pycmf_amd.implicit_confidence`` makes targets and confidences from counts).
+    ``ValueError`` before any device is touched: a non-zero value with another solver, without entry weights for that relation or
+    with dense ones; a bool, a non-finite or a negative value; a stored weight below the background.
     """
     if n_components is None:
         n_components = max(X.shape[1], Y.shape[1])
@@ -91,6 +99,8 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     check_als_nn_sweeps(als_nn_sweeps, solver)
     check_als_cg_steps(als_cg_steps, solver, [nn for nn, upd in ((U_non_negative, update_U), (V_non_negative, update_V),
                                                                  (Z_non_negative, update_Z)) if upd])
+    x_background_weight = check_background_weight(x_background_weight, "x", solver, x_entry_weights)
+    y_background_weight = check_background_weight(y_background_weight, "y", solver, y_entry_weights)
 
     if update_U or update_V:
         X = check_array(X, accept_sparse=('csr', 'csc'), dtype=float)
@@ -138,7 +148,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                           "link arguments will be ignored")
         solver_object = HipALSSolver(U_non_negative=U_non_negative, V_non_negative=V_non_negative, Z_non_negative=Z_non_negative,
                                      x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, nn_sweeps=als_nn_sweeps, cg_steps=als_cg_steps,
-                                     **common)
+                                     x_background_weight=x_background_weight, y_background_weight=y_background_weight, **common)
         solver_object.check_weights(X, Y)
     else:
         raise ValueError("No such solver: %s" % solver)
@@ -316,9 +326,13 @@ class CMF(BaseEstimator, TransformerMixin):
                     sg_sample_ratio=self.sg_sample_ratio, device=self.device, sg_sampler=self.sg_sampler,
                     loss=self.loss, als_nn_sweeps=self.als_nn_sweeps, als_cg_steps=self.als_cg_steps)
 
-    def fit_transform(self, X, Y, U=None, V=None, Z=None, x_entry_weights=None, y_entry_weights=None):
+    def fit_transform(self, X, Y, U=None, V=None, Z=None, x_entry_weights=None, y_entry_weights=None, x_background_weight=0.0,
+                      y_background_weight=0.0):
         """``x_entry_weights`` / ``y_entry_weights``: per-entry weights of X / Y for this fit (``collective_matrix_factorization``);
-        ``reconstruction_err_`` is then sqrt(sum Wx (X - U V^T)^2) + sqrt(sum Wy (Y - V Z^T)^2)."""
+        ``reconstruction_err_`` is then sqrt(sum Wx (X - U V^T)^2) + sqrt(sum Wy (Y - V Z^T)^2).
+        ``x_background_weight`` / ``y_background_weight`` (``solver='als'``, sparse entry weights): the weight of the cells outside
+        the weights' pattern, for implicit feedback; ``reconstruction_err_`` is then sqrt(E_x) + sqrt(E_y) with
+        E = sum_O w (t - a.b)^2 + c0 sum_{not O} (a.b)^2."""
         X = check_array(X, accept_sparse=('csr', 'csc'), dtype=float)
         Y = check_array(Y, accept_sparse=('csr', 'csc'), dtype=float)
         if X.shape[1] != Y.shape[0]:
@@ -327,7 +341,8 @@ class CMF(BaseEstimator, TransformerMixin):
         U, V, Z, n_iter_, solver_object = collective_matrix_factorization(
             X=X, Y=Y, U=U, V=V, Z=Z, n_components=self.n_components,
             x_init=self.x_init, y_init=self.y_init, alpha=self.alpha, n_gpus=self.n_gpus,
-            _return_solver=True, x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, **self._kwargs())
+            _return_solver=True, x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights,
+            x_background_weight=x_background_weight, y_background_weight=y_background_weight, **self._kwargs())
         # unweighted sum of the two residual norms, evaluated on the device where the
         # data and the final factors still live (cmf.py:697-698)
         self.reconstruction_err_ = solver_object.reconstruction_error()
@@ -343,10 +358,11 @@ class CMF(BaseEstimator, TransformerMixin):
         self.fit_transform(X, Y, **params)
         return self
 
-    def transform(self, X, Y, x_entry_weights=None, y_entry_weights=None):
+    def transform(self, X, Y, x_entry_weights=None, y_entry_weights=None, x_background_weight=0.0, y_background_weight=0.0):
         """Re-fit U and/or Z with the learnt components V held fixed; pass ``None`` for
         the side that should be left alone (cmf.py:726-747).  ``x_entry_weights`` / ``y_entry_weights``: per-entry weights of
-        the given X / Y, as in ``fit_transform``."""
+        the given X / Y, as in ``fit_transform``; ``x_background_weight`` / ``y_background_weight`` likewise: with them this is
+        the fold-in of new users (rows of X) against the fixed V under the implicit-feedback model."""
         assert hasattr(self, "components")
         update_U = X is not None
         update_Z = Y is not None
@@ -357,7 +373,8 @@ class CMF(BaseEstimator, TransformerMixin):
             X=X, Y=Y, U=U, V=self.components, Z=Z, n_components=self.n_components,
             x_init="custom", y_init="custom", alpha=alpha,
             update_U=update_U, update_V=False, update_Z=update_Z, x_entry_weights=x_entry_weights,
-            y_entry_weights=y_entry_weights, **self._kwargs())
+            y_entry_weights=y_entry_weights, x_background_weight=x_background_weight, y_background_weight=y_background_weight,
+            **self._kwargs())
         return U, V, Z
 
     def top_n(self, relation="x", axis=0, rows=None, n=10, exclude=None, queries=None):

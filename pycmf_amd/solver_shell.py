@@ -129,6 +129,61 @@ def check_entry_weights(x_entry_weights, y_entry_weights, solver="mu", loss="fro
         raise ValueError("x_entry_weights / y_entry_weights run on one GPU: n_gpus must be 1, got %r (the sharded form is not built)" % (n_gpus,))
 
 
+def check_background_weight(value, name, solver="als", entry_weights="observed"):
+    """``x_background_weight`` / ``y_background_weight`` (``name`` 'x' | 'y'): a finite number >= 0, non-zero with solver='als' only
+    and only for a relation whose entry weights are a SciPy sparse W or 'observed' (``entry_weights``: what the call was given).
+    Returns the value as a float; no device is touched."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (numbers.Real, np.integer, np.floating)):
+        raise ValueError("%s_background_weight must be a finite number >= 0, got %r" % (name, value))
+    value = float(value)
+    if not np.isfinite(value) or value < 0:
+        raise ValueError("%s_background_weight must be a finite number >= 0, got %r" % (name, value))
+    if value == 0:
+        return 0.0
+    if solver != "als":
+        raise ValueError("%s_background_weight is the implicit-feedback model of solver='als': it must be 0 with solver=%r, got %r" % (name, solver, value))
+    if entry_weights is None:
+        raise ValueError("%s_background_weight=%r needs %s_entry_weights: the confidences of the stored entries (a SciPy sparse W, or "
+                         "'observed'); without them every cell already counts with weight 1" % (name, value, name))
+    import scipy.sparse as sp
+    if not (isinstance(entry_weights, str) or sp.issparse(entry_weights)):
+        raise ValueError("%s_background_weight=%r with dense %s_entry_weights: the background is the weight of the cells OUTSIDE a stored "
+                         "pattern, which a dense W does not have; pass a SciPy sparse W or 'observed'" % (name, value, name))
+    return value
+
+
+def check_background_floor(ew, value, name):
+    """Every stored weight of the resolved ``ew`` must be >= the background weight, compared as the device does, in float32."""
+    if not value or ew is None:
+        return
+    w = np.asarray(ew.w, dtype=np.float32)
+    if w.size and w.min() < np.float32(value):
+        raise ValueError("%s_entry_weights has a stored weight %r below %s_background_weight=%r: a stored entry must count at least as "
+                         "much as an unobserved cell" % (name, float(w.min()), name, value))
+
+
+def implicit_confidence(R, alpha=1.0, background=1.0):
+    """``(P, W)`` of the implicit-feedback model for a SciPy sparse matrix ``R`` of counts (clicks, plays, purchases): ``P`` is the
+    pattern of R with ones (the targets), ``W = background + alpha * R`` on the same pattern (the confidences).  Fit with
+    ``CMF(solver='als', ...).fit(P, Y, x_entry_weights=W, x_background_weight=background)``.  Negative or non-finite counts are a
+    ``ValueError``; stored zeros stay stored (target 1, confidence ``background``)."""
+    import scipy.sparse as sp
+    if not sp.issparse(R):
+        raise ValueError("implicit_confidence takes a SciPy sparse matrix of counts, got %s" % type(R).__name__)
+    for v, nm in ((alpha, "alpha"), (background, "background")):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (numbers.Real, np.integer, np.floating)) or not np.isfinite(v) or v < 0:
+            raise ValueError("implicit_confidence: %s must be a finite number >= 0, got %r" % (nm, v))
+    A = _canonical_csr(R)
+    counts = np.asarray(A.data, dtype=np.float64)
+    if counts.size and not np.isfinite(counts).all():
+        raise ValueError("implicit_confidence: the counts must be finite: found NaN or infinite values")
+    if counts.size and counts.min() < 0:
+        raise ValueError("implicit_confidence: the counts must be non-negative: found negative values")
+    P = sp.csr_matrix((np.ones(A.nnz), A.indices.copy(), A.indptr.copy()), shape=A.shape)
+    W = sp.csr_matrix((float(background) + float(alpha) * counts, A.indices.copy(), A.indptr.copy()), shape=A.shape)
+    return P, W
+
+
 def _as_f64(a):
     return a if (isinstance(a, np.ndarray) and a.dtype == np.float64) else np.asarray(a, dtype=np.float64)
 
@@ -544,29 +599,54 @@ class HipALSSolver(HipMUSolver):
     50.05 with 6 steps against 50.46 exact, 51.45 with 4, 55.3 with 3, 60.8 with 2, 144.7 with 1).  A non-negative factor keeps the route ``nn_sweeps`` names,
     a factor whose relations are all unweighted the one shared inverse; refused when every updated factor is non-negative.
 
+    ``x_background_weight=c0`` / ``y_background_weight`` (default 0): the implicit-feedback model (Hu, Koren, Volinsky).  The
+    relation must have sparse entry weights W (or ``'observed'``) with every stored weight >= c0; the cells outside W's pattern
+    then count with weight c0 and target 0,
+
+        1/2 sum_O w (t - a.b)^2 + 1/2 c0 sum_{not O} (a.b)^2,
+
+    at the cost of the pattern alone: the rows' systems take the excess weights w - c0 and c0 B^T B (``cmf_set_background_weight``).
+    All three row solves honour it.  ``pycmf_amd.implicit_confidence(R, alpha)`` makes the targets and confidences from counts.  The
+    error of such a relation is sqrt(sum_O w e^2 + c0 sum_{not O} (a.b)^2) (``cmf_als_residual_sq``).  On patterns with a few very
+    long columns keep the exact route for V (``cg_steps=0``), as without a background.
+
     Like MU it ignores alpha and the links.  The error metric is the one of a weighted MU fit, sqrt(sum wx e^2) +
     sqrt(sum wy e^2); the loop stays on the host (``cmf_run`` knows the MU and Newton steps only)."""
 
     _densify_unweighted = False
 
-    def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, cg_steps=0, **kwargs):
+    def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, cg_steps=0, x_background_weight=0.0,
+                 y_background_weight=0.0, **kwargs):
         check_als_nn_sweeps(nn_sweeps)
         check_als_cg_steps(cg_steps)
+        self.x_background_weight = check_background_weight(x_background_weight, "x", "als", x_entry_weights)
+        self.y_background_weight = check_background_weight(y_background_weight, "y", "als", y_entry_weights)
         super().__init__(*args, loss="frobenius", x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, **kwargs)
         check_als(self.l1_reg, self.l2_reg)
         self.nn_sweeps = int(nn_sweeps)
         self.cg_steps = int(cg_steps)
 
+    def _weights_key(self):
+        return super()._weights_key() + (self.x_background_weight, self.y_background_weight)
+
     def _resolve_weights(self, X, Y):
         key = (id(X), id(Y))
         if getattr(self, "_als_resolved_for", None) != key:
             self._als_resolved = tuple(_weights_as_pattern(ew) for ew in super()._resolve_weights(X, Y))
+            check_background_floor(self._als_resolved[0], self.x_background_weight, "x")
+            check_background_floor(self._als_resolved[1], self.y_background_weight, "y")
             self._als_resolved_for = key
         return self._als_resolved
 
     def _bind_dims(self, X, Y, m, d, p, k):
         check_als(n_components=k)
-        return super()._bind_dims(X, Y, m, d, p, k)
+        fresh = self._bound != (id(X), id(Y), m, d, p, k) + self._weights_key()
+        ctx = super()._bind_dims(X, Y, m, d, p, k)
+        if fresh:   # (binding the weights reset the background of the relation)
+            for which, c0 in ((0, self.x_background_weight), (1, self.y_background_weight)):
+                if c0:
+                    ctx.set_background_weight(which, c0)
+        return ctx
 
     def _device_step(self, l1_reg, l2_reg, alpha):
         check_als(l1_reg, l2_reg)
@@ -581,7 +661,11 @@ class HipALSSolver(HipMUSolver):
         X, Y = self._XY
         wx, wy = self.x_entry_weights is not None, self.y_entry_weights is not None
         ex2 = ey2 = 0.0
-        if wx or wy:
+        if self.x_background_weight or self.y_background_weight:
+            # E = sum_O w (t - s)^2 + c0 (<A^T A, B^T B> - sum_O s^2): the error over every cell; a side without a background
+            # gets the bits of the weighted residual from the same call
+            ex2, ey2 = self._ctx.als_residual_sq(wx and X is not None, wy and Y is not None)
+        elif wx or wy:
             ex2, ey2 = self._ctx.weighted_residual_sq(wx and X is not None, wy and Y is not None)
         if not (wx and wy):   # a relation without weights: every cell with weight 1 -- the plain residual, whatever its layout
             fx2, fy2 = self._ctx.residual_sq("linear", "linear")
