@@ -1,14 +1,30 @@
 // cmf_als.hip.h -- ALS (alternating least squares) on the quadratic objective over an observed pattern
 //   1/2 sum_{Ox} wx_ij (x_ij - u_i . v_j)^2 + 1/2 sum_{Oy} wy_jc (y_jc - v_j . z_c)^2 + l2 / 2 (|U|^2 + |V|^2 + |Z|^2),   l2 > 0.
-// Every row f_i of the factor being swept is the exact minimiser of its own k x k system
+// Every row f_i of the factor being swept has its own k x k system
 //   (sum_{c in O_i} w_ic b_c b_c^T + S + l2 I) f_i = sum_{c in O_i} w_ic t_ic b_c + N_i
 // where an OBSERVED relation (weights bound as CSR, cmf_set_weighted_csr) contributes the sums over its stored entries and a FULL
-// relation (no weights: every cell counts with weight 1) the shared Gram S = B^T B and the row N_i of T B.
+// relation (no weights: every cell counts with weight 1) the shared Gram S = B^T B and the row N_i of T B.  Under a background
+// weight c0 (cmf_als_bg.hip.h, implicit feedback) an observed relation counts the cells outside its pattern too: the kernels read
+// the excess weights w - c0 where they read w, and S = sum_sides coef Gram(B_side) (als_shared_terms).  What depended on "a full
+// side exists" depends on "S is set".  The route of a sweep (als_route; sweeps / cg_steps: 0 where the entry point has no count):
+//   route         taken when                                           what it does
+//   shared exact  no observed relation; signed, or sweeps = 0          ONE matrix G + l2 I for all rows, inverted once in float64
+//                                                                      (shared_inverse64), one product, projected if non-negative
+//   shared HALS   no observed relation; non-negative, sweeps > 0       hals_sweep (cmf_hals.hip.h) `sweeps` times on the one Gram
+//   rows exact    observed; non-negative with sweeps = 0, or signed    the finished systems through safe_solve_rows (cmf_newton.hip.h):
+//                 with cg_steps = 0                                    Hessians declared positive semi-definite, threshold l2 / 16
+//                                                                      (lambda_min(H_i) >= l2: the spectral clamp never acts), no
+//                                                                      float64 refinement; projected if non-negative
+//   rows NNLS     observed; non-negative, sweeps > 0                   the finished systems to als_nnls_kernel (cmf_als_nnls.hip.h):
+//                                                                      cyclic coordinate descent from the current rows, in place
+//   rows CG       observed; signed, cg_steps > 0                       no systems: als_cg_kernel (cmf_als_cg.hip.h) runs matrix-free
+//                                                                      CG steps per row from the current rows, in place; the host
+//                                                                      sorts the rows into LDS capacity classes by length
 //
-// als_normal_kernel<KP>: one 512-thread workgroup per PIECE of a row (at most `als_piece` stored entries, a multiple of 32) of a CSR
-// image (indptr, idx, pv = w t, wv = w).  The gathered rows b_e are staged 32 at a time through registers into a double-buffered
-// LDS tile, scaled by sqrt(w_e); while they are in registers the owning lanes add p_e b_e to the gradient part g.  H is a rank-32
-// update per step on v_mfma_f32_32x32x2_f32, both operands read from the ONE staged image:
+// The finished systems (als_chunks).  als_normal_kernel<KP>: one 512-thread workgroup per PIECE of a row (at most `als_piece` stored
+// entries, a multiple of 32) of a CSR image (indptr, idx, pv = w t, wv = w).  The gathered rows b_e are staged 32 at a time through
+// registers into a double-buffered LDS tile, scaled by sqrt(w_e); while they are in registers the owning lanes add p_e b_e to the
+// gradient part g.  H is a rank-32 update per step on v_mfma_f32_32x32x2_f32, both operands read from the ONE staged image:
 //     H = sum_e (sqrt(w_e) b_e)(sqrt(w_e) b_e)^T,     g = sum_e p_e b_e.
 // The geometry is that of row_hess_kernel in its single-image symmetric form (cmf_rowhess.hip.h, SYM = 3), restated here, not
 // shared: 16 lanes per gathered row, row-major 32 x KP tiles, and at k_pad = 256 only the 36 blocks (32 x 32) on or above the block
@@ -22,19 +38,6 @@
 // piece order, mirrors the upper triangle (so H_i is symmetric to the bit), adds S, l2 on the first k diagonal entries and 1 on the
 // padding diagonal, and N_i to g.  No atomics anywhere: a repeated call from the same state is bit-identical.  Padding columns of
 // the factors are zero, so the padding of H_i and g_i is exact zeros (unit diagonal apart).
-// The solves go through safe_solve_rows (cmf_newton.hip.h) with the Hessians declared positive semi-definite, the threshold l2 / 16
-// (lambda_min(H_i) >= l2: the spectral clamp never acts) and the float64 refinement off.
-// A sweep without an observed side has ONE matrix G + l2 I for all rows: inverted once in float64 (shared_inverse64) and applied
-// with one product.
-// Non-negative rows (cmf_als_nnls_step): the finished systems of a chunk go to als_nnls_kernel (cmf_als_nnls.hip.h) instead of the
-// Cholesky solves -- cyclic coordinate descent from the current rows, `sweeps` passes; a sweep whose relations are all full runs
-// hals_sweep (cmf_hals.hip.h) that many times on the one Gram.
-// Signed rows by conjugate gradients (cmf_als_cg_step): a signed swept factor with an observed relation skips the normal equations
-// and the Cholesky solves altogether -- als_cg_kernel (cmf_als_cg.hip.h) runs `cg_steps` matrix-free CG steps per row from the
-// current rows, in place.  The host sorts the rows into a few LDS capacity classes by their length (als_cg_rows).
-// Background weights (cmf_als_bg.hip.h, implicit feedback): an observed relation may count the cells outside its pattern with a
-// weight c0 -- the kernels above then read the excess weights w - c0 where they read w, and S becomes sum_sides coef Gram(B_side)
-// (als_shared_terms); everything that depended on "a full side exists" depends on "S is set".
 #pragma once
 #include "cmf_kernels.hip.h"
 #include "cmf_als_nnls.hip.h"
@@ -294,9 +297,50 @@ static int als_rels(int f, AlsRel out[2]) {
     out[1] = AlsRel{1, 0, CMF_Z, false};
     return 2;
 }
+
+// The sweep of factor f as every route reads it: its relations, which of them are observed (CSR weights bound), and the observed
+// ones in order with their CSR image and gathered factor.  Built on the host: no launch, no device access.
+struct AlsSweep {
+    int f, nrel, nobs = 0;
+    AlsRel rel[2];
+    bool observed[2];                                       // of rel[s]
+    struct { const WCsrDev *M; const float *B; } obs[2];   // [nobs]
+};
+static AlsSweep als_sweep(const cmf_ctx *c, int f) {
+    AlsSweep sw;
+    sw.f = f;
+    sw.nrel = als_rels(f, sw.rel);
+    for (int s = 0; s < sw.nrel; ++s) {
+        const AlsRel &r = sw.rel[s];
+        sw.observed[s] = c->wm_kind[r.which] == WM_CSR;
+        if (sw.observed[s]) sw.obs[sw.nobs++] = {&c->wm_sp[r.which][r.t], c->F[r.fb]};
+    }
+    return sw;
+}
+static bool als_observed(const AlsSweep &sw) { return sw.nobs > 0; }
+
 #define CMF_ALS_BG_HOST
 #include "cmf_als_bg.hip.h"   // background weights: als_shared_terms, als_side_weights and the entry points of its own
 static int64_t als_piece_len(const cmf_ctx *c) { return c->opt_als_piece > 0 ? rup(c->opt_als_piece, 32) : (int64_t)ALS_PIECE_DEFAULT; }
+
+enum AlsRoute { ALS_SHARED_EXACT, ALS_SHARED_HALS, ALS_ROWS_EXACT, ALS_ROWS_NNLS, ALS_ROWS_CG };
+// the route of one sweep (file header); nn: the factor is non-negative, sweeps / cg_steps: 0 where the entry point has no such count
+static AlsRoute als_route(bool observed, bool nn, int sweeps, int cg_steps) {
+    if (nn && sweeps) return observed ? ALS_ROWS_NNLS : ALS_SHARED_HALS;
+    if (!observed) return ALS_SHARED_EXACT;
+    return !nn && cg_steps ? ALS_ROWS_CG : ALS_ROWS_EXACT;
+}
+
+// The launch ladder of the row kernels, templates on k_pad: LAUNCH is a statement that names the instance of cmfk::KERNEL as `kern`.
+#define ALS_LAUNCH_KP(c, KERNEL, WHAT, LAUNCH)                                                                           \
+    switch ((c)->kp) {                                                                                                   \
+    case 32: { auto kern = cmfk::KERNEL<32>; LAUNCH; break; }                                                            \
+    case 64: { auto kern = cmfk::KERNEL<64>; LAUNCH; break; }                                                            \
+    case 128: { auto kern = cmfk::KERNEL<128>; LAUNCH; break; }                                                          \
+    case 256: { auto kern = cmfk::KERNEL<256>; LAUNCH; break; }                                                          \
+    default: return fail(CMF_EUNSUPPORTED, WHAT " built for n_components <= 256 (k_pad = %d)", (c)->kp);                 \
+    }                                                                                                                    \
+    HIPCHK(hipGetLastError())
 
 static int als_relation_ok(cmf_ctx *c, const char *what, int which) {
     if (c->wm_kind[which] == WM_DENSE)
@@ -307,30 +351,31 @@ static int als_relation_ok(cmf_ctx *c, const char *what, int which) {
     return CMF_OK;
 }
 
+// indptr[r0 .. r1] of every observed side back to the host (the pattern lives on the device only): the row lengths behind the
+// piece plan and behind the capacity classes of the CG rows
+static int als_fetch_indptr(cmf_ctx *c, const AlsSweep &sw, int64_t r0, int64_t r1, std::vector<int64_t> ip[2]) {
+    for (int s = 0; s < sw.nobs; ++s) {
+        ip[s].assign((size_t)(r1 - r0 + 1), 0);
+        HIPCHK(hipMemcpyAsync(ip[s].data(), sw.obs[s].M->indptr + r0, ip[s].size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return CMF_OK;
+}
+
 struct AlsPlan { // the pieces of rows [r0, r1) of one sweep, host side
     std::vector<cmfk::AlsPiece> pieces;
     std::vector<int64_t> first;   // [r1 - r0 + 1]
-    int64_t nnz = 0;
 };
-// indptr of an observed side back to the host (the pattern lives on the device only)
-static int als_fetch_indptr(cmf_ctx *c, const WCsrDev &M, int64_t r0, int64_t r1, std::vector<int64_t> &ip) {
-    ip.assign((size_t)(r1 - r0 + 1), 0);
-    HIPCHK(hipMemcpyAsync(ip.data(), M.indptr + r0, ip.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return CMF_OK;
-}
-static int als_plan(cmf_ctx *c, const AlsRel *obs, int nobs, int64_t r0, int64_t r1, AlsPlan &pl) {
+static int als_plan(cmf_ctx *c, const AlsSweep &sw, int64_t r0, int64_t r1, AlsPlan &pl) {
     const int64_t L = als_piece_len(c);
     std::vector<int64_t> ip[2];
-    for (int s = 0; s < nobs; ++s) CHK(als_fetch_indptr(c, c->wm_sp[obs[s].which][obs[s].t], r0, r1, ip[s]));
+    CHK(als_fetch_indptr(c, sw, r0, r1, ip));
     pl.pieces.clear();
     pl.first.assign((size_t)(r1 - r0 + 1), 0);
-    pl.nnz = 0;
     for (int64_t r = 0; r < r1 - r0; ++r) {
         pl.first[(size_t)r] = (int64_t)pl.pieces.size();
-        for (int s = 0; s < nobs; ++s) {
+        for (int s = 0; s < sw.nobs; ++s) {
             const int64_t b = ip[s][(size_t)r], e = ip[s][(size_t)r + 1];
-            pl.nnz += e - b;
             for (int64_t q = b; q < e; q += L) pl.pieces.push_back(cmfk::AlsPiece{q, (int32_t)std::min(L, e - q), s});
         }
     }
@@ -342,14 +387,7 @@ static int als_launch_normal(cmf_ctx *c, const cmfk::AlsArgs &a, int64_t npieces
     if (npieces <= 0) return CMF_OK;
     Timed tm(c, CMF_K_ROWHESS, 2.0 * (double)nnz * c->k * c->k);
     const dim3 grid((unsigned)npieces), block(512);
-    switch (c->kp) {
-    case 32: hipLaunchKernelGGL((cmfk::als_normal_kernel<32>), grid, block, 0, c->stream, a); break;
-    case 64: hipLaunchKernelGGL((cmfk::als_normal_kernel<64>), grid, block, 0, c->stream, a); break;
-    case 128: hipLaunchKernelGGL((cmfk::als_normal_kernel<128>), grid, block, 0, c->stream, a); break;
-    case 256: hipLaunchKernelGGL((cmfk::als_normal_kernel<256>), grid, block, 0, c->stream, a); break;
-    default: return fail(CMF_EUNSUPPORTED, "ALS normal equations are built for n_components <= 256 (k_pad = %d)", c->kp);
-    }
-    HIPCHK(hipGetLastError());
+    ALS_LAUNCH_KP(c, als_normal_kernel, "ALS normal equations are", hipLaunchKernelGGL(kern, grid, block, 0, c->stream, a));
     return CMF_OK;
 }
 
@@ -359,42 +397,32 @@ static int als_nnls_launch(cmf_ctx *c, const float *H, const float *g, float *F,
     a.H = H; a.g = g; a.F = F; a.first = first; a.nrows = nrows; a.k = c->k; a.sweeps = sweeps;
     Timed tm(c, CMF_K_HALS, 2.0 * (double)nrows * c->k * c->k * sweeps);
     const dim3 grid((unsigned)((nrows + cmfk::NNLS_WAVES - 1) / cmfk::NNLS_WAVES)), block(64 * cmfk::NNLS_WAVES);
-    switch (c->kp) {
-    case 32: hipLaunchKernelGGL((cmfk::als_nnls_kernel<32>), grid, block, 0, c->stream, a); break;
-    case 64: hipLaunchKernelGGL((cmfk::als_nnls_kernel<64>), grid, block, 0, c->stream, a); break;
-    case 128: hipLaunchKernelGGL((cmfk::als_nnls_kernel<128>), grid, block, 0, c->stream, a); break;
-    case 256: hipLaunchKernelGGL((cmfk::als_nnls_kernel<256>), grid, block, 0, c->stream, a); break;
-    default: return fail(CMF_EUNSUPPORTED, "the non-negative row solve is built for n_components <= 256 (k_pad = %d)", c->kp);
-    }
-    HIPCHK(hipGetLastError());
+    ALS_LAUNCH_KP(c, als_nnls_kernel, "the non-negative row solve is", hipLaunchKernelGGL(kern, grid, block, 0, c->stream, a));
     return CMF_OK;
 }
 
-// Rows [r_begin, r_end) of the sweep of factor f in per-row form: normal equations chunk by chunk, then (solve) the Cholesky
-// solves into c->als_sol -- or, nnls_sweeps > 0, that many coordinate-descent sweeps of the chunk's rows of F, in place -- or
-// (host_H / host_g, one chunk) the finished systems back to the host.
-static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end, bool solve, float *host_H, float *host_g, int nnls_sweeps = 0) {
+// The finished systems of rows [row0, row0 + nr) as als_chunks hands them on: H [nr][k_pad][k_pad] (c->als_h), g [nr][k_pad] (those
+// rows of c->als_g), and the piece index of those rows (no pieces: a row without information), null where S gives every row a system.
+struct AlsChunk { int64_t row0, nr; float *H; const float *g; const int64_t *no_info; };
+
+// Rows [r_begin, r_end) of the sweep in per-row form, chunk by chunk: als_normal_kernel over the chunk's pieces, als_finish_kernel,
+// then use(chunk).  A chunk holds at most `cap` rows and (but for a single row) as many pieces.
+template <class Use>
+static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin, int64_t r_end, int64_t cap, Use use) {
     using namespace cmfk;
-    AlsRel rel[2], obs[2];
-    const int nrel = als_rels(f, rel);
-    int nobs = 0;
-    for (int s = 0; s < nrel; ++s)
-        if (c->wm_kind[rel[s].which] == WM_CSR) obs[nobs++] = rel[s];
     const int kp = c->kp;
-    const int64_t kk = (int64_t)kp * kp, rows_pad = c->frows_pad[f];
+    const int64_t kk = (int64_t)kp * kp, rows_pad = c->frows_pad[sw.f];
     // the full relation: its Gram into every row's matrix, its product into the right-hand sides; a background: c0 times the Gram
     const float *S = nullptr, *N = nullptr;
-    CHK(als_shared_terms(c, rel, nrel, &S, &N));
+    CHK(als_shared_terms(c, sw, &S, &N));
     AlsPlan pl;
-    CHK(als_plan(c, obs, nobs, r_begin, r_end, pl));
+    CHK(als_plan(c, sw, r_begin, r_end, pl));
     const int64_t nrows = r_end - r_begin;
-    // chunks: at most hessian_chunk_rows rows and (but for a single row) as many pieces
-    const int64_t cap = solve ? hessian_chunk_rows(c, rows_pad) : std::max<int64_t>(1, nrows);
     int64_t max_rows = 0, max_pieces = 0;
     std::vector<int64_t> cuts{0};
     for (int64_t r = 0; r < nrows;) {
         int64_t e = r;
-        while (e < nrows && e - r < cap && (e == r || !solve || pl.first[(size_t)e + 1] - pl.first[(size_t)r] <= cap)) ++e;
+        while (e < nrows && e - r < cap && (e == r || pl.first[(size_t)e + 1] - pl.first[(size_t)r] <= cap)) ++e;
         max_rows = std::max(max_rows, e - r);
         max_pieces = std::max(max_pieces, pl.first[(size_t)e] - pl.first[(size_t)r]);
         cuts.push_back(e);
@@ -403,7 +431,6 @@ static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end
     CHK(kl_ensure(c, c->als_h, (size_t)std::max<int64_t>(1, max_rows) * kk * sizeof(float)));
     CHK(kl_ensure(c, c->als_part, (size_t)std::max<int64_t>(1, max_pieces) * (kk + kp) * sizeof(float)));
     CHK(kl_ensure(c, c->als_g, (size_t)rows_pad * kp * sizeof(float)));
-    if (!nnls_sweeps) CHK(kl_ensure(c, c->als_sol, (size_t)rows_pad * kp * sizeof(float)));
     const size_t pbytes = std::max<size_t>(16, pl.pieces.size() * sizeof(AlsPiece)), fbytes = pl.first.size() * sizeof(int64_t);
     CHK(kl_ensure(c, c->als_desc, pbytes + fbytes));
     AlsPiece *dpieces = (AlsPiece *)c->als_desc.p;
@@ -414,22 +441,17 @@ static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end
 
     AlsArgs a;
     memset(&a, 0, sizeof a);
-    for (int s = 0; s < nobs; ++s) {
-        const WCsrDev &M = c->wm_sp[obs[s].which][obs[s].t];
-        AlsSide sd{M.idx, M.pv, als_side_weights(M), c->F[obs[s].fb]};
-        if (s == 0) a.s0 = sd; else a.s1 = sd;
+    for (int s = 0; s < sw.nobs; ++s) {
+        const WCsrDev &M = *sw.obs[s].M;
+        (s == 0 ? a.s0 : a.s1) = AlsSide{M.idx, M.pv, als_side_weights(M), sw.obs[s].B};
     }
-    float *Hc = (float *)c->als_h.p, *Hp = (float *)c->als_part.p;
-    float *grad = (float *)c->als_g.p, *sol = (float *)c->als_sol.p;   // (sol: null and unused under nnls_sweeps)
+    float *Hc = (float *)c->als_h.p, *Hp = (float *)c->als_part.p, *grad = (float *)c->als_g.p;
     a.Hp = Hp;
-    // the threshold of the plain Cholesky route, well below l2 <= lambda_min(H_i): its test (a Cholesky of H_i - pert I whose pivots
-    // must exceed 4e-6 max H_jj) passes unless cond(H_i) is above ~2e5, where a float32 factorisation has nothing left to give
-    const double pert = l2 / 16.0;
+    a.gp = Hp + std::max<int64_t>(1, max_pieces) * kk;
     for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
         const int64_t c0 = cuts[ci], c1 = cuts[ci + 1], nr = c1 - c0, row0 = r_begin + c0;
         const int64_t pbase = pl.first[(size_t)c0], np = pl.first[(size_t)c1] - pbase;
         a.pieces = dpieces + pbase;
-        a.gp = Hp + std::max<int64_t>(1, max_pieces) * kk;
         int64_t nnz = 0;
         for (int64_t p = pbase; p < pbase + np; ++p) nnz += pl.pieces[(size_t)p].len;
         CHK(als_launch_normal(c, a, np, nnz));
@@ -439,57 +461,70 @@ static int als_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end
                                pbase, S, N ? N + row0 * kp : nullptr, (float)l2, c->k, kp, Hc, grad + row0 * kp);
             HIPCHK(hipGetLastError());
         }
-        if (solve && nnls_sweeps) {
-            // the gathered factors are the other ones: the chunks to come do not read the rows written here
-            CHK(als_nnls_launch(c, Hc, grad + row0 * kp, c->F[f] + row0 * kp, S ? nullptr : dfirst + c0, nr, nnls_sweeps));
-        } else if (solve) {
-            // the plain Cholesky route of the per-row Newton sweeps; what it reads of the Newton step's state is put back
-            const bool save_psd = c->hess_psd;
-            const int64_t save_r1 = c->rank1_rows, save_eig = c->eig_clamp_rows;
-            std::vector<int> save_bad;
-            save_bad.swap(c->bad_host);
-            c->hess_psd = true;
-            const int rc = safe_solve_rows(c, Hc, grad + row0 * kp, sol + row0 * kp, nr, c->k, kp, pert);
-            c->hess_psd = save_psd;
-            c->rank1_rows = save_r1; c->eig_clamp_rows = save_eig;
-            c->bad_host.swap(save_bad);
-            CHK(rc);
-        } else {
-            if (host_H) HIPCHK(hipMemcpyAsync(host_H, Hc, (size_t)nr * kk * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            if (host_g) HIPCHK(hipMemcpyAsync(host_g, grad + row0 * kp, (size_t)nr * kp * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-        }
+        CHK(use(AlsChunk{row0, nr, Hc, grad + row0 * kp, S ? nullptr : dfirst + c0}));
     }
     return CMF_OK;
+}
+
+// What safe_solve_rows (cmf_newton.hip.h) reads and writes of the Newton step's state: put back when the scope ends.
+struct AlsNewtonStateGuard {
+    cmf_ctx *const c;
+    const bool psd;
+    const int64_t rank1, eig;
+    std::vector<int> bad;
+    explicit AlsNewtonStateGuard(cmf_ctx *ctx) : c(ctx), psd(ctx->hess_psd), rank1(ctx->rank1_rows), eig(ctx->eig_clamp_rows) { bad.swap(c->bad_host); }
+    ~AlsNewtonStateGuard() { c->hess_psd = psd; c->rank1_rows = rank1; c->eig_clamp_rows = eig; c->bad_host.swap(bad); }
+};
+
+// rows exact: the Cholesky solves of every chunk into c->als_sol -- the plain route of the per-row Newton sweeps
+static int als_rows_solve(cmf_ctx *c, const AlsSweep &sw, double l2) {
+    CHK(kl_ensure(c, c->als_sol, (size_t)c->frows_pad[sw.f] * c->kp * sizeof(float)));
+    // the threshold of that route, well below l2 <= lambda_min(H_i): its test (a Cholesky of H_i - pert I whose pivots must exceed
+    // 4e-6 max H_jj) passes unless cond(H_i) is above ~2e5, where a float32 factorisation has nothing left to give
+    const double pert = l2 / 16.0;
+    return als_chunks(c, sw, l2, 0, c->frows[sw.f], hessian_chunk_rows(c, c->frows_pad[sw.f]), [&](const AlsChunk &ch) -> int {
+        AlsNewtonStateGuard keep(c);
+        c->hess_psd = true;
+        return safe_solve_rows(c, ch.H, ch.g, (float *)c->als_sol.p + ch.row0 * c->kp, ch.nr, c->k, c->kp, pert);
+    });
+}
+
+// rows NNLS: `sweeps` coordinate-descent sweeps of every chunk's rows of F, in place (the gathered factors are the other ones: the
+// chunks to come do not read the rows written here)
+static int als_rows_nnls(cmf_ctx *c, const AlsSweep &sw, double l2, int sweeps) {
+    return als_chunks(c, sw, l2, 0, c->frows[sw.f], hessian_chunk_rows(c, c->frows_pad[sw.f]), [&](const AlsChunk &ch) -> int {
+        return als_nnls_launch(c, ch.H, ch.g, c->F[sw.f] + ch.row0 * c->kp, ch.no_info, ch.nr, sweeps);
+    });
+}
+
+// cmf_als_normal: the finished systems of rows [r_begin, r_end), one chunk, back to the host
+static int als_rows_to_host(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin, int64_t r_end, float *host_H, float *host_g) {
+    return als_chunks(c, sw, l2, r_begin, r_end, INT64_MAX, [&](const AlsChunk &ch) -> int {
+        if (host_H) HIPCHK(hipMemcpyAsync(host_H, ch.H, (size_t)ch.nr * c->kp * c->kp * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (host_g) HIPCHK(hipMemcpyAsync(host_g, ch.g, (size_t)ch.nr * c->kp * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return CMF_OK;
+    });
 }
 
 static int als_apply(cmf_ctx *c, int f, const float *sol, bool nn) {
     return launch_ew(c, cmfk::als_apply_kernel, c->frows[f] * c->kp, c->F[f], sol, c->frows[f], c->k, c->kp, nn ? 1 : 0);
 }
 
-static bool als_observed(const cmf_ctx *c, int f) {
-    AlsRel rel[2];
-    const int n = als_rels(f, rel);
-    for (int s = 0; s < n; ++s)
-        if (c->wm_kind[rel[s].which] == WM_CSR) return true;
-    return false;
-}
-
-// a sweep whose relations are all full: F <- clamp(N (G + l2 I)^-1), the inverse formed once in float64
-static int als_sweep_shared(cmf_ctx *c, int f, double l2, bool nn) {
-    AlsRel rel[2];
-    const int nrel = als_rels(f, rel);
+// shared exact: F <- clamp(N (G + l2 I)^-1), the inverse formed once in float64
+static int als_sweep_shared(cmf_ctx *c, const AlsSweep &sw, double l2, bool nn) {
     CHK(ensure_shared64(c));
-    for (int s = 0; s < nrel; ++s) {
-        CHK(gram64(c, c->F[rel[s].fb], c->frows_pad[rel[s].fb], (double *)(s == 0 ? c->g64a.p : c->g64b.p), nullptr));
-        CHK(data_times(c, rel[s].which, rel[s].data_trans, c->F[rel[s].fb], c->num, s > 0));
+    for (int s = 0; s < sw.nrel; ++s) {
+        const AlsRel &r = sw.rel[s];
+        CHK(gram64(c, c->F[r.fb], c->frows_pad[r.fb], (double *)(s == 0 ? c->g64a.p : c->g64b.p), nullptr));
+        CHK(data_times(c, r.which, r.data_trans, c->F[r.fb], c->num, s > 0));
     }
-    CHK(launch_hess64(c, (const double *)c->g64a.p, 1.0, nrel > 1 ? (const double *)c->g64b.p : nullptr, 1.0, l2));
+    CHK(launch_hess64(c, (const double *)c->g64a.p, 1.0, sw.nrel > 1 ? (const double *)c->g64b.p : nullptr, 1.0, l2));
     const int rc = shared_inverse64(c, (const double *)c->h64.p, c->k, 0.5 * l2, true);
     if (rc == CMF_EUNSUPPORTED) return fail(CMF_EHIP, "cmf_als_step: the float64 inverse of G + l2 I failed (non-finite factors?)");
     CHK(rc);
-    CHK(gemm(c, MODE_NN, c->num, c->kp, c->Hinv, c->kp, c->den, c->frows_pad[f], c->kp, c->kp));
-    return als_apply(c, f, c->den, nn);
+    CHK(gemm(c, MODE_NN, c->num, c->kp, c->Hinv, c->kp, c->den, c->frows_pad[sw.f], c->kp, c->kp));
+    return als_apply(c, sw.f, c->den, nn);
 }
 
 static int als_check(cmf_ctx *c, const char *what, double l2, int mask) {
@@ -501,7 +536,7 @@ static int als_check(cmf_ctx *c, const char *what, double l2, int mask) {
     return CMF_OK;
 }
 
-// a non-negative sweep whose relations are all full: N and G as cmf_hals_step forms them, `sweeps` passes of hals_sweep
+// shared HALS: N and G as cmf_hals_step forms them, `sweeps` passes of hals_sweep
 static int als_nnls_sweep_shared(cmf_ctx *c, int f, double l2, int sweeps) {
     const float *N = c->num, *G = c->G2;
     if (f == CMF_V) {
@@ -529,45 +564,27 @@ static int als_cg_launch(cmf_ctx *c, const cmfk::AlsCgArgs &a, int64_t nrows) {
     if (nrows <= 0) return CMF_OK;
     const size_t lds = 4 * (size_t)cmfk::als_cg_fixed_floats(c->kp) + (size_t)a.cap * cmfk::als_cg_entry_bytes(c->kp);
     const dim3 grid((unsigned)nrows), block(256);
-#define ALS_CG_CASE(KP)                                                                                   \
-    case KP:                                                                                              \
-        CHK(allow_big_lds(c, (const void *)cmfk::als_cg_kernel<KP>, ALS_CG_LDS_TOTAL));                   \
-        hipLaunchKernelGGL((cmfk::als_cg_kernel<KP>), grid, block, lds, c->stream, a);                    \
-        break;
-    switch (c->kp) {
-    ALS_CG_CASE(32)
-    ALS_CG_CASE(64)
-    ALS_CG_CASE(128)
-    ALS_CG_CASE(256)
-    default: return fail(CMF_EUNSUPPORTED, "the conjugate-gradient row solve is built for n_components <= 256 (k_pad = %d)", c->kp);
-    }
-#undef ALS_CG_CASE
-    HIPCHK(hipGetLastError());
+    ALS_LAUNCH_KP(c, als_cg_kernel, "the conjugate-gradient row solve is",
+                  CHK(allow_big_lds(c, (const void *)kern, ALS_CG_LDS_TOTAL)); hipLaunchKernelGGL(kern, grid, block, lds, c->stream, a));
     return CMF_OK;
 }
 
-// Rows [r_begin, r_end) of the sweep of factor f (which has an observed relation) by `steps` CG steps from the rows of c->F[f];
+// rows CG: rows [r_begin, r_end) of the sweep (which has an observed relation) by `steps` CG steps from the rows of c->F[f];
 // row r goes to Fout + (r - out_row0) * k_pad (in place: Fout = c->F[f], out_row0 = 0 -- the gathered factors are the other ones).
 // The rows are sorted into capacity classes by their stored entries: capacity / 8, / 4, / 2 and the whole capacity keep the
 // gathered rows in LDS (shorter rows: more workgroups per CU), longer rows stream; one launch per class.
-static int als_cg_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_end, int steps, float *Fout, int64_t out_row0) {
+static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin, int64_t r_end, int steps, float *Fout, int64_t out_row0) {
     using namespace cmfk;
-    AlsRel rel[2], obs[2];
-    const int nrel = als_rels(f, rel);
-    int nobs = 0;
-    for (int s = 0; s < nrel; ++s)
-        if (c->wm_kind[rel[s].which] == WM_CSR) obs[nobs++] = rel[s];
     const int kp = c->kp;
     const int64_t nrows = r_end - r_begin;
     AlsCgArgs a;
     memset(&a, 0, sizeof a);
-    CHK(als_shared_terms(c, rel, nrel, &a.S, &a.N)); // as als_rows
+    CHK(als_shared_terms(c, sw, &a.S, &a.N)); // as als_chunks
     std::vector<int64_t> ip[2];
-    for (int s = 0; s < nobs; ++s) {
-        const WCsrDev &M = c->wm_sp[obs[s].which][obs[s].t];
-        CHK(als_fetch_indptr(c, M, r_begin, r_end, ip[s]));
-        AlsCgSide sd{M.indptr, M.idx, M.pv, als_side_weights(M), c->F[obs[s].fb]};
-        if (s == 0) a.s0 = sd; else a.s1 = sd;
+    CHK(als_fetch_indptr(c, sw, r_begin, r_end, ip));
+    for (int s = 0; s < sw.nobs; ++s) {
+        const WCsrDev &M = *sw.obs[s].M;
+        (s == 0 ? a.s0 : a.s1) = AlsCgSide{M.indptr, M.idx, M.pv, als_side_weights(M), sw.obs[s].B};
     }
     const int64_t cap_max = als_cg_lds_bytes(c) / als_cg_entry_bytes(kp);
     int64_t caps[ALS_CG_CLASSES + 1];
@@ -577,7 +594,7 @@ static int als_cg_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_
     int64_t nnz = 0;
     for (int64_t r = 0; r < nrows; ++r) {
         int64_t len = 0;
-        for (int s = 0; s < nobs; ++s) len += ip[s][(size_t)r + 1] - ip[s][(size_t)r];
+        for (int s = 0; s < sw.nobs; ++s) len += ip[s][(size_t)r + 1] - ip[s][(size_t)r];
         if (len > INT32_MAX) return fail(CMF_EUNSUPPORTED, "cmf_als_cg_step: a row with more than 2^31 - 1 stored entries");
         nnz += len;
         int q = 0;
@@ -591,7 +608,7 @@ static int als_cg_rows(cmf_ctx *c, int f, double l2, int64_t r_begin, int64_t r_
     int64_t *drows = (int64_t *)c->als_desc.p;
     if (!all.empty()) HIPCHK(hipMemcpyAsync(drows, all.data(), all.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream)); // the host vector may go
-    a.Fin = c->F[f];
+    a.Fin = c->F[sw.f];
     a.Fout = Fout;
     a.out_row0 = out_row0;
     a.l2 = (float)l2;
@@ -615,25 +632,20 @@ static int als_step(cmf_ctx *c, double l2, int nn_mask, int mask, int sweeps, in
     const int bits[3] = {CMF_UPD_V, CMF_UPD_U, CMF_UPD_Z}, fs[3] = {CMF_V, CMF_U, CMF_Z}; // sweep order V, U, Z (cmf_solvers.py:248-263)
     const int nnb[3] = {CMF_NN_V, CMF_NN_U, CMF_NN_Z};
     for (int s = 0; s < 3; ++s) {
-        if (!(mask & bits[s])) continue;
         const int f = fs[s];
+        if (!(mask & bits[s]) || c->frows[f] <= 0) continue;
         const bool nn = (nn_mask & nnb[s]) != 0;
-        if (c->frows[f] <= 0) continue;
-        if (!als_observed(c, f)) {
-            if (nn && sweeps) CHK(als_nnls_sweep_shared(c, f, l2, sweeps));
-            else CHK(als_sweep_shared(c, f, l2, nn));
-            continue;
+        const AlsSweep sw = als_sweep(c, f);
+        switch (als_route(als_observed(sw), nn, sweeps, cg_steps)) {
+        case ALS_SHARED_EXACT: CHK(als_sweep_shared(c, sw, l2, nn)); break;
+        case ALS_SHARED_HALS: CHK(als_nnls_sweep_shared(c, f, l2, sweeps)); break;
+        case ALS_ROWS_NNLS: CHK(als_rows_nnls(c, sw, l2, sweeps)); break;
+        case ALS_ROWS_CG: CHK(als_cg_rows(c, sw, l2, 0, c->frows[f], cg_steps, c->F[f], 0)); break;
+        case ALS_ROWS_EXACT:
+            CHK(als_rows_solve(c, sw, l2));
+            CHK(als_apply(c, f, (const float *)c->als_sol.p, nn));
+            break;
         }
-        if (nn && sweeps) {
-            CHK(als_rows(c, f, l2, 0, c->frows[f], true, nullptr, nullptr, sweeps));
-            continue;
-        }
-        if (!nn && cg_steps) {
-            CHK(als_cg_rows(c, f, l2, 0, c->frows[f], cg_steps, c->F[f], 0));
-            continue;
-        }
-        CHK(als_rows(c, f, l2, 0, c->frows[f], true, nullptr, nullptr));
-        CHK(als_apply(c, f, (const float *)c->als_sol.p, nn));
     }
     return CMF_OK;
 }
@@ -644,28 +656,24 @@ extern "C" int cmf_als_step(cmf_ctx *c, double l2, int nn_mask, int mask) {
     return als_step(c, l2, nn_mask, mask, 0);
 }
 
-static int als_nnls_sweeps_ok(const char *what, int sweeps) {
-    if (sweeps < 1 || sweeps > 1024) return fail(CMF_EINVAL, "%s: sweeps must be 1 .. 1024, got %d", what, sweeps);
+// the range of a sweep or step count: lo .. 1024
+static int als_count_ok(const char *what, const char *name, int n, int lo = 1) {
+    if (n < lo || n > 1024) return fail(CMF_EINVAL, "%s: %s must be %d .. 1024, got %d", what, name, lo, n);
     return CMF_OK;
 }
 
 extern "C" int cmf_als_nnls_step(cmf_ctx *c, double l2, int nn_mask, int mask, int sweeps) {
     NEED_PROBLEM(c);
     CHK(als_check(c, "cmf_als_nnls_step", l2, mask));
-    CHK(als_nnls_sweeps_ok("cmf_als_nnls_step", sweeps));
+    CHK(als_count_ok("cmf_als_nnls_step", "sweeps", sweeps));
     return als_step(c, l2, nn_mask, mask, sweeps);
-}
-
-static int als_cg_steps_ok(const char *what, int cg_steps) {
-    if (cg_steps < 1 || cg_steps > 1024) return fail(CMF_EINVAL, "%s: cg_steps must be 1 .. 1024, got %d", what, cg_steps);
-    return CMF_OK;
 }
 
 extern "C" int cmf_als_cg_step(cmf_ctx *c, double l2, int nn_mask, int mask, int cg_steps, int nn_sweeps) {
     NEED_PROBLEM(c);
     CHK(als_check(c, "cmf_als_cg_step", l2, mask));
-    CHK(als_cg_steps_ok("cmf_als_cg_step", cg_steps));
-    if (nn_sweeps < 0 || nn_sweeps > 1024) return fail(CMF_EINVAL, "cmf_als_cg_step: nn_sweeps must be 0 .. 1024, got %d", nn_sweeps);
+    CHK(als_count_ok("cmf_als_cg_step", "cg_steps", cg_steps));
+    CHK(als_count_ok("cmf_als_cg_step", "nn_sweeps", nn_sweeps, 0));
     return als_step(c, l2, nn_mask, mask, nn_sweeps, cg_steps);
 }
 
@@ -674,16 +682,17 @@ extern "C" int cmf_als_cg_rows(cmf_ctx *c, int which, int64_t row0, int64_t nrow
     NEED_PROBLEM(c);
     if (which < 0 || which > 2) return fail(CMF_EINVAL, "cmf_als_cg_rows: bad factor selector");
     CHK(als_check(c, "cmf_als_cg_rows", l2, 1 << which));
-    CHK(als_cg_steps_ok("cmf_als_cg_rows", cg_steps));
+    CHK(als_count_ok("cmf_als_cg_rows", "cg_steps", cg_steps));
     if (row0 < 0 || nrows < 0 || row0 + nrows > c->frows[which]) return fail(CMF_EINVAL, "cmf_als_cg_rows: rows out of range");
-    if (!als_observed(c, which)) return fail(CMF_EINVAL, "cmf_als_cg_rows: this sweep has no observed relation: one shared matrix, no per-row systems");
+    const AlsSweep sw = als_sweep(c, which);
+    if (!als_observed(sw)) return fail(CMF_EINVAL, "cmf_als_cg_rows: this sweep has no observed relation: one shared matrix, no per-row systems");
     if (nrows == 0) return CMF_OK;
     if (!host_f) return fail(CMF_EINVAL, "cmf_als_cg_rows: null output");
     DeviceGuard dg(c->device);
     const size_t bytes = (size_t)nrows * c->kp * sizeof(float);
     CHK(kl_ensure(c, c->als_cg_ws, bytes));
     HIPCHK(hipMemsetAsync(c->als_cg_ws.p, 0, bytes, c->stream));
-    CHK(als_cg_rows(c, which, l2, row0, row0 + nrows, cg_steps, (float *)c->als_cg_ws.p, row0));
+    CHK(als_cg_rows(c, sw, l2, row0, row0 + nrows, cg_steps, (float *)c->als_cg_ws.p, row0));
     HIPCHK(hipMemcpyAsync(host_f, c->als_cg_ws.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return CMF_OK;
@@ -693,7 +702,7 @@ extern "C" int cmf_als_cg_rows(cmf_ctx *c, int which, int64_t row0, int64_t nrow
 extern "C" int cmf_als_nnls_rows(cmf_ctx *c, int64_t nrows, const float *host_H, const float *host_g, float *host_f, int sweeps) {
     NEED_PROBLEM(c);
     if (!host_H || !host_g || !host_f || nrows < 0) return fail(CMF_EINVAL, "cmf_als_nnls_rows: null pointer or negative row count");
-    CHK(als_nnls_sweeps_ok("cmf_als_nnls_rows", sweeps));
+    CHK(als_count_ok("cmf_als_nnls_rows", "sweeps", sweeps));
     if (c->kp > 256) return fail(CMF_EUNSUPPORTED, "cmf_als_nnls_rows: n_components <= 256 only (k_pad = %d)", c->kp);
     if (nrows == 0) return CMF_OK;
     DeviceGuard dg(c->device);
@@ -714,10 +723,11 @@ extern "C" int cmf_als_normal(cmf_ctx *c, int which, int64_t row0, int64_t nrows
     if (which < 0 || which > 2) return fail(CMF_EINVAL, "cmf_als_normal: bad factor selector");
     CHK(als_check(c, "cmf_als_normal", l2, 1 << which));
     if (row0 < 0 || nrows < 0 || row0 + nrows > c->frows[which]) return fail(CMF_EINVAL, "cmf_als_normal: rows out of range");
-    if (!als_observed(c, which)) return fail(CMF_EINVAL, "cmf_als_normal: this sweep has no observed relation: one shared matrix, no per-row systems");
+    const AlsSweep sw = als_sweep(c, which);
+    if (!als_observed(sw)) return fail(CMF_EINVAL, "cmf_als_normal: this sweep has no observed relation: one shared matrix, no per-row systems");
     if (nrows == 0) return CMF_OK;
     DeviceGuard dg(c->device);
-    return als_rows(c, which, l2, row0, row0 + nrows, false, host_H, host_g);
+    return als_rows_to_host(c, sw, l2, row0, row0 + nrows, host_H, host_g);
 }
 
 extern "C" int cmf_als_layout(cmf_ctx *c, int64_t *out4) {
@@ -728,13 +738,9 @@ extern "C" int cmf_als_layout(cmf_ctx *c, int64_t *out4) {
     out4[0] = als_piece_len(c);
     const int fs[3] = {CMF_U, CMF_V, CMF_Z};
     for (int s = 0; s < 3; ++s) {
-        AlsRel rel[2], obs[2];
-        const int nrel = als_rels(fs[s], rel);
-        int nobs = 0;
-        for (int q = 0; q < nrel; ++q)
-            if (c->wm_kind[rel[q].which] == WM_CSR) obs[nobs++] = rel[q];
+        const AlsSweep sw = als_sweep(c, fs[s]);
         AlsPlan pl;
-        if (nobs) CHK(als_plan(c, obs, nobs, 0, c->frows[fs[s]], pl));
+        if (als_observed(sw)) CHK(als_plan(c, sw, 0, c->frows[fs[s]], pl));
         out4[1 + s] = (int64_t)pl.pieces.size();
     }
     return CMF_OK;

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void als_bg_dot64_kernel(const double *a, cons
 } // namespace cmfk
 #endif // CMF_ALS_BG_KERNELS
 
-// ------------------------------------------------------------------ host side (included by cmf_als.hip.h behind als_rels)
+// ------------------------------------------------------------------ host side (included by cmf_als.hip.h behind AlsSweep)
 #if defined(CMF_ALS_BG_HOST) && !defined(CMF_ALS_BG_HOST_DONE)
 #define CMF_ALS_BG_HOST_DONE
 
@@ -132,42 +132,30 @@ __global__ __launch_bounds__(256) void als_bg_dot64_kernel(const double *a, cons
 static const float *als_side_weights(const WCsrDev &M) { return M.ev ? M.ev : M.wv; }
 
 // The part of a sweep's systems that all its rows share: *S = sum_sides coef Gram(B_side) (coef: c0 of a side with a background,
-// 1 of a full side; null when no side has either) and *N = T B of the full side (or null).  Without a background this is the
-// code cmf_als.hip.h had in its place: the Gram of the full side in c->G2, nothing else launched.
-static int als_shared_terms(cmf_ctx *c, const AlsRel *rel, int nrel, const float **S, const float **N) {
+// 1 of a full side; null when no side has either) and *N = T B of the full side (or null).  Without a background S is the Gram of
+// the full side where gram32 leaves it (c->G2): nothing else is launched.
+static int als_shared_terms(cmf_ctx *c, const AlsSweep &sw, const float **S, const float **N) {
     *S = *N = nullptr;
     bool bg = false;
-    for (int s = 0; s < nrel; ++s) bg = bg || (c->wm_kind[rel[s].which] == WM_CSR && c->wm_bg[rel[s].which] > 0.0);
-    if (!bg) {
-        for (int s = 0; s < nrel; ++s) {
-            if (c->wm_kind[rel[s].which] == WM_CSR) continue;
-            CHK(gram32(c, c->F[rel[s].fb], c->frows_pad[rel[s].fb], c->G2));
-            CHK(data_times(c, rel[s].which, rel[s].data_trans, c->F[rel[s].fb], c->num));
-            *S = c->G2;
-            *N = c->num;
-        }
-        return CMF_OK;
-    }
+    for (int s = 0; s < sw.nrel; ++s) bg = bg || (sw.observed[s] && c->wm_bg[sw.rel[s].which] > 0.0);
     const int n4 = c->kp * c->kp / 4;
-    CHK(kl_ensure(c, c->als_bg_s, (size_t)n4 * 16));
-    int have = 0;
-    for (int s = 0; s < nrel; ++s) {   // the order of als_rels: the sum of a V sweep is (coef_x G_u) + (coef_y G_z)
-        const bool obs = c->wm_kind[rel[s].which] == WM_CSR;
-        if (obs && !(c->wm_bg[rel[s].which] > 0.0)) continue;
-        CHK(gram32(c, c->F[rel[s].fb], c->frows_pad[rel[s].fb], c->G2));
-        {
+    if (bg) CHK(kl_ensure(c, c->als_bg_s, (size_t)n4 * 16));
+    for (int s = 0; s < sw.nrel; ++s) {   // the order of als_rels: the sum of a V sweep is (coef_x G_u) + (coef_y G_z)
+        const AlsRel &r = sw.rel[s];
+        if (sw.observed[s] && !(c->wm_bg[r.which] > 0.0)) continue;
+        CHK(gram32(c, c->F[r.fb], c->frows_pad[r.fb], c->G2));
+        if (bg) {
             Timed tm(c, CMF_K_ELEMWISE);
             hipLaunchKernelGGL(cmfk::als_bg_combine_kernel, dim3((unsigned)std::min(64, (n4 + 255) / 256)), dim3(256), 0, c->stream, (float *)c->als_bg_s.p,
-                               (const float *)c->G2, obs ? (float)c->wm_bg[rel[s].which] : 1.0f, have, n4);
+                               (const float *)c->G2, sw.observed[s] ? (float)c->wm_bg[r.which] : 1.0f, *S ? 1 : 0, n4);
             HIPCHK(hipGetLastError());
         }
-        have = 1;
-        if (!obs) {
-            CHK(data_times(c, rel[s].which, rel[s].data_trans, c->F[rel[s].fb], c->num));
+        *S = bg ? (const float *)c->als_bg_s.p : c->G2;
+        if (!sw.observed[s]) {
+            CHK(data_times(c, r.which, r.data_trans, c->F[r.fb], c->num));
             *N = c->num;
         }
     }
-    *S = (const float *)c->als_bg_s.p;
     return CMF_OK;
 }
 

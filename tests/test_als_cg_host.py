@@ -1,5 +1,5 @@
-"""Conjugate-gradient row solve of the ALS solver, host side: the NumPy yardstick (als_cg_yardstick.py) against the exact solves of
-als_yardstick.py, the planted problem of the documentation, keyword validation before any device is opened, the ABI surface."""
+"""Conjugate-gradient row solve of the ALS solver, host side: the NumPy yardstick (als_yardstick.py) against its own exact solves,
+the planted problem of the documentation, keyword validation before any device is opened, the ABI surface."""
 import os
 import re
 
@@ -7,7 +7,6 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import als_cg_yardstick as G
 import als_yardstick as A
 from test_gpu_wmu import fit_inputs
 
@@ -49,11 +48,11 @@ def test_k_steps_are_the_exact_solve():
     for wy in (Wy, None):
         Rx, Ry = A.Relation(X, Wx), A.Relation(Y, wy)
         for which in "UVZ":
-            if not G.observed(Rx, Ry, which):
+            if not A.observed(Rx, Ry, which):
                 continue
             H, g = A.systems(Rx, Ry, U, V, Z, which, 0.1)
             ref = np.linalg.solve(H, g[:, :, None])[:, :, 0]
-            got = G.sweep_rows(Rx, Ry, U, V, Z, which, 0.1, k)
+            got = A.sweep(Rx, Ry, U, V, Z, which, 0.1, cg_steps=k)
             worst = max(worst, float(np.abs(got - ref).max() / np.abs(ref).max()))
     print("7 CG steps against the exact solve: worst relative difference %.2e" % worst)
     assert worst <= 1e-10
@@ -67,12 +66,12 @@ def test_planted_problem_descends_for_every_step_count_and_the_documented_count_
     X, Y, Wx, U, V, Z = _planted()
     Ws = sp.csr_matrix(Wx)
     start = A.objective(X, Y, Wx, None, U, V, Z, L2)
-    Ur, Vr, Zr, _, _ = A.fit(X, Y, Ws, None, U, V, Z, 20, 0, L2)
+    Ur, Vr, Zr, _, _ = A.fit(X, Y, Ws, None, U, V, Z, 20, L2)
     exact = A.objective(X, Y, Wx, None, Ur, Vr, Zr, L2)
     last = {}
     for steps in (1, 2, 3, 4, 6):
         trace = []
-        G.fit(X, Y, Ws, None, U, V, Z, 20, L2, steps, trace=trace)
+        A.fit(X, Y, Ws, None, U, V, Z, 20, L2, cg_steps=steps, trace=trace)
         seq = [start] + trace
         assert len(trace) == 20 and all(b <= a * (1 + 1e-12) for a, b in zip(seq, seq[1:])), (steps, seq)
         last[steps] = trace[-1]
@@ -86,15 +85,14 @@ def test_rows_without_information_become_zeros_and_other_routes_are_kept():
     Wx = Wx.copy()
     Wx[7] = 0
     Ws = sp.csr_matrix(Wx)
-    Un, _, _ = G.step(X, Y, Ws, None, U, V, Z, L2, 4, mask=A.U_BIT)
+    Un, _, _ = A.step(X, Y, Ws, None, U, V, Z, L2, cg_steps=4, mask=A.U_BIT)
     assert (Un[7] == 0).all() and (np.abs(Un).sum(axis=1) > 0).sum() == len(Un) - 1
     # Z has no observed relation here: the exact solve; a factor in nn_mask: the projection, or coordinate descent
-    assert (G.step(X, Y, Ws, None, U, V, Z, L2, 4, mask=A.Z_BIT)[2] == A.step(X, Y, Ws, None, U, V, Z, L2, mask=A.Z_BIT)[2]).all()
-    assert (G.step(X, Y, Ws, None, U, V, Z, L2, 4, mask=A.U_BIT, nn_mask=A.U_BIT)[0]
+    assert (A.step(X, Y, Ws, None, U, V, Z, L2, cg_steps=4, mask=A.Z_BIT)[2] == A.step(X, Y, Ws, None, U, V, Z, L2, mask=A.Z_BIT)[2]).all()
+    assert (A.step(X, Y, Ws, None, U, V, Z, L2, cg_steps=4, mask=A.U_BIT, nn_mask=A.U_BIT)[0]
             == A.step(X, Y, Ws, None, U, V, Z, L2, mask=A.U_BIT, nn_mask=A.U_BIT)[0]).all()
-    import als_nnls_yardstick as N
-    assert (G.step(X, Y, Ws, None, U, V, Z, L2, 4, mask=A.U_BIT, nn_mask=A.U_BIT, nn_sweeps=2)[0]
-            == N.step(X, Y, Ws, None, U, V, Z, L2, 2, mask=A.U_BIT, nn_mask=A.U_BIT)[0]).all()
+    assert (A.step(X, Y, Ws, None, U, V, Z, L2, cg_steps=4, mask=A.U_BIT, nn_mask=A.U_BIT, nn_sweeps=2)[0]
+            == A.step(X, Y, Ws, None, U, V, Z, L2, nn_sweeps=2, mask=A.U_BIT, nn_mask=A.U_BIT)[0]).all()
 
 
 # ------------------------------------------------------------------ validation before any device is opened

@@ -88,7 +88,7 @@ def test_objective_descends_and_beats_300_mu_iterations_on_the_planted_problem()
     X, Y, Wx, U, V, Z = _planted()
     l2 = 0.05
     trace = []
-    Ua, Va, Za, n, _ = A.fit(X, Y, sp.csr_matrix(Wx), None, U, V, Z, 10, 0, l2, trace=trace)
+    Ua, Va, Za, n, _ = A.fit(X, Y, sp.csr_matrix(Wx), None, U, V, Z, 10, l2, trace=trace)
     assert n == 10 and len(trace) == 10
     start = A.objective(X, Y, Wx, None, U, V, Z, l2)
     seq = [start] + trace
@@ -103,7 +103,7 @@ def test_objective_descends_and_beats_300_mu_iterations_on_the_planted_problem()
     assert trace[-1] < 0.95 * mu
     assert rmse[0] < rmse[1]
     # the non-negative projection is honoured and is weaker (documented): every factor >= 0, a larger objective
-    Up, Vp, Zp, _, _ = A.fit(X, Y, Wx, None, U, V, Z, 10, 0, l2, nn_mask=7)
+    Up, Vp, Zp, _, _ = A.fit(X, Y, Wx, None, U, V, Z, 10, l2, nn_mask=7)
     assert min(Up.min(), Vp.min(), Zp.min()) >= 0 and A.objective(X, Y, Wx, None, Up, Vp, Zp, l2) > trace[-1]
 
 

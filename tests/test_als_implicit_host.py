@@ -1,4 +1,4 @@
-"""ALS with a background weight (implicit feedback), host side: the structured yardstick (als_implicit_yardstick.py) against the
+"""ALS with a background weight (implicit feedback), host side: the structured yardstick (als_yardstick.py with cx / cy) against the
 dense weighted problem it is equal to, its optimality conditions, the planted click problem of the documentation, keyword
 validation before any device is opened, the ABI surface."""
 import os
@@ -8,10 +8,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import als_cg_yardstick as C
-import als_implicit_yardstick as I
-import als_nnls_yardstick as N
 import als_yardstick as A
+import click_problem as K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -51,22 +49,22 @@ def _config(name):
     rng = np.random.RandomState(9)
     Wx = _weights(rng, X.shape, cx)
     Wy = _weights(rng, Y.shape, max(cy, 0.25)) if y_obs else None
-    Dx, Wdx = I.dense_equivalent(X, Wx, cx)
-    Dy, Wdy = I.dense_equivalent(Y, Wy, cy) if cy else (Y, Wy)
+    Dx, Wdx = A.dense_equivalent(X, Wx, cx)
+    Dy, Wdy = A.dense_equivalent(Y, Wy, cy) if cy else (Y, Wy)
     return (X, Y, Wx, Wy, cx, cy), (Dx, Dy, Wdx, Wdy), (U, V, Z)
 
 
 # ------------------------------------------------------------------ the structured form is the dense weighted problem
 @pytest.mark.parametrize("config", sorted(CONFIGS))
 def test_structured_step_equals_the_dense_equivalent(config):
-    """One step of each route -- exact, 4 coordinate-descent sweeps, 3 CG steps -- equals the step of the yardstick it is built on
+    """One step of each route -- exact, 4 coordinate-descent sweeps, 3 CG steps -- equals the same step without a background
     fed c0 everywhere / w on the pattern / data 0 off it, to 1e-10 of the largest entry.  An empty row and an empty column included."""
     (X, Y, Wx, Wy, cx, cy), (Dx, Dy, Wdx, Wdy), (U, V, Z) = _config(config)
     l2 = 0.05
     assert (np.diff(Wx.indptr) == 0).any() and (np.diff(Wx.tocsc().indptr) == 0).any()
-    cases = (("exact", I.step(X, Y, Wx, Wy, U, V, Z, l2, cx, cy), A.step(Dx, Dy, Wdx, Wdy, U, V, Z, l2)),
-             ("nnls", I.step(X, Y, Wx, Wy, U, V, Z, l2, cx, cy, nn_mask=7, nn_sweeps=4), N.step(Dx, Dy, Wdx, Wdy, U, V, Z, l2, 4)),
-             ("cg", I.step(X, Y, Wx, Wy, U, V, Z, l2, cx, cy, cg_steps=3), C.step(Dx, Dy, Wdx, Wdy, U, V, Z, l2, 3)))
+    cases = (("exact", A.step(X, Y, Wx, Wy, U, V, Z, l2, cx=cx, cy=cy), A.step(Dx, Dy, Wdx, Wdy, U, V, Z, l2)),
+             ("nnls", A.step(X, Y, Wx, Wy, U, V, Z, l2, cx=cx, cy=cy, nn_mask=7, nn_sweeps=4), A.step(Dx, Dy, Wdx, Wdy, U, V, Z, l2, nn_mask=7, nn_sweeps=4)),
+             ("cg", A.step(X, Y, Wx, Wy, U, V, Z, l2, cx=cx, cy=cy, cg_steps=3), A.step(Dx, Dy, Wdx, Wdy, U, V, Z, l2, cg_steps=3)))
     for route, got, ref in cases:
         for name, a, b in zip("UVZ", got, ref):
             err = np.abs(a - b).max() / np.abs(b).max()
@@ -74,9 +72,9 @@ def test_structured_step_equals_the_dense_equivalent(config):
             assert err <= 1e-10, (config, route, name)
     # the error and the objective are the dense ones too
     Un, Vn, Zn = cases[0][1]
-    for a, b in zip(I.errors(X, Y, Wx, Wy, Un, Vn, Zn, cx, cy), A.errors(Dx, Dy, Wdx, Wdy, Un, Vn, Zn)):
+    for a, b in zip(A.errors(X, Y, Wx, Wy, Un, Vn, Zn, cx=cx, cy=cy), A.errors(Dx, Dy, Wdx, Wdy, Un, Vn, Zn)):
         assert abs(a - b) <= 1e-10 * b
-    assert abs(I.objective(X, Y, Wx, Wy, Un, Vn, Zn, l2, cx, cy) - A.objective(Dx, Dy, Wdx, Wdy, Un, Vn, Zn, l2)) <= 1e-10 * A.objective(Dx, Dy, Wdx, Wdy, Un, Vn, Zn, l2)
+    assert abs(A.objective(X, Y, Wx, Wy, Un, Vn, Zn, l2, cx=cx, cy=cy) - A.objective(Dx, Dy, Wdx, Wdy, Un, Vn, Zn, l2)) <= 1e-10 * A.objective(Dx, Dy, Wdx, Wdy, Un, Vn, Zn, l2)
 
 
 @pytest.mark.parametrize("config", sorted(CONFIGS))
@@ -87,7 +85,7 @@ def test_every_swept_row_has_zero_gradient_of_the_dense_objective(config):
     l2 = 0.05
     F = dict(U=U, V=V, Z=Z)
     for which, bit in (("V", A.V_BIT), ("U", A.U_BIT), ("Z", A.Z_BIT)):
-        Un, Vn, Zn = I.step(X, Y, Wx, Wy, F["U"], F["V"], F["Z"], l2, cx, cy, mask=bit)
+        Un, Vn, Zn = A.step(X, Y, Wx, Wy, F["U"], F["V"], F["Z"], l2, cx=cx, cy=cy, mask=bit)
         F = dict(U=Un, V=Vn, Z=Zn)
         G = A.gradient(Dx, Dy, Wdx, Wdy, Un, Vn, Zn, l2, which)
         H, g = A.systems(A.Relation(Dx, Wdx), A.Relation(Dy, Wdy), Un, Vn, Zn, which, l2)
@@ -100,24 +98,24 @@ def test_every_swept_row_has_zero_gradient_of_the_dense_objective(config):
 def test_systems_of_a_row_without_entries():
     (X, Y, Wx, Wy, cx, cy), _, (U, V, Z) = _config("x")
     i = X.shape[0] // 4
-    H, g = I.systems(A.Relation(X, Wx), A.Relation(Y, Wy), U, V, Z, "U", 0.05, cx, cy, rows=[i])
+    H, g = A.systems(A.Relation(X, Wx), A.Relation(Y, Wy), U, V, Z, "U", 0.05, cx=cx, cy=cy, rows=[i])
     assert (g == 0).all() and np.abs(H[0] - (cx * V.T @ V + 0.05 * np.eye(V.shape[1]))).max() <= 1e-13 * np.abs(H).max()
 
 
 # ------------------------------------------------------------------ the planted click problem
 def _click_fits(seed):
-    counts, train, test, Y, U0, V0, Z0 = I.clicks(seed)
-    P, W = I.click_relations(counts, train)
+    counts, train, test, Y, U0, V0, Z0 = K.clicks(seed)
+    P, W = K.click_relations(counts, train)
     ones = sp.csr_matrix(train.astype(np.float64))
     trace = []
-    U, V, Z, _, _ = I.fit(P, Y, W, None, U0, V0, Z0, 15, 0, 2.0, cx=1.0, trace=trace)
-    start = I.objective(P, Y, W, None, U0, V0, Z0, 2.0, cx=1.0)
-    rec = {"background": I.recall_at(U @ V.T, train, test)}
-    U, V, Z, _, _ = I.fit(P, Y, ones, None, U0, V0, Z0, 15, 0, 2.0, cx=1.0)
-    rec["zeros as data"] = I.recall_at(U @ V.T, train, test)
-    U, V, Z, _, _ = I.fit(P, Y, ones, None, U0, V0, Z0, 15, 0, 2.0)
-    rec["observed only"] = I.recall_at(U @ V.T, train, test)
-    rec["popularity"] = I.recall_at(np.broadcast_to(train.sum(axis=0)[None].astype(np.float64), train.shape), train, test)
+    U, V, Z, _, _ = A.fit(P, Y, W, None, U0, V0, Z0, 15, 2.0, cx=1.0, trace=trace)
+    start = A.objective(P, Y, W, None, U0, V0, Z0, 2.0, cx=1.0)
+    rec = {"background": K.recall_at(U @ V.T, train, test)}
+    U, V, Z, _, _ = A.fit(P, Y, ones, None, U0, V0, Z0, 15, 2.0, cx=1.0)
+    rec["zeros as data"] = K.recall_at(U @ V.T, train, test)
+    U, V, Z, _, _ = A.fit(P, Y, ones, None, U0, V0, Z0, 15, 2.0)
+    rec["observed only"] = K.recall_at(U @ V.T, train, test)
+    rec["popularity"] = K.recall_at(np.broadcast_to(train.sum(axis=0)[None].astype(np.float64), train.shape), train, test)
     return rec, [start] + trace
 
 

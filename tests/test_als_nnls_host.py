@@ -1,4 +1,4 @@
-"""Non-negative row solve of the ALS solver, host side: the NumPy yardstick (als_nnls_yardstick.py) against scipy's NNLS and the
+"""Non-negative row solve of the ALS solver, host side: the NumPy yardstick (als_yardstick.py) against scipy's NNLS and the
 KKT conditions, the planted problem of the documentation against the projection and the weighted MU yardstick, one pass against
 the HALS yardstick, keyword validation before any device is opened, the ABI surface."""
 import os
@@ -10,7 +10,6 @@ import scipy.linalg
 import scipy.optimize
 import scipy.sparse as sp
 
-import als_nnls_yardstick as N
 import als_yardstick as A
 import hals_yardstick as HY
 import wmu_yardstick as WM
@@ -41,7 +40,7 @@ def test_many_sweeps_reach_the_nnls_solution_and_its_kkt_conditions():
     (H f - g)_j >= -eps where f_j = 0, |(H f - g)_j| <= eps where f_j > 0."""
     X, Y, Wx, U, V, Z = _planted()
     H, g = A.systems(A.Relation(X, sp.csr_matrix(Wx)), A.Relation(Y, None), U, V, Z, "U", 0.05)
-    F = N.cd_rows(H, g, U, 2000)
+    F = A.cd_rows(H, g, U, 2000)
     ref = np.empty_like(F)
     for i in range(len(F)):
         L = np.linalg.cholesky(H[i])
@@ -63,12 +62,12 @@ def test_planted_problem_descends_and_beats_projection_and_300_mu_iterations():
     l2 = 0.05
     Ws = sp.csr_matrix(Wx)
     trace = []
-    Un, Vn, Zn = N.fit(X, Y, Ws, None, U, V, Z, 10, l2, 4, trace=trace)
+    Un, Vn, Zn = A.fit(X, Y, Ws, None, U, V, Z, 10, l2, nn_mask=7, nn_sweeps=4, trace=trace)[:3]
     seq = [A.objective(X, Y, Wx, None, U, V, Z, l2)] + trace
     assert len(trace) == 10 and all(b <= a * (1 + 1e-12) for a, b in zip(seq, seq[1:])), seq
     assert min(Un.min(), Vn.min(), Zn.min()) >= 0
     Um, Vm, Zm, _, _ = WM.fit(X, Y, Wx, None, U, V, Z, 300, 0, l2=l2)
-    Up, Vp, Zp, _, _ = A.fit(X, Y, Ws, None, U, V, Z, 10, 0, l2, nn_mask=7)
+    Up, Vp, Zp, _, _ = A.fit(X, Y, Ws, None, U, V, Z, 10, l2, nn_mask=7)
     mu, proj = (A.objective(X, Y, Wx, None, P, Q, R, l2) for P, Q, R in ((Um, Vm, Zm), (Up, Vp, Zp)))
     unobserved = Wx == 0
     rmse = [float(np.sqrt((((X - P @ Q.T) ** 2)[unobserved]).mean())) for P, Q in ((Un, Vn), (Um, Vm), (Up, Vp))]
@@ -82,12 +81,12 @@ def test_one_sweep_on_an_unweighted_problem_is_a_hals_step():
     """No weights at all: every row of a sweep has the one Gram, and one pass is hals_yardstick's step with l1 = 0."""
     X, Y, _, U, V, Z = _planted()
     l2 = 0.05
-    got = N.step(X, Y, None, None, U, V, Z, l2, 1)
+    got = A.step(X, Y, None, None, U, V, Z, l2, nn_mask=7, nn_sweeps=1)
     ref = HY.hals_step(X, Y, U, V, Z, 0.0, l2)
     for a, b in zip(got, ref):
         assert np.abs(a - b).max() <= 1e-12 * np.abs(b).max()
-    # a signed V (nn_mask without its bit) takes the solve of als_yardstick
-    got = N.step(X, Y, None, None, U, V, Z, l2, 1, nn_mask=5)
+    # a signed V (nn_mask without its bit) takes the exact solve
+    got = A.step(X, Y, None, None, U, V, Z, l2, nn_mask=5, nn_sweeps=1)
     assert (got[1] == A.step(X, Y, None, None, U, V, Z, l2, mask=A.V_BIT)[1]).all()
 
 
@@ -95,7 +94,7 @@ def test_rows_without_information_become_zeros():
     X, Y, Wx, U, V, Z = _planted()
     Wx = Wx.copy()
     Wx[7] = 0
-    Un, _, _ = N.step(X, Y, sp.csr_matrix(Wx), None, U, V, Z, 0.05, 4, mask=A.U_BIT)
+    Un, _, _ = A.step(X, Y, sp.csr_matrix(Wx), None, U, V, Z, 0.05, mask=A.U_BIT, nn_mask=7, nn_sweeps=4)
     assert (Un[7] == 0).all() and (Un.sum(axis=1) > 0).sum() == len(Un) - 1
 
 

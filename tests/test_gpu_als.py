@@ -156,8 +156,55 @@ def test_rows_cut_into_pieces(lib, k):
         ctx.close()
 
 
+# ------------------------------------------------------------------ 2b. rows in more than one chunk
+def test_rows_on_both_sides_of_a_chunk_boundary(lib):
+    """k = 200 (k_pad = 256: chunks of 2 GiB / 256 KiB = 8192 rows) and 8492 rows of U, so the U sweep runs a chunk of 8192 rows and
+    one of 300, each with its own slice of the piece list and of the piece index.  Rows i and i + 8192 (i < 300) carry the same
+    pattern, weights and data, lengths cycling through 0, 1, 31, 32, 33, 70; rows 300 .. 8191 hold one entry.  Y is full and zero:
+    no shared matrix, so the piece index is what tells a row without information.  A row's arithmetic does not depend on its chunk:
+    after the sweep the two blocks are equal with ==, and both agree with the yardstick (als_yardstick.tolerance on those 600
+    rows) -- by the exact solves, and by 2 coordinate-descent sweeps from a non-negative start, where the rows of length 0 on
+    either side of the boundary are exact zeros."""
+    m, d, p, k, twin, cut, l2 = 8492, 80, 4, 200, 300, 8192, 0.1
+    rng = np.random.RandomState(17)
+    lengths = np.ones(m, dtype=np.int64)
+    lengths[:twin] = lengths[cut:] = np.resize([0, 1, 31, 32, 33, 70], twin)
+    W, X = np.zeros((m, d)), np.zeros((m, d))
+    for i in range(cut):
+        c = rng.permutation(d)[:lengths[i]]
+        W[i, c], X[i, c] = _f32(0.25 + 3.75 * rng.rand(len(c))), _f32(rng.randn(len(c)))
+    W[cut:], X[cut:] = W[:twin], X[:twin]
+    Wx, Y = sp.csr_matrix(W), np.zeros((d, p))
+    assert (np.diff(Wx.indptr) == lengths).all()
+    U0 = _f32(rng.randn(m, k))
+    U0[cut:] = U0[:twin]
+    rows = np.concatenate((np.arange(twin), np.arange(cut, m)))
+    empty = lengths[rows] == 0
+    Rx, Ry = A.Relation(X, Wx), A.Relation(Y, None)
+    for name, nn_sweeps in (("exact", 0), ("nnls", 2)):
+        F = [np.abs(U0) if nn_sweeps else U0, _f32(rng.randn(d, k)), _f32(rng.randn(p, k))]
+        route = dict(non_negative=bool(nn_sweeps), nn_sweeps=nn_sweeps, rows=rows)
+        y64, y32 = (A.sweep(Rx, Ry, *F, "U", l2, **route, dtype=dt) for dt in (np.float64, np.float32))
+        ctx = _context(lib, X, Y, F, Wx, None)
+        assert ctx.geometry()[3] == 256 and ctx.als_layout()[1] == int((lengths > 0).sum())
+        if nn_sweeps:
+            ctx.als_nnls_step(l2, A.U_BIT, A.U_BIT, nn_sweeps)
+        else:
+            ctx.als_step(l2, 0, A.U_BIT)
+        got = ctx.get_factor(U_)
+        ctx.close()
+        tol = A.tolerance(y32, y64, k)
+        err = float(np.abs(got[rows] - y64).max())
+        print("%s: rows 0 .. 299 and 8192 .. 8491 against the yardstick: |err| / tol %.3f (tol %.3e)" % (name, err / tol, tol))
+        assert (got[cut:] == got[:twin]).all(), "%s: %d rows differ from their twins in the other chunk" % (name, int((got[cut:] != got[:twin]).any(axis=1).sum()))
+        assert np.isfinite(got).all() and err <= tol
+        assert empty.sum() == 100 and (y64[empty] == 0).all() and (got[rows][empty] == 0).all()
+        if nn_sweeps:
+            assert (got >= 0).all()
+
+
 # ------------------------------------------------------------------ 3, 5. one full step against the yardstick
-SHAPES = [(257, 1031, 77, 7), (128, 3000, 150, 128), (70, 333, 129, 40), (300, 1200, 130, 256)]
+SHAPES =[(257, 1031, 77, 7), (128, 3000, 150, 128), (70, 333, 129, 40), (300, 1200, 130, 256)]
 _cases = {}
 
 
@@ -192,7 +239,7 @@ def _reference(case, l2, mask, nn):
     X, Y, Wx, Wy, F, refs = case
     if (l2, mask, nn) not in refs:
         Rx, Ry = A.Relation(X, Wx), A.Relation(Y, Wy)
-        refs[(l2, mask, nn)] = (A.step(Rx, Ry, None, None, *F, l2, mask, nn), A.step(Rx, Ry, None, None, *F, l2, mask, nn, dtype=np.float32))
+        refs[(l2, mask, nn)] = tuple(A.step(Rx, Ry, None, None, *F, l2, mask=mask, nn_mask=nn, dtype=dt) for dt in (np.float64, np.float32))
     return refs[(l2, mask, nn)]
 
 
@@ -298,7 +345,7 @@ def test_fit_matches_the_float64_yardstick(lib):
     signed = dict(U_non_negative=False, V_non_negative=False, Z_non_negative=False)
     model = CMF(solver="als", max_iter=iters, **signed, **kw)
     Ug, Vg, Zg = model.fit_transform(Xi, Y, U=U.copy(), V=V.copy(), Z=Z.copy(), x_entry_weights="observed")
-    Ur, Vr, Zr, n_iter, _ = A.fit(X, Y, Wref, None, U, V, Z, iters, 0, l2)
+    Ur, Vr, Zr, n_iter, _ = A.fit(X, Y, Wref, None, U, V, Z, iters, l2)
     assert model.n_iter_ == n_iter == iters
     ref = sum(A.errors(X, Y, Wref, None, Ur, Vr, Zr))
     print("fit: reconstruction_err_ %.9g, yardstick %.9g, relative %.2e" % (model.reconstruction_err_, ref, abs(model.reconstruction_err_ - ref) / ref))
@@ -342,7 +389,7 @@ def test_fit_matches_the_float64_yardstick(lib):
 def test_fit_stops_at_the_yardsticks_iteration(lib, tol, seed, n_listed):
     from pycmf_amd import CMF
     X, Y, Wx, Wy, U, V, Z = fit_inputs(seed)
-    _, _, _, n_ref, ratios = A.fit(X, Y, Wx, Wy, U, V, Z, 200, tol, 0.05, alpha=0.5)
+    _, _, _, n_ref, ratios = A.fit(X, Y, Wx, Wy, U, V, Z, 200, 0.05, tol=tol, alpha=0.5)
     # the yardstick alone must be far from the crossing at every check, or rounding would decide the test
     margin = min(abs(r - tol) for r in ratios) / tol
     assert margin >= 0.2 and n_ref == n_listed, (n_ref, margin)

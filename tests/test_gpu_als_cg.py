@@ -1,5 +1,5 @@
 """The conjugate-gradient row solve of the ALS solver on the device (cmf_als_cg_rows, cmf_als_cg_step, CMF(als_cg_steps=n)) against
-the float64 yardstick of als_cg_yardstick.py on float32-rounded inputs.  All factor data is SIGNED: with positive factors one
+the float64 yardstick of als_yardstick.py on float32-rounded inputs.  All factor data is SIGNED: with positive factors one
 eigenvalue dominates and float32 and float64 CG iterates part ways after three steps, which would make a comparison of iterates
 vacuous.  Tolerance per comparison (als_yardstick.tolerance, the HALS rule): tol = max(4 max|y32 - y64|, (k + 16) 2^-24 max|y64|)
 with y32 the float32 run of the same formulas -- and the first term may not exceed 1e-3 max|y64| (``_tol`` asserts it), so the rule
@@ -10,8 +10,6 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import als_cg_yardstick as G
-import als_nnls_yardstick as N
 import als_yardstick as A
 from test_gpu_als import SHAPES, _case, _context, _f32
 from test_gpu_wmu import fit_inputs
@@ -70,7 +68,7 @@ def test_exact_inputs_are_solved_exactly(lib, k):
     Rx, Ry = A.Relation(X, Wx), A.Relation(Y, None)
     ctx = _context(lib, X, Y, F, Wx, None)
     for steps in (1, 3):
-        ref = G.sweep_rows(Rx, Ry, *F, "U", 0.25, steps)
+        ref = A.sweep(Rx, Ry, *F, "U", 0.25, cg_steps=steps)
         assert (ref == 0.5 * X[:, :k] + 0.25 * X[:, k:]).all() and (ref[3] == 0).all() and (ref != 0).any()
         got = ctx.als_cg_rows(0, 0, len(ref), 0.25, steps)
         assert (got[:, :k] == ref).all(), "k %d, %d steps: %d of %d coordinates differ" % (k, steps, int((got[:, :k] != ref).sum()), ref.size)
@@ -123,7 +121,7 @@ def _rows_reference(case, which, steps):
     X, Y, Wx, Wy, F, refs = case
     if (which, steps) not in refs:
         Rx, Ry = A.Relation(X, Wx), A.Relation(Y, Wy)
-        refs[(which, steps)] = tuple(G.sweep_rows(Rx, Ry, *F, which, L2, steps, dtype=dt) for dt in (np.float64, np.float32))
+        refs[(which, steps)] = tuple(A.sweep(Rx, Ry, *F, which, L2, cg_steps=steps, dtype=dt) for dt in (np.float64, np.float32))
     return refs[(which, steps)]
 
 
@@ -185,7 +183,7 @@ def test_twelve_steps_at_k_7_reach_the_exact_solve(lib):
     for w, which in enumerate(NAMES):
         H, g = A.systems(Rx, Ry, *F, which, L2)
         ref = np.linalg.solve(H, g[:, :, None])[:, :, 0]
-        ref[N.no_information(Rx, Ry, *F, which)] = 0
+        ref[A.no_information(Rx, Ry, *F, which)] = 0
         got = ctx.als_cg_rows(w, 0, F[w].shape[0], L2, 12)[:, :7]
         rel = float(np.abs(got - ref).max() / np.abs(ref).max())
         print("sweep %s, 12 steps at k = 7: %.2e relative to the float64 exact solve" % (which, rel))
@@ -209,8 +207,8 @@ def _reference(shape, yform, mask, nn, nn_sweeps):
     if key not in _refs:
         X, Y, Wx, Wy, F = _start(shape, yform, nn)
         Rx, Ry = A.Relation(X, Wx), A.Relation(Y, Wy)
-        _refs[key] = tuple(G.step(Rx, Ry, None, None, *F, L2, STEP_STEPS, mask, nn, nn_sweeps, dtype=dt) for dt in (np.float64, np.float32)) + (
-            [N.no_information(Rx, Ry, *F, w) for w in NAMES],)
+        _refs[key] = tuple(A.step(Rx, Ry, None, None, *F, L2, cg_steps=STEP_STEPS, mask=mask, nn_mask=nn, nn_sweeps=nn_sweeps, dtype=dt) for dt in (np.float64, np.float32)) + (
+            [A.no_information(Rx, Ry, *F, w) for w in NAMES],)
     return _refs[key]
 
 
@@ -400,7 +398,7 @@ def test_fit_reaches_the_objective_of_exact_als(lib):
         Ug, Vg, Zg = model.fit_transform(Xi, Y, U=U.copy(), V=V.copy(), Z=Z.copy(), x_entry_weights="observed")
         assert model.n_iter_ == iters and all(np.isfinite(G_).all() for G_ in (Ug, Vg, Zg))
         obj[steps] = A.objective(X, Y, Wx, None, Ug, Vg, Zg, l2)
-    Ur, Vr, Zr, _, _ = A.fit(X, Y, Wref, None, U, V, Z, iters, 0, l2)
+    Ur, Vr, Zr, _, _ = A.fit(X, Y, Wref, None, U, V, Z, iters, l2)
     exact = A.objective(X, Y, Wx, None, Ur, Vr, Zr, l2)
     print("objective after %d iterations: exact ALS (float64) %.2f, %d CG steps %.2f, 1 CG step %.2f" % (iters, exact, DOCUMENTED_STEPS, obj[DOCUMENTED_STEPS], obj[1]))
     assert obj[DOCUMENTED_STEPS] <= 1.02 * exact

@@ -1,5 +1,5 @@
 """ALS with a background weight on the device (cmf_set_background_weight, cmf_als_residual_sq, the three step entry points,
-CMF(solver="als", x_background_weight=...)) against the float64 yardstick of als_implicit_yardstick.py on float32-rounded inputs.
+CMF(solver="als", x_background_weight=...)) against the float64 yardstick of als_yardstick.py (cx / cy) on float32-rounded inputs.
 Shapes and cases are the ones of test_gpu_als.py; its weights lie in [0.25, 4], so c0 = 0.25 satisfies w >= c0 as they stand.
 Tolerance of every comparison of factors, per factor: tol = max(4 max|y32 - y64|, (k + 16) 2^-24 max|y64|) with y32 the float32 run
 of the same formulas, and its first term may not exceed 1e-3 max|y64| (``_tol`` asserts it; on the CPU it is at most 1.2e-5 max|y64|
@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import als_implicit_yardstick as I
 import als_yardstick as A
+import click_problem as K
 import wmu_yardstick as WM
 from test_gpu_als import NAMES, SHAPES, U_, V_, Z_, _case, _context, _exact_factor, _f32
 
@@ -62,7 +62,7 @@ def _bg_pattern(lengths, cols, rng):
 def _check_systems(ctx, Rx, Ry, F, which, l2, cx, cy, k, what):
     n = F[which].shape[0]
     H, g = ctx.als_normal(which, 0, n, l2)
-    Hr, gr = I.systems(Rx, Ry, *F, WHICH[which], l2, cx, cy)
+    Hr, gr = A.systems(Rx, Ry, *F, WHICH[which], l2, cx=cx, cy=cy)
     kp = H.shape[1]
     assert (H[:, :k, :k] == Hr).all() and (g[:, :k] == gr).all(), what
     assert all((H[i] == H[i].T).all() for i in range(n)), what
@@ -129,13 +129,13 @@ def _reference(shape, yform, mask, nn, nn_sweeps, cg):
     for w, bit in ((V_, 2), (U_, 1), (Z_, 4)):
         if not mask & bit:
             continue
-        route = (bool(nn & bit), nn_sweeps, cg)
-        ck = key + (w, route, tag)
+        route = dict(non_negative=bool(nn & bit), nn_sweeps=nn_sweeps, cg_steps=cg)
+        ck = key + (w, tuple(route.values()), tag)
         if ck not in store:
-            store[ck] = tuple(I.sweep(*rels, *state[dt], WHICH[w], L2, C0, YFORMS[yform], *route, dtype=dt) for dt in (np.float64, np.float32))
+            store[ck] = tuple(A.sweep(*rels, *state[dt], WHICH[w], L2, cx=C0, cy=YFORMS[yform], **route, dtype=dt) for dt in (np.float64, np.float32))
         state[np.float64][w], state[np.float32][w] = store[ck]
         if w == V_:
-            tag = ("afterV", route)
+            tag = ("afterV", tuple(route.values()))
     return start, state[np.float64], state[np.float32]
 
 
@@ -198,8 +198,8 @@ def test_rows_cut_into_pieces_with_a_background(lib, k):
     X, Y = _f32(rng.randn(m, d)), _f32(rng.randn(d, p))
     F = [_f32(rng.randn(n, k)) for n in (m, d, p)]
     Wx = sp.csr_matrix(W)
-    Hr, gr = I.systems(A.Relation(X, Wx), A.Relation(Y, None), *F, "U", l2, C0, 0)
-    Ha, ga = I.systems(A.Relation(np.abs(X), Wx), A.Relation(Y, None), F[0], np.abs(F[1]), F[2], "U", l2, C0, 0)    # sum |terms|
+    Hr, gr = A.systems(A.Relation(X, Wx), A.Relation(Y, None), *F, "U", l2, cx=C0)
+    Ha, ga = A.systems(A.Relation(np.abs(X), Wx), A.Relation(Y, None), F[0], np.abs(F[1]), F[2], "U", l2, cx=C0)    # sum |terms|
     for piece in (32, 0):
         ctx = _background(_context(lib, X, Y, F, Wx, None, piece=piece), C0, 0)
         lay = ctx.als_layout()
@@ -303,7 +303,7 @@ def test_error_with_a_background(lib, shape):
     pattern_only = ctx.weighted_residual_sq()
     ctx.close()
     for name, rel, Af, Bf, g, po in (("X", A.Relation(X, Wx), F[0], F[1], got[0], pattern_only[0]), ("Y", A.Relation(Y, Wy), F[1], F[2], got[1], pattern_only[1])):
-        ref = I.residual_sq(rel, Af, Bf, C0)
+        ref = A.residual_sq(rel, Af, Bf, C0)
         tol = _error_tol(k, rel, Af, Bf, C0)
         print("%s %s: E %.9g, yardstick %.9g, |err| / tol %.3f (tol / E %.2e); pattern term alone %.9g" % (shape, name, g, ref, abs(g - ref) / tol, tol / ref, po))
         assert abs(g - ref) <= tol and g > po
@@ -428,7 +428,7 @@ def test_background_refusals_leave_the_context_usable(lib):
         ctx.set_factor(w, F[w])
     ctx.als_step(0.1, 0, 7)
     Rx, Ry = A.Relation(X, Ws), A.Relation(Y, None)
-    y64, y32 = (I.step(Rx, Ry, None, None, *F, 0.1, 0.5, 0, dtype=dt) for dt in (np.float64, np.float32))
+    y64, y32 = (A.step(Rx, Ry, None, None, *F, 0.1, cx=0.5, dtype=dt) for dt in (np.float64, np.float32))
     for w in range(3):
         assert np.abs(ctx.get_factor(w) - y64[w]).max() <= _tol(y32[w], y64[w], k)[0]
     ctx.set_background_weight(0, 0)
@@ -445,15 +445,15 @@ _fit = {}
 
 def _click_case():
     if not _fit:
-        counts, train, test, Y, U0, V0, Z0 = I.clicks(7)
-        P, W = I.click_relations(counts, train)
+        counts, train, test, Y, U0, V0, Z0 = K.clicks(7)
+        P, W = K.click_relations(counts, train)
         ones = sp.csr_matrix(train.astype(np.float64))
-        Ur, Vr, Zr, _, _ = I.fit(P, Y, W, None, U0, V0, Z0, 15, 0, 2.0, cx=1.0)
-        Uo, Vo, _, _, _ = I.fit(P, Y, ones, None, U0, V0, Z0, 15, 0, 2.0)
+        Ur, Vr, Zr, _, _ = A.fit(P, Y, W, None, U0, V0, Z0, 15, 2.0, cx=1.0)
+        Uo, Vo, _, _, _ = A.fit(P, Y, ones, None, U0, V0, Z0, 15, 2.0)
         _fit.update(counts=counts, train=train, test=test, Y=Y, start=(U0, V0, Z0), ref=(Ur, Vr, Zr),
-                    err=sum(I.errors(P, Y, W, None, Ur, Vr, Zr, 1.0, 0.0)),
-                    bar=1.3 * max(I.recall_at(Uo @ Vo.T, train, test),
-                                  I.recall_at(np.broadcast_to(train.sum(axis=0)[None].astype(np.float64), train.shape), train, test)))
+                    err=sum(A.errors(P, Y, W, None, Ur, Vr, Zr, cx=1.0)),
+                    bar=1.3 * max(K.recall_at(Uo @ Vo.T, train, test),
+                                  K.recall_at(np.broadcast_to(train.sum(axis=0)[None].astype(np.float64), train.shape), train, test)))
     return _fit
 
 
@@ -491,7 +491,7 @@ def test_fit_on_the_planted_clicks(lib, route):
     U2, V2, Z2 = model.transform(P_new, None, x_entry_weights=W_new, x_background_weight=1.0)
     assert V2.tobytes() == model.components.tobytes() and U2.shape == (10, 8)
     Rx, Ry = A.Relation(P_new, W_new), A.Relation(np.zeros((V2.shape[0], 1)), None)
-    y64, y32 = (I.exact_sweep(Rx, Ry, np.zeros((10, 8)), V2, np.zeros((1, 8)), "U", 2.0, 1.0, 0.0, dtype=dt) for dt in (np.float64, np.float32))
+    y64, y32 = (A.sweep(Rx, Ry, np.zeros((10, 8)), V2, np.zeros((1, 8)), "U", 2.0, cx=1.0, dtype=dt) for dt in (np.float64, np.float32))
     tol, _ = _tol(y32, y64, 8, "fold-in")
     print("fold-in: |err| / tol %.3f" % (np.abs(U2 - y64).max() / tol))
     assert np.abs(U2 - y64).max() <= tol
@@ -503,9 +503,9 @@ def test_fit_with_a_background_stops_at_the_yardsticks_iteration(lib):
     (Seeds 1 .. 8 on the CPU: smallest distances 0.29, 0.17, 0.33, 0.70, 0.30, 0.08, 0.05, 0.84 tol.)"""
     from pycmf_amd import CMF
     tol = 1e-3
-    counts, train, _, Y, U0, V0, Z0 = I.clicks(8)
-    P, W = I.click_relations(counts, train)
-    _, _, _, n_ref, ratios = I.fit(P, Y, W, None, U0, V0, Z0, 200, tol, 2.0, cx=1.0)
+    counts, train, _, Y, U0, V0, Z0 = K.clicks(8)
+    P, W = K.click_relations(counts, train)
+    _, _, _, n_ref, ratios = A.fit(P, Y, W, None, U0, V0, Z0, 200, 2.0, tol=tol, cx=1.0)
     margin = min(abs(r - tol) for r in ratios) / tol
     assert margin >= 0.3 and n_ref == 30, (n_ref, ratios)
     model = CMF(n_components=8, solver="als", l2_reg=2.0, max_iter=200, tol=tol, x_init="custom", y_init="custom", **SIGNED)

@@ -1,5 +1,5 @@
 """The non-negative row solve of the ALS solver on the device (cmf_als_nnls_rows, cmf_als_nnls_step, CMF(als_nn_sweeps=n)) against
-the float64 yardstick of als_nnls_yardstick.py on float32-rounded inputs.  Tolerance per factor (als_yardstick.tolerance, the HALS
+the float64 yardstick of als_yardstick.py on float32-rounded inputs.  Tolerance per factor (als_yardstick.tolerance, the HALS
 rule): tol = max(4 max|y32 - y64|, (k + 16) 2^-24 max|y64|) with y32 the float32 run of the same formulas.
 
 Measured on an MI355X (worst |err| / tol of each group): see DESIGN section 16."""
@@ -7,7 +7,6 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import als_nnls_yardstick as N
 import als_yardstick as A
 from test_gpu_als import SHAPES, _case, _context, _f32
 from test_gpu_wmu import fit_inputs
@@ -71,7 +70,7 @@ def test_exact_systems_are_swept_exactly(lib, k):
     ctx, kp = _rows_context(lib, k)
     Hp, gp, fp = _padded(H, g, F, kp)
     for sweeps in (1, 3):
-        ref = N.cd_rows(H, g, F, sweeps)
+        ref = A.cd_rows(H, g, F, sweeps)
         assert np.abs(ref * 16 - np.round(ref * 16)).max() == 0 and (ref == 0).any() and (ref > 0).any() and (ref != F).any()
         got = ctx.als_nnls_rows(Hp, gp, fp, sweeps)
         assert (got[:, :k] == ref).all(), "k %d, %d sweeps: %d of %d coordinates differ" % (k, sweeps, int((got[:, :k] != ref).sum()), ref.size)
@@ -102,7 +101,7 @@ def test_random_systems_against_the_yardstick(lib, k):
     Hp, gp, fp = _padded(H, g, F, kp)
     worst = 0.0
     for sweeps in (1, 4, 16):
-        y64, y32 = N.cd_rows(H, g, F, sweeps), N.cd_rows(H, g, F, sweeps, dtype=np.float32)
+        y64, y32 = A.cd_rows(H, g, F, sweeps), A.cd_rows(H, g, F, sweeps, dtype=np.float32)
         full = None
         for n in (70, 5, 1):
             got = ctx.als_nnls_rows(Hp[:n], gp[:n], fp[:n], sweeps)
@@ -139,8 +138,8 @@ def _reference(shape, yform, mask, nn, sweeps):
     if key not in _refs:
         X, Y, Wx, Wy, F = _start(shape, yform, nn)
         Rx, Ry = A.Relation(X, Wx), A.Relation(Y, Wy)
-        _refs[key] = (N.step(Rx, Ry, None, None, *F, L2, sweeps, mask, nn), N.step(Rx, Ry, None, None, *F, L2, sweeps, mask, nn, dtype=np.float32),
-                      [N.no_information(Rx, Ry, *F, w) for w in NAMES])
+        _refs[key] = tuple(A.step(Rx, Ry, None, None, *F, L2, mask=mask, nn_mask=nn, nn_sweeps=sweeps, dtype=dt) for dt in (np.float64, np.float32)) + (
+            [A.no_information(Rx, Ry, *F, w) for w in NAMES],)
     return _refs[key]
 
 
@@ -262,7 +261,7 @@ def test_unweighted_non_negative_step_is_repeated_hals_sweeps(lib):
     F = [_f32(np.abs(rng.randn(n, k))) for n in (m, d, p)]
     ctx = _context(lib, X, Y, F, None, None)
     ctx.als_nnls_step(L2, 7, 7, 3)
-    y64, y32 = N.step(X, Y, None, None, *F, L2, 3), N.step(X, Y, None, None, *F, L2, 3, dtype=np.float32)
+    y64, y32 = (A.step(X, Y, None, None, *F, L2, nn_mask=7, nn_sweeps=3, dtype=dt) for dt in (np.float64, np.float32))
     for w in range(3):
         got = ctx.get_factor(w)
         assert (got >= 0).all() and np.abs(got - y64[w]).max() <= A.tolerance(y32[w], y64[w], k)
@@ -316,7 +315,7 @@ def test_fit_matches_the_float64_yardstick_and_beats_mu(lib):
     kw = dict(n_components=3, l2_reg=l2, tol=0, x_init="custom", y_init="custom")
     model = CMF(solver="als", als_nn_sweeps=4, max_iter=iters, **kw)
     Ug, Vg, Zg = model.fit_transform(Xi, Y, U=U.copy(), V=V.copy(), Z=Z.copy(), x_entry_weights="observed")
-    Ur, Vr, Zr = N.fit(X, Y, Wref, None, U, V, Z, iters, l2, 4)
+    Ur, Vr, Zr = A.fit(X, Y, Wref, None, U, V, Z, iters, l2, nn_mask=7, nn_sweeps=4)[:3]
     ref = sum(A.errors(X, Y, Wref, None, Ur, Vr, Zr))
     print("fit: reconstruction_err_ %.9g, yardstick %.9g, relative %.2e" % (model.reconstruction_err_, ref, abs(model.reconstruction_err_ - ref) / ref))
     assert model.n_iter_ == iters and abs(model.reconstruction_err_ - ref) <= 1e-4 * ref
