@@ -116,7 +116,11 @@ int cmf_sync(cmf_ctx *ctx);
  * "kl_split" n: the dense passes of cmf_mu_kl_step / cmf_kl_divergence cut the streamed dimension into n shares (<= 0, default:
  * enough to give every CU a workgroup); another n regroups the float32 sums,
  * "als_piece" n: stored entries per piece of a row in the normal-equation kernel of cmf_als_step (<= 0, default: 4096; rounded up
- * to a multiple of 32); another n regroups the float32 sums                                                                */
+ * to a multiple of 32); another n regroups the float32 sums,
+ * "als_cg_piece" n: stored entries per piece of a LONG row of cmf_als_cg_step -- a row with more than n stored entries (both
+ * sides of a V sweep counted together) is cut into pieces of n, each summed by a workgroup of its own (n > 0: rounded up to a
+ * multiple of 16; 0, default: 2048; n < 0: no row is ever cut, every row is walked by one workgroup); another n regroups the
+ * float32 sums of the rows longer than the smaller of the two                                                                */
 int cmf_set_option(cmf_ctx *ctx, const char *name, int64_t value);
 
 /* ---- problem ---------------------------------------------------------- */
@@ -339,8 +343,15 @@ int cmf_hals_sweep(cmf_ctx *ctx, int which, const double *N, const double *G, do
  * (nn_sweeps 1 .. 1024, as cmf_als_nnls_step); a sweep whose relations are all full takes the shared float64 inverse.
  * Validation as cmf_als_step, and CMF_EINVAL for cg_steps outside 1 .. 1024 or nn_sweeps outside 0 .. 1024.  Kernel time: class
  * CMF_K_ROWHESS, 4 nnz k (cg_steps + 1) flops, plus 2 rows k^2 (cg_steps + 1) with a full side.
+ * LONG ROWS (the hot columns of click, play and bag-of-words data in the V sweep): a row with more than L stored entries (option
+ * "als_cg_piece", default 2048) is not walked by one workgroup.  Its entries, side 0 then side 1 in stored order, are cut into
+ * pieces of L; per product H x one launch sums every piece in a workgroup of its own and a second one adds a row's pieces in piece
+ * order and takes the CG step, all long rows of the sweep together: 2 (cg_steps + 1) launches, no atomics, the same formulas and
+ * stop rule.  The result of such a row depends on the row and on L alone; shorter rows keep the single launch and its bits.
  *   cmf_als_cg_rows (tests): host_f[nrows x k_pad] = the rows the CG route would write for rows [row0, row0 + nrows) of the sweep
- *   of factor `which`, from the current factors, which are left unchanged.  CMF_EINVAL for a sweep without an observed relation. */
+ *   of factor `which`, from the current factors, which are left unchanged.  CMF_EINVAL for a sweep without an observed relation.
+ *   cmf_als_cg_last (tests, read-only): out2[0] = the long rows, out2[1] = their pieces in the last sweep of the CG route
+ *   (cmf_als_cg_step or cmf_als_cg_rows) of this context; zeros before the first one.  CMF_EINVAL for a null pointer.          */
 int cmf_als_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask);
 int cmf_als_normal(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, double l2, float *host_H, float *host_g);
 int cmf_als_layout(cmf_ctx *ctx, int64_t *out4);
@@ -348,6 +359,7 @@ int cmf_als_nnls_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask, int
 int cmf_als_nnls_rows(cmf_ctx *ctx, int64_t nrows, const float *host_H, const float *host_g, float *host_f, int sweeps);
 int cmf_als_cg_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask, int cg_steps, int nn_sweeps);
 int cmf_als_cg_rows(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, double l2, int cg_steps, float *host_f);
+int cmf_als_cg_last(cmf_ctx *ctx, int64_t *out2);
 
 /* ---- ALS for implicit feedback: a background weight on the cells outside the pattern ----------------------------------------
  * Clicks, plays, purchases: every stored target is 1, so a fit over the pattern alone is degenerate, and a fit with every cell at

@@ -81,6 +81,7 @@ PROTOTYPES = {
     "cmf_als_nnls_rows": [_vp, _i64, _pf, _pf, _pf, _i32],
     "cmf_als_cg_step": [_vp, _dbl, _i32, _i32, _i32, _i32],
     "cmf_als_cg_rows": [_vp, _i32, _i64, _i64, _dbl, _i32, _pf],
+    "cmf_als_cg_last": [_vp, _pi64],
     "cmf_set_background_weight": [_vp, _i32, _dbl],
     "cmf_get_background_weight": [_vp, _i32, _pd],
     "cmf_als_residual_sq": [_vp, _pd, _pd],
@@ -587,6 +588,13 @@ class Context:
         out = np.zeros((max(nrows, 0), kp), dtype=np.float32)
         check(self._lib.cmf_als_cg_rows(self._h, which, row0, nrows, l2, cg_steps, out.ctypes.data_as(_pf)))
         return out
+
+    def als_cg_last(self):
+        """(long rows, pieces) of the last sweep of the CG route (``als_cg_step`` or ``als_cg_rows``): the rows longer than option
+        ``"als_cg_piece"`` entries, which were cut into that many pieces.  Read-only; for the tests."""
+        out = np.zeros(2, dtype=np.int64)
+        check(self._lib.cmf_als_cg_last(self._h, out.ctypes.data_as(_pi64)))
+        return int(out[0]), int(out[1])
 
     # ---- ALS for implicit feedback (csrc/cmf_als_bg.hip.h)
     def set_background_weight(self, which, c0):

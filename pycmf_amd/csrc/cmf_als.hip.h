@@ -19,7 +19,9 @@
 //                                                                      cyclic coordinate descent from the current rows, in place
 //   rows CG       observed; signed, cg_steps > 0                       no systems: als_cg_kernel (cmf_als_cg.hip.h) runs matrix-free
 //                                                                      CG steps per row from the current rows, in place; the host
-//                                                                      sorts the rows into LDS capacity classes by length
+//                                                                      sorts the rows into LDS capacity classes by length; a row
+//                                                                      longer than "als_cg_piece" entries is cut into pieces
+//                                                                      (als_cg_piece_kernel / als_cg_combine_kernel)
 //
 // The finished systems (als_chunks).  als_normal_kernel<KP>: one 512-thread workgroup per PIECE of a row (at most `als_piece` stored
 // entries, a multiple of 32) of a CSR image (indptr, idx, pv = w t, wv = w).  The gathered rows b_e are staged 32 at a time through
@@ -569,10 +571,30 @@ static int als_cg_launch(cmf_ctx *c, const cmfk::AlsCgArgs &a, int64_t nrows) {
     return CMF_OK;
 }
 
+enum { ALS_CG_PIECE_DEFAULT = 2048 };   // the fastest of 2048, 4096, 16384 and 65536 on the V sweep of C5 Zipf at k = 256
+// entries per piece of a long row of the CG route ("als_cg_piece": > 0 rounded up to 16; 0 the default; < 0 no row is ever cut)
+static int64_t als_cg_piece_len(const cmf_ctx *c) {
+    if (c->opt_als_cg_piece < 0) return INT64_MAX;
+    return c->opt_als_cg_piece > 0 ? rup(c->opt_als_cg_piece, 16) : (int64_t)ALS_CG_PIECE_DEFAULT;
+}
+
+// the long rows of a sweep: 2 (steps + 1) launches, pieces then combine, once for r = g - H f and once per step
+static int als_cg_long_rows(cmf_ctx *c, cmfk::AlsCgPieceArgs &a, int64_t nlong, int64_t npieces, int steps) {
+    if (nlong <= 0) return CMF_OK;
+    const dim3 pgrid((unsigned)npieces), cgrid((unsigned)nlong), block(256);
+    for (int s = 0; s <= steps; ++s) {
+        a.phase = s == 0 ? 0 : (s == steps ? 2 : 1);
+        ALS_LAUNCH_KP(c, als_cg_piece_kernel, "the conjugate-gradient row solve is", hipLaunchKernelGGL(kern, pgrid, block, 0, c->stream, a));
+        ALS_LAUNCH_KP(c, als_cg_combine_kernel, "the conjugate-gradient row solve is", hipLaunchKernelGGL(kern, cgrid, block, 0, c->stream, a));
+    }
+    return CMF_OK;
+}
+
 // rows CG: rows [r_begin, r_end) of the sweep (which has an observed relation) by `steps` CG steps from the rows of c->F[f];
 // row r goes to Fout + (r - out_row0) * k_pad (in place: Fout = c->F[f], out_row0 = 0 -- the gathered factors are the other ones).
 // The rows are sorted into capacity classes by their stored entries: capacity / 8, / 4, / 2 and the whole capacity keep the
-// gathered rows in LDS (shorter rows: more workgroups per CU), longer rows stream; one launch per class.
+// gathered rows in LDS (shorter rows: more workgroups per CU), longer rows stream; one launch per class.  A row with more than
+// als_cg_piece_len entries goes to none of them: it is cut into pieces (cmf_als_cg.hip.h), all such rows of the sweep together.
 static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin, int64_t r_end, int steps, float *Fout, int64_t out_row0) {
     using namespace cmfk;
     const int kp = c->kp;
@@ -590,30 +612,65 @@ static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begi
     int64_t caps[ALS_CG_CLASSES + 1];
     for (int q = 0; q < ALS_CG_CLASSES; ++q) caps[q] = cap_max >> (ALS_CG_CLASSES - 1 - q);
     caps[ALS_CG_CLASSES] = 0;                                   // the streamed class
+    const int64_t L = als_cg_piece_len(c);
     std::vector<int64_t> list[ALS_CG_CLASSES + 1];
+    std::vector<AlsCgLongRow> longs;
+    std::vector<AlsCgPiece> pieces;
     int64_t nnz = 0;
     for (int64_t r = 0; r < nrows; ++r) {
         int64_t len = 0;
         for (int s = 0; s < sw.nobs; ++s) len += ip[s][(size_t)r + 1] - ip[s][(size_t)r];
         if (len > INT32_MAX) return fail(CMF_EUNSUPPORTED, "cmf_als_cg_step: a row with more than 2^31 - 1 stored entries");
         nnz += len;
+        if (len > L) {
+            const int64_t np = (len + L - 1) / L;
+            if ((int64_t)pieces.size() + np > INT32_MAX) return fail(CMF_EUNSUPPORTED, "cmf_als_cg_step: more than 2^31 - 1 pieces of long rows (als_cg_piece too small)");
+            const int32_t slot = (int32_t)longs.size();
+            longs.push_back(AlsCgLongRow{r_begin + r, (int32_t)pieces.size(), (int32_t)np});
+            for (int64_t q = 0; q < len; q += L) pieces.push_back(AlsCgPiece{slot, (int32_t)q, (int32_t)std::min(L, len - q), 0});
+            continue;
+        }
         int q = 0;
         while (q < ALS_CG_CLASSES && len > caps[q]) ++q;
         list[q].push_back(r_begin + r);
     }
+    c->als_cg_last[0] = (int64_t)longs.size();
+    c->als_cg_last[1] = (int64_t)pieces.size();
     std::vector<int64_t> all;
     all.reserve((size_t)nrows);
     for (int q = 0; q <= ALS_CG_CLASSES; ++q) all.insert(all.end(), list[q].begin(), list[q].end());
-    CHK(kl_ensure(c, c->als_desc, std::max<size_t>(16, all.size() * sizeof(int64_t))));
+    // descriptors, once per sweep: the rows of the class launches | the long rows | their pieces
+    const size_t rbytes = std::max<size_t>(16, all.size() * sizeof(int64_t)), lbytes = longs.size() * sizeof(AlsCgLongRow);
+    CHK(kl_ensure(c, c->als_desc, rbytes + lbytes + pieces.size() * sizeof(AlsCgPiece)));
     int64_t *drows = (int64_t *)c->als_desc.p;
+    AlsCgLongRow *dlongs = (AlsCgLongRow *)((char *)c->als_desc.p + rbytes);
+    AlsCgPiece *dpieces = (AlsCgPiece *)((char *)dlongs + lbytes);
     if (!all.empty()) HIPCHK(hipMemcpyAsync(drows, all.data(), all.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream)); // the host vector may go
+    if (!longs.empty()) {
+        HIPCHK(hipMemcpyAsync(dlongs, longs.data(), lbytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dpieces, pieces.data(), pieces.size() * sizeof(AlsCgPiece), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream)); // the host vectors may go
     a.Fin = c->F[sw.f];
     a.Fout = Fout;
     a.out_row0 = out_row0;
     a.l2 = (float)l2;
     a.k = c->k;
     a.steps = steps;
+    AlsCgPieceArgs pa;
+    memset(&pa, 0, sizeof pa);
+    if (!longs.empty()) {   // scratch of the long rows: state [3][k_pad] per row | partials [k_pad] per piece | r.r | alive flags
+        const size_t nl = longs.size(), sfloats = (3 * nl + pieces.size()) * (size_t)kp;
+        CHK(kl_ensure(c, c->als_cg_long, (sfloats + 2 * nl) * sizeof(float)));
+        pa.s0 = a.s0; pa.s1 = a.s1;
+        pa.pieces = dpieces; pa.rows = dlongs;
+        pa.S = a.S; pa.N = a.N; pa.Fin = a.Fin; pa.Fout = Fout; pa.out_row0 = out_row0;
+        pa.state = (float *)c->als_cg_long.p;
+        pa.partial = pa.state + 3 * nl * (size_t)kp;
+        pa.rr = pa.state + sfloats;
+        pa.alive = (int32_t *)(pa.rr + nl);
+        pa.l2 = a.l2; pa.k = a.k;
+    }
     Timed tm(c, CMF_K_ROWHESS, (4.0 * (double)nnz * c->k + (a.S ? 2.0 * (double)nrows * c->k * c->k : 0.0)) * (steps + 1));
     int64_t done = 0;
     for (int q = 0; q <= ALS_CG_CLASSES; ++q) {
@@ -622,7 +679,7 @@ static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begi
         CHK(als_cg_launch(c, a, (int64_t)list[q].size()));
         done += (int64_t)list[q].size();
     }
-    return CMF_OK;
+    return als_cg_long_rows(c, pa, (int64_t)longs.size(), (int64_t)pieces.size(), steps);
 }
 
 // sweeps == 0: the solved rows of the factors in nn_mask are projected; sweeps > 0: those factors are swept by coordinate descent;
@@ -695,6 +752,14 @@ extern "C" int cmf_als_cg_rows(cmf_ctx *c, int which, int64_t row0, int64_t nrow
     CHK(als_cg_rows(c, sw, l2, row0, row0 + nrows, cg_steps, (float *)c->als_cg_ws.p, row0));
     HIPCHK(hipMemcpyAsync(host_f, c->als_cg_ws.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return CMF_OK;
+}
+
+// test entry: the long rows and the pieces of the last CG sweep (or cmf_als_cg_rows call)
+extern "C" int cmf_als_cg_last(cmf_ctx *c, int64_t *out2) {
+    if (!c || !out2) return fail(CMF_EINVAL, "cmf_als_cg_last: null context or output");
+    out2[0] = c->als_cg_last[0];
+    out2[1] = c->als_cg_last[1];
     return CMF_OK;
 }
 

@@ -22,6 +22,22 @@
 //     longer one gathers them again every pass.  Both forms run the same arithmetic in the same order on the same values, so the
 //     capacity class the host sorts a row into changes no bit of its result.
 // Vector stores only; no scratch.
+//
+// Long rows (hot columns): a row with more than L stored entries ("als_cg_piece") leaves that kernel.  Its entries, side 0 then
+// side 1 in stored order, are cut into pieces of L consecutive entries (the last one shorter; a piece may straddle the two sides),
+// and one product H x becomes two plain launches, all long rows of the sweep together:
+//   als_cg_piece_kernel<KP>    one 256-thread workgroup per piece: the inner loop of `pass` over the piece's entries (wave e mod 4
+//                              takes entry e of the piece, four in flight, b_e in registers, the butterfly dot, acc += coef b_e),
+//                              the four wave accumulators added in wave order, the piece's partial [KP] to its own slot.  x comes
+//                              from the row's state (f in the first pass, p afterwards), each lane its KP / 64 floats straight into
+//                              registers.  Pieces always stream; 4 KP floats of static LDS.  A piece of a row that has stopped
+//                              returns at once.
+//   als_cg_combine_kernel<KP>  one workgroup per long row: thread j < KP adds the row's partials in piece order, then (S x)_j for c
+//                              ascending and l2 x_j as `pass` does; the first launch forms r = g - H f (+ N), p = r, r.r, the later
+//                              ones one CG step each with the formulas and the stop rule above; the last one writes f.
+// The sum across workgroups is the kernel boundary: no atomics, no grid barrier, no workgroup waits for another.  The state
+// (f, r, p [KP], r.r and an alive flag per long row) and the partials live in a scratch buffer of their own.  A long row's result
+// depends on that row and on L alone.
 #pragma once
 #include "cmf_kernels.hip.h"
 
@@ -201,6 +217,184 @@ __global__ __launch_bounds__(256) void als_cg_kernel(AlsCgArgs g) {
         rr = rn;
     }
     if (t < k) out[t] = f;
+}
+
+// ------------------------------------------------------------------ long rows, cut into pieces
+struct AlsCgPiece {
+    int32_t slot;           // the long row (index into AlsCgPieceArgs::rows) this piece belongs to
+    int32_t first, count;   // entries [first, first + count) of the row, side 0 then side 1 concatenated
+    int32_t pad;
+};
+struct AlsCgLongRow {
+    int64_t row;            // of the swept factor
+    int32_t first, pieces;  // its partial slots [first, first + pieces)
+};
+struct AlsCgPieceArgs {
+    AlsCgSide s0, s1;       // s1.indptr == nullptr: one side
+    const AlsCgPiece *pieces;
+    const AlsCgLongRow *rows;
+    const float *S, *N, *Fin;
+    float *Fout;
+    int64_t out_row0;
+    float *state;           // [long row][3][KP]: f, r, p
+    float *rr;              // [long row]
+    int32_t *alive;         // [long row]
+    float *partial;         // [piece][KP]
+    float l2;
+    int k;
+    int phase;              // 0: the first pass / its combine; 1: a step; 2: the last step (f goes to Fout)
+};
+
+__device__ __forceinline__ bool als_cg_positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
+
+template <int KP>
+__global__ __launch_bounds__(256) void als_cg_piece_kernel(AlsCgPieceArgs g) {
+    constexpr int VPL = KP >= 64 ? KP / 64 : 1;
+    __shared__ __attribute__((aligned(16))) float part[4 * KP];
+    const int t = threadIdx.x, lane = t & 63;
+    const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
+    const bool holds = lane * VPL < KP;
+    const AlsCgPiece pc = g.pieces[blockIdx.x];
+    const bool first = g.phase == 0;
+    if (!first && !g.alive[pc.slot]) return;            // workgroup-uniform
+    const int64_t row = g.rows[pc.slot].row;
+    const int64_t b0 = g.s0.indptr[row], b1 = g.s1.indptr ? g.s1.indptr[row] : 0;
+    const int n0 = (int)(g.s0.indptr[row + 1] - b0);
+    const float *x = first ? g.Fin + row * KP : g.state + ((int64_t)pc.slot * 3 + 2) * KP;
+    float xr[VPL], acc[VPL];
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+        xr[v] = holds ? x[lane * VPL + v] : 0.f;
+        acc[v] = 0.f;
+    }
+    const int n = pc.count;
+    for (int e0 = uw; e0 < n; e0 += 4 * ALS_CG_U) {
+        float b[ALS_CG_U][VPL], w[ALS_CG_U], pv[ALS_CG_U];
+#pragma unroll
+        for (int u = 0; u < ALS_CG_U; ++u) {
+            const int e = e0 + 4 * u;                    // wave-uniform
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) b[u][v] = 0.f;
+            w[u] = pv[u] = 0.f;
+            if (e >= n) continue;
+            const int ge = pc.first + e;                 // entry of the row
+            const bool second = ge >= n0;
+            const int64_t q = second ? b1 + (ge - n0) : b0 + ge;
+            w[u] = (second ? g.s1.wv : g.s0.wv)[q];
+            if (first) pv[u] = (second ? g.s1.pv : g.s0.pv)[q];
+            if (holds) {
+                const float *src = (second ? g.s1.B : g.s0.B) + (int64_t)(second ? g.s1.idx : g.s0.idx)[q] * KP + lane * VPL;
+                if constexpr (VPL == 4) {
+                    const f32x4 x4 = *reinterpret_cast<const f32x4 *>(src);
+                    b[u][0] = x4[0]; b[u][1] = x4[1]; b[u][2] = x4[2]; b[u][3] = x4[3];
+                } else if constexpr (VPL == 2) {
+                    const float2 x2 = *reinterpret_cast<const float2 *>(src);
+                    b[u][0] = x2.x; b[u][1] = x2.y;
+                } else {
+                    b[u][0] = src[0];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < ALS_CG_U; ++u) {
+            float d = 0.f;
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) d = fmaf(b[u][v], xr[v], d);
+            d = als_cg_wave_sum(d);
+            const float coef = first ? pv[u] - w[u] * d : w[u] * d;
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) acc[v] = fmaf(coef, b[u][v], acc[v]);
+        }
+    }
+    if (holds) {
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) part[uw * KP + lane * VPL + v] = acc[v];
+    }
+    __syncthreads();
+    if (t < KP) g.partial[(int64_t)blockIdx.x * KP + t] = ((part[t] + part[KP + t]) + part[2 * KP + t]) + part[3 * KP + t];
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void als_cg_combine_kernel(AlsCgPieceArgs g) {
+    __shared__ float xs[KP], wsum[8];
+    const int t = threadIdx.x, lane = t & 63;
+    const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int slot = blockIdx.x, k = g.k;
+    const AlsCgLongRow lr = g.rows[slot];
+    float *st = g.state + (int64_t)slot * 3 * KP;
+    float *out = g.Fout + (lr.row - g.out_row0) * KP;
+    const bool first = g.phase == 0, last = g.phase == 2;
+    if (!first && !g.alive[slot]) {                      // stopped earlier: the row keeps what it has
+        if (last && t < k) out[t] = st[t];
+        return;
+    }
+    auto dot = [&](float v, int s) -> float {            // as in als_cg_kernel
+        v = als_cg_wave_sum(v);
+        if (lane == 0) wsum[4 * s + uw] = v;
+        __syncthreads();
+        return ((wsum[4 * s] + wsum[4 * s + 1]) + wsum[4 * s + 2]) + wsum[4 * s + 3];
+    };
+    float f = 0.f, r = 0.f, p = 0.f, o = 0.f;
+    if (t < KP) {
+        f = first ? g.Fin[lr.row * KP + t] : st[t];
+        if (!first) {
+            r = st[KP + t];
+            p = st[2 * KP + t];
+        }
+        xs[t] = first ? f : p;
+    }
+    __syncthreads();
+    if (t < KP) {
+        const float *pp = g.partial + (int64_t)lr.first * KP + t;
+        for (int q = 0; q < lr.pieces; ++q) o += pp[(int64_t)q * KP];
+        float sx = 0.f;
+        if (g.S) {
+            for (int c = 0; c < k; ++c) sx = fmaf(g.S[c * KP + t], xs[c], sx);
+        }
+        if (t < k) sx += g.l2 * xs[t];
+        o = first ? o - sx : o + sx;
+    }
+    if (first) {
+        r = o;
+        if (t < KP && g.N) r += g.N[lr.row * KP + t];
+        const float rr = dot(r * r, 0);
+        if (t < KP) {
+            st[t] = f;
+            st[KP + t] = r;
+            st[2 * KP + t] = r;
+        }
+        if (t == 0) {
+            g.rr[slot] = rr;
+            g.alive[slot] = als_cg_positive_finite(rr) ? 1 : 0;
+        }
+        return;
+    }
+    const float rr = g.rr[slot];
+    const float pq = dot(p * o, 1);
+    if (!als_cg_positive_finite(pq)) {
+        if (t == 0) g.alive[slot] = 0;
+        if (last && t < k) out[t] = f;
+        return;
+    }
+    const float alpha = rr / pq;
+    f = fmaf(alpha, p, f);
+    r = fmaf(-alpha, o, r);
+    const float rn = dot(r * r, 0);
+    const float beta = rn / rr;
+    p = fmaf(beta, p, r);
+    if (last) {
+        if (t < k) out[t] = f;
+        return;
+    }
+    if (t < KP) {
+        st[t] = f;
+        st[KP + t] = r;
+        st[2 * KP + t] = p;
+    }
+    if (t == 0) {
+        g.rr[slot] = rn;
+        g.alive[slot] = als_cg_positive_finite(rn) ? 1 : 0;
+    }
 }
 
 } // namespace cmfk

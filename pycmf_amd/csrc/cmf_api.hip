@@ -146,6 +146,9 @@ struct cmf_ctx {
     DevBuf als_nnls_ws;                   // cmf_als_nnls_rows (test entry): the caller's systems and rows
     int opt_als_cg_lds = -1;              // CG row solves (cmf_als_cg.hip.h): most bytes of LDS a row's gathered rows may take (< 0: the default, a quarter of the LDS; 0: every row streams)
     DevBuf als_cg_ws;                     // cmf_als_cg_rows (test entry): the rows it returns
+    int opt_als_cg_piece = 0;             // ... stored entries per piece of a long row (rows with more are cut; 0: the default, 2048; > 0 rounded up to 16; < 0: no row is cut)
+    DevBuf als_cg_long;                   // ... the long rows' state (f, r, p, r.r, alive) and the partial sums of their pieces
+    int64_t als_cg_last[2] = {0, 0};      // long rows and pieces of the last CG sweep (cmf_als_cg_last, tests)
     double wm_bg[2] = {0.0, 0.0};         // background weight c0 of X / Y on the cells outside a CSR pattern (cmf_als_bg.hip.h; 0: none)
     DevBuf als_bg_s, als_bg64;            // ... the shared matrix sum coef Gram of a sweep; float64 Grams of the error's trace term
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
@@ -758,6 +761,7 @@ static void release_problem(cmf_ctx *c) {
     c->wm_slab = DevBuf(); c->wm_small = DevBuf(); c->wm_part = DevBuf();
     c->hals_ws = DevBuf();
     c->als_h = DevBuf(); c->als_part = DevBuf(); c->als_g = DevBuf(); c->als_sol = DevBuf(); c->als_desc = DevBuf(); c->als_nnls_ws = DevBuf(); c->als_cg_ws = DevBuf();
+    c->als_cg_long = DevBuf(); c->als_cg_last[0] = c->als_cg_last[1] = 0;
     c->als_bg_s = DevBuf(); c->als_bg64 = DevBuf();
     for (int w = 0; w < 2; ++w) {
         c->wm_bg[w] = 0.0;
@@ -916,6 +920,8 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
         c->opt_als_piece = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "als_cg_lds")) {
         c->opt_als_cg_lds = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20));
+    } else if (!strcmp(name, "als_cg_piece")) {
+        c->opt_als_cg_piece = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 30));
     } else if (!strcmp(name, "topk_split")) {
         c->opt_topk_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "sparse_mode")) {
