@@ -83,6 +83,9 @@ int cmf_ctx_create(cmf_ctx **out, int device, void *stream);
 int cmf_ctx_destroy(cmf_ctx *ctx);
 int cmf_sync(cmf_ctx *ctx);
 /* tuning knobs (A/B measurements in one process): "gemm_split" n = force the split-K factor (<= 0: heuristic),
+ * "data_pass_wg" bits: the fp32 data passes with a 256-wide factor (k_pad = 256) run on the 256-thread workgroup with 128 x 128
+ * wave tiles (cmf_gemm_wg256.hip.h) -- bit 0 the TN form (X^T U, Y^T V: X feeds the MFMAs from registers), bit 1 the NN form
+ * (X V, Y Z); 3 (default) both, 0 both on the 512-thread kernel.  Same accumulation order: the results do not depend on it, bit for bit,
  * "sparse_mode" 0 auto | 1 dense | 2 native CSR (set before cmf_set_data_csr),
  * "row_kernel" 1 fused gather kernel | 0 masked-dense GEMMs for per-row Newton sweeps,
  * "z_logit_hessian_l2" 1 (live Python path, cmf_solvers.py:505-506) | 0 (Cython twin,

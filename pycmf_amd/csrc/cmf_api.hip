@@ -3,6 +3,7 @@
 // (reference: pycmf/cmf_solvers.py:248-263 MU, :510-522 Newton, :36-42 error).
 #include "../../include/cmfhip.h"
 #include "cmf_kernels.hip.h"
+#include "cmf_gemm_wg256.hip.h"
 #include "cmf_gemm_pair.hip.h"
 #include "cmf_eigen.hip.h"
 #include "cmf_chol_mfma.hip.h"
@@ -126,6 +127,7 @@ struct cmf_ctx {
                            // only (single steps measured neutral: the ~4 us per dependent kernel boundary is device-side)
     StepGraph mu_graph, newton_graph;
     int opt_split = -1;    // force split-K factor (<=0: heuristic)
+    int opt_data_pass_wg = 3; // BN = 256 data passes on the 256-thread workgroup of cmf_gemm_wg256.hip.h: bit 0 the TN form, bit 1 the NN form (same bits out; C4: 62.22 -> 60.78 ms per iteration)
     int opt_pair = 1;      // k_pad = 128, dense X and Y: the two data passes of an MU half-iteration as one balanced launch (cmf_gemm_pair.hip.h) | 0: two split launches
     int opt_arith_min_tiles = 8;   // ... only for operands of at least this many 256-row tiles
     int opt_arith = 0;     // data passes at k_pad = 256: 0 fp32 MFMA | 1 bf16x6 (three bf16 planes per operand, fp32-equivalent)
@@ -411,6 +413,15 @@ template <int MODE, int ROLE>
 static int launch_gemm(cmf_ctx *c, const GemmArgs &a, const GemmPlan &pl) {
     static_assert(MODE != MODE_NT, "NT passes: gemm_nt");
     dim3 grid((unsigned)pl.tiles_m, (unsigned)pl.ntiles_n, (unsigned)pl.nsplit);
+    if (ROLE == 0 && pl.bn == 256 && (c->opt_data_pass_wg & (MODE == MODE_TN ? 1 : 2)) && a.epi == EPI_NONE && a.Mout % 256 == 0) {
+        // four waves, 128 x 128 wave tiles, the TN form's X straight from global memory (cmf_gemm_wg256.hip.h): whole 256-row
+        // tiles only (X, Y and their images are padded to 256); every split-K slab has at least one K-step (plan_gemm)
+        using Cfg = Wg256Cfg<MODE>;
+        CHK(allow_big_lds(c, reinterpret_cast<const void *>(&gemm_wg256_kernel<MODE>), (int)Cfg::LDS_BYTES));
+        hipLaunchKernelGGL((gemm_wg256_kernel<MODE>), grid, dim3(Cfg::NT), Cfg::LDS_BYTES, c->stream, a);
+        HIPCHK(hipGetLastError());
+        return CMF_OK;
+    }
     dim3 block(512);
 #define CMF_LAUNCH(BN_)                                                                          \
     do {                                                                                         \
@@ -816,6 +827,9 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
         c->opt_pipe_nt = (int)value;
     } else if (!strcmp(name, "gemm_split")) {
         c->opt_split = (int)value;
+    } else if (!strcmp(name, "data_pass_wg")) {
+        if (value < 0 || value > 3) return fail(CMF_EINVAL, "data_pass_wg: bit 0 the TN data passes, bit 1 the NN data passes (0..3)");
+        c->opt_data_pass_wg = (int)value;
     } else if (!strcmp(name, "small_gram_shares")) {
         c->opt_gram32_shares = (int)std::max<int64_t>(1, std::min<int64_t>(value, 1024));
     } else if (!strcmp(name, "small_gram")) {
