@@ -85,7 +85,9 @@ int cmf_sync(cmf_ctx *ctx);
 /* tuning knobs (A/B measurements in one process): "gemm_split" n = force the split-K factor (<= 0: heuristic),
  * "data_pass_wg" bits: the fp32 data passes with a 256-wide factor (k_pad = 256) run on the 256-thread workgroup with 128 x 128
  * wave tiles (cmf_gemm_wg256.hip.h) -- bit 0 the TN form (X^T U, Y^T V: X feeds the MFMAs from registers), bit 1 the NN form
- * (X V, Y Z); 3 (default) both, 0 both on the 512-thread kernel.  Same accumulation order: the results do not depend on it, bit for bit,
+ * (X V, Y Z); 3 both, 0 both on the 512-thread kernel; bit 2 (acts with bit 0) the TN form takes the factor from a second register
+ * ring as well: no LDS, no barrier; bit 3 (acts with bit 1) the NN form does, X alone stays in LDS.  15 (default): all of them.
+ * Same accumulation order: the results do not depend on it, bit for bit,
  * "sparse_mode" 0 auto | 1 dense | 2 native CSR (set before cmf_set_data_csr),
  * "row_kernel" 1 fused gather kernel | 0 masked-dense GEMMs for per-row Newton sweeps,
  * "z_logit_hessian_l2" 1 (live Python path, cmf_solvers.py:505-506) | 0 (Cython twin,
@@ -407,6 +409,10 @@ int cmf_als_residual_sq(cmf_ctx *ctx, double *ex, double *ey);
  * cmf_solvers.py:242-246 (V numerator/denominator).                        */
 int cmf_v_buf_elems(cmf_ctx *ctx, int64_t *n);
 int cmf_mu_v_partials(cmf_ctx *ctx, float *dev_buf);
+/* (tests, read-only) the fp32 data passes with a 256-wide factor this context has launched so far, by kernel form: out5[0] the
+ * 512-thread gemm_kernel, [1] / [2] the TN / NN form of the 256-thread workgroup, [3] / [4] their forms with the factor in a
+ * register ring (option "data_pass_wg").  Launches are counted where they are issued: a replayed graph adds none.           */
+int cmf_data_pass_launches(cmf_ctx *ctx, int64_t *out5);
 /* the partial of cmf_mu_v_partials for a 256-aligned block of V rows only (dense X, Y), the Gram part when with_gram: lets a
  * sharded driver compute block c + 1 while block c is all-reduced in the background (cmf_comm_allreduce_f32_bg)              */
 int cmf_mu_v_partials_rows(cmf_ctx *ctx, float *dev_buf, int64_t row0, int64_t nrows, int with_gram);

@@ -86,6 +86,7 @@ PROTOTYPES = {
     "cmf_get_background_weight": [_vp, _i32, _pd],
     "cmf_als_residual_sq": [_vp, _pd, _pd],
     "cmf_v_buf_elems": [_vp, _pi64],
+    "cmf_data_pass_launches": [_vp, _pi64],
     "cmf_mu_v_partials": [_vp, _vp],
     "cmf_mu_v_apply": [_vp, _vp, _dbl, _dbl],
     "cmf_mu_v_partials_rows": [_vp, _vp, _i64, _i64, _i32],
@@ -624,6 +625,13 @@ class Context:
         n = C.c_int64(0)
         check(self._lib.cmf_v_buf_elems(self._h, C.byref(n)))
         return n.value
+
+    def data_pass_launches(self):
+        """Data passes with a 256-wide factor launched so far, by kernel form: (gemm_kernel, wg256 TN, wg256 NN, TN with the
+        factor ring, NN with the factor ring); see option ``"data_pass_wg"``.  Read-only; for the tests."""
+        out = np.zeros(5, dtype=np.int64)
+        check(self._lib.cmf_data_pass_launches(self._h, out.ctypes.data_as(_pi64)))
+        return tuple(int(v) for v in out)
 
     def mu_v_partials(self, dev_ptr):
         check(self._lib.cmf_mu_v_partials(self._h, _vp(dev_ptr)))

@@ -127,7 +127,10 @@ struct cmf_ctx {
                            // only (single steps measured neutral: the ~4 us per dependent kernel boundary is device-side)
     StepGraph mu_graph, newton_graph;
     int opt_split = -1;    // force split-K factor (<=0: heuristic)
-    int opt_data_pass_wg = 3; // BN = 256 data passes on the 256-thread workgroup of cmf_gemm_wg256.hip.h: bit 0 the TN form, bit 1 the NN form (same bits out; C4: 62.22 -> 60.78 ms per iteration)
+    int opt_data_pass_wg = 15; // BN = 256 data passes on the 256-thread workgroup of cmf_gemm_wg256.hip.h: bit 0 the TN form, bit 1 the NN form (C4: 62.22 -> 60.78 ms per iteration);
+                               // bit 2 (with bit 0): the TN form takes the factor from a register ring too -- no LDS, no barrier; bit 3 (with bit 1): the NN form does, X alone
+                               // in LDS; both with buffer loads (C4: 60.81 -> 58.07 ms, profiles/HISTORY.md section 13).  Same bits out whatever the value
+    int64_t data_pass_launches[5] = {0, 0, 0, 0, 0}; // BN = 256 data passes launched by this context (cmf_data_pass_launches, tests): gemm_kernel | wg256 TN | wg256 NN | TN ring | NN ring
     int opt_pair = 1;      // k_pad = 128, dense X and Y: the two data passes of an MU half-iteration as one balanced launch (cmf_gemm_pair.hip.h) | 0: two split launches
     int opt_arith_min_tiles = 8;   // ... only for operands of at least this many 256-row tiles
     int opt_arith = 0;     // data passes at k_pad = 256: 0 fp32 MFMA | 1 bf16x6 (three bf16 planes per operand, fp32-equivalent)
@@ -416,12 +419,22 @@ static int launch_gemm(cmf_ctx *c, const GemmArgs &a, const GemmPlan &pl) {
     if (ROLE == 0 && pl.bn == 256 && (c->opt_data_pass_wg & (MODE == MODE_TN ? 1 : 2)) && a.epi == EPI_NONE && a.Mout % 256 == 0) {
         // four waves, 128 x 128 wave tiles, the TN form's X straight from global memory (cmf_gemm_wg256.hip.h): whole 256-row
         // tiles only (X, Y and their images are padded to 256); every split-K slab has at least one K-step (plan_gemm)
-        using Cfg = Wg256Cfg<MODE>;
-        CHK(allow_big_lds(c, reinterpret_cast<const void *>(&gemm_wg256_kernel<MODE>), (int)Cfg::LDS_BYTES));
-        hipLaunchKernelGGL((gemm_wg256_kernel<MODE>), grid, dim3(Cfg::NT), Cfg::LDS_BYTES, c->stream, a);
+        if ((c->opt_data_pass_wg & (MODE == MODE_TN ? 4 : 8)) && a.lda < ((int64_t)1 << 21) && a.ldb < ((int64_t)1 << 21)) {
+            // ... and the factor from a register ring (32-bit offsets: row pitches below 2^21): the TN form asks for no LDS at all
+            using Cfg = Wg256Cfg<MODE, true>;
+            if constexpr (Cfg::LDS_BYTES != 0) CHK(allow_big_lds(c, reinterpret_cast<const void *>(&gemm_wg256_kernel<MODE, true>), (int)Cfg::LDS_BYTES));
+            hipLaunchKernelGGL((gemm_wg256_kernel<MODE, true>), grid, dim3(Cfg::NT), Cfg::LDS_BYTES, c->stream, a);
+            ++c->data_pass_launches[MODE == MODE_TN ? 3 : 4];
+        } else {
+            using Cfg = Wg256Cfg<MODE, false>;
+            CHK(allow_big_lds(c, reinterpret_cast<const void *>(&gemm_wg256_kernel<MODE, false>), (int)Cfg::LDS_BYTES));
+            hipLaunchKernelGGL((gemm_wg256_kernel<MODE, false>), grid, dim3(Cfg::NT), Cfg::LDS_BYTES, c->stream, a);
+            ++c->data_pass_launches[MODE == MODE_TN ? 1 : 2];
+        }
         HIPCHK(hipGetLastError());
         return CMF_OK;
     }
+    if (ROLE == 0 && pl.bn == 256) ++c->data_pass_launches[0];
     dim3 block(512);
 #define CMF_LAUNCH(BN_)                                                                          \
     do {                                                                                         \
@@ -828,7 +841,8 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
     } else if (!strcmp(name, "gemm_split")) {
         c->opt_split = (int)value;
     } else if (!strcmp(name, "data_pass_wg")) {
-        if (value < 0 || value > 3) return fail(CMF_EINVAL, "data_pass_wg: bit 0 the TN data passes, bit 1 the NN data passes (0..3)");
+        if (value < 0 || value > 15)
+            return fail(CMF_EINVAL, "data_pass_wg: bit 0 the TN data passes, bit 1 the NN data passes, bit 2 / bit 3 their factor from a register ring (0..15)");
         c->opt_data_pass_wg = (int)value;
     } else if (!strcmp(name, "small_gram_shares")) {
         c->opt_gram32_shares = (int)std::max<int64_t>(1, std::min<int64_t>(value, 1024));
@@ -1366,6 +1380,13 @@ extern "C" int cmf_v_buf_elems(cmf_ctx *c, int64_t *n) {
     NEED_PROBLEM(c);
     if (!n) return fail(CMF_EINVAL, "null argument");
     *n = c->dp * c->kp + (int64_t)c->kp * c->kp;
+    return CMF_OK;
+}
+
+// test entry: the BN = 256 data passes this context has launched, by kernel form (a replayed graph launches none here)
+extern "C" int cmf_data_pass_launches(cmf_ctx *c, int64_t *out5) {
+    if (!c || !out5) return fail(CMF_EINVAL, "cmf_data_pass_launches: null context or output");
+    for (int f = 0; f < 5; ++f) out5[f] = c->data_pass_launches[f];
     return CMF_OK;
 }
 
