@@ -402,6 +402,57 @@ int cmf_set_background_weight(cmf_ctx *ctx, int which, double c0);
 int cmf_get_background_weight(cmf_ctx *ctx, int which, double *c0);
 int cmf_als_residual_sq(cmf_ctx *ctx, double *ex, double *ey);
 
+/* ---- ALS for explicit ratings: a global mean, row and column biases, and the value of given cells ------------------------------
+ * Ratings: "this user rates high" and "this item is liked" are offsets, not factors.  For a relation with CSR weights w on its
+ * pattern O and biases enabled the term of the objective is (written for X; Y is the same with V, Z)
+ *   1/2 sum_{O} w_ij (x_ij - mu - r_i - c_j - u_i . v_j)^2  +  lb/2 (|r|^2 + |c|^2),        mu FIXED, lb >= 0
+ * and one iteration is block coordinate descent: the factor sweeps V, U, Z of the steps above, every sweep of a biased relation
+ * reading the adjusted targets t - mu - r_i - c_j in place of t; then, per biased relation, r and then c from the new r, each the
+ * exact minimiser  r_i = sum_{j in O_i} w (t - mu - c_j - u_i . v_j) / (sum_{j in O_i} w + lb).  A row without stored entries gets
+ * exactly 0, and so does a row whose denominator is 0.  Every block is an exact minimisation or a CG / coordinate step that lowers
+ * its quadratic: the descent stays monotone wherever it is monotone without biases.  The bias blocks follow the update mask of
+ * the factor on their axis: r_x with U, c_x and r_y with V, c_y with Z -- so a fold-in of new rows fits their own biases too.
+ *   cmf_set_biases(ctx, which, enable, mu, lb): `which` (0 = X, 1 = Y) must have CSR weights bound (CMF_EINVAL otherwise, and for a
+ *   non-finite mu or lb < 0) and NO background weight (CMF_EUNSUPPORTED; cmf_set_background_weight with c0 > 0 on a biased relation
+ *   is refused the same way; the state is unchanged in both cases).  Allocates zeroed r and c, the adjusted targets of both
+ *   orientations of the pattern and the piece lists.  enable = 0 frees all of it: the state of a context that never had biases.
+ *   cmf_set_weighted_csr, cmf_clear_weight, cmf_set_weight_f32 / _f64 and cmf_set_problem drop the biases of the relation.
+ *   cmf_get_biases: mu, lb and whether biases are bound (any pointer may be NULL).
+ *   cmf_set_bias_f64 / cmf_get_bias_f64(ctx, which, axis, v): the row (axis 0) or column (axis 1) biases, rounded to float32.
+ *   cmf_als_bias_step(ctx, l2, nn_mask, update_mask, cg_steps, nn_sweeps): runs the sweeps of cmf_als_cg_step with the same
+ *   arguments on the adjusted targets (cg_steps = 0: the exact rows; cg_steps = 0 and nn_sweeps = 0: cmf_als_step's routes), then
+ *   the bias sweeps update_mask allows, then rewrites the adjusted targets (they are rewritten whenever the biases change: by
+ *   this step, cmf_set_biases and cmf_set_bias_f64, so every entry point finds them current).  Validation as cmf_als_cg_step, except that cg_steps may be 0.  With no relation
+ *   biased it is that step, byte for byte.
+ *   cmf_als_bias_rows (tests): host_out = the biases one bias sweep of `which` along `axis` would write from the current state;
+ *   nothing is changed.  cmf_als_bias_targets (tests): the adjusted targets bt and bp = w bt of the pattern (image 0) or its
+ *   transpose (image 1) in stored order into buffers of nnz floats (either pointer may be NULL; CMF_EINVAL unless nnz is the number
+ *   of stored entries of the pattern).
+ *   cmf_predict_pairs(ctx, which, link, n, rows, cols, out): out[q] = f(mu + r[rows[q]] + c[cols[q]] + a . b) in float32 for n
+ *   arbitrary cells, a . b = U V^T (which = 0) or V Z^T (1), the bias terms only when biases are bound on `which`, f the identity
+ *   (CMF_LINK_LINEAR) or the sigmoid (CMF_LINK_LOGIT).  Needs the factors only and changes nothing.  CMF_EINVAL: an index outside
+ *   the relation (checked on the host); CMF_EUNSUPPORTED: k_pad > 256.
+ * The kernels (csrc/cmf_als_bias.hip.h): a bias sweep cuts every row into pieces of at most L stored entries (option
+ * "als_bias_piece": 0 the default, 2048; > 0 rounded up to 16; < 0 every row is one piece), one workgroup per piece, the lane groups
+ * of k_pad / 4 lanes dealing its entries round-robin; each term in float32, sums in float64, groups added in group order, pieces in
+ * piece order by a second launch.  No lane group ever walks a whole long row (hot items).  A row's bias depends on the row and on
+ * L alone; no atomics: a repeated call from the same state is bit-identical.  The adjusted targets are rewritten with each
+ * operation rounded once in float32.  The row kernels of the sweeps are unchanged: they read w (t - mu - r - c) where they read w t.
+ * HONOURED BY cmf_als_bias_step and cmf_predict_pairs, and by cmf_als_residual_sq, which reads the adjusted targets where it reads
+ * t (with no biases bound it returns the bits it returned before).  cmf_als_step, cmf_als_nnls_step and cmf_als_cg_step sweep the
+ * factors on the adjusted targets too but never move the biases.  cmf_weighted_residual_sq is unchanged (no bias terms).
+ * NOT HONOURED by cmf_mu_weighted_step: with biases bound on a relation it reads it returns CMF_EUNSUPPORTED (clear them with
+ * cmf_set_biases(ctx, which, 0, 0, 0)).  One GPU; cmf_run is not extended.  Kernel time: the bias passes and cmf_predict_pairs
+ * go to CMF_K_KLMU, the rewrite of the targets to CMF_K_ELEMWISE.                                                            */
+int cmf_set_biases(cmf_ctx *ctx, int which, int enable, double mu, double lb);
+int cmf_get_biases(cmf_ctx *ctx, int which, double *mu, double *lb, int *enabled);
+int cmf_set_bias_f64(cmf_ctx *ctx, int which, int axis, const double *v);
+int cmf_get_bias_f64(cmf_ctx *ctx, int which, int axis, double *v);
+int cmf_als_bias_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask, int cg_steps, int nn_sweeps);
+int cmf_als_bias_rows(cmf_ctx *ctx, int which, int axis, float *host_out);
+int cmf_als_bias_targets(cmf_ctx *ctx, int which, int image, int64_t nnz, float *host_bt, float *host_bp);
+int cmf_predict_pairs(cmf_ctx *ctx, int which, int link, int64_t n, const int64_t *rows, const int64_t *cols, float *out);
+
 /* sharded form: rank g holds rows of X/U and columns of
  * Y/Z, V replicated.  buf is a DEVICE buffer of cmf_v_buf_elems() floats:
  *   [ X_g^T U_g + Y_g Z_g  (d_pad x k_pad) | U_g^T U_g + Z_g^T Z_g (k_pad x k_pad) ]

@@ -4,7 +4,7 @@ The public names are resolved on first use (PEP 562): ``from pycmf_amd import _l
 drivers need -- then imports NumPy only, not scikit-learn / SciPy / pandas behind the estimator."""
 
 __all__ = ["CMF", "collective_matrix_factorization", "HipMUSolver", "HipNewtonSolver", "HipHALSSolver", "HipALSSolver", "top_n_products", "rank_products",
-           "ranking_metrics", "implicit_confidence"]
+           "ranking_metrics", "implicit_confidence", "predict_products"]
 
 
 def __getattr__(name):
@@ -20,6 +20,9 @@ def __getattr__(name):
     if name == "top_n_products":
         from . import prediction
         return prediction.top_n_products
+    if name == "predict_products":
+        from . import prediction
+        return prediction.predict_products
     if name == "rank_products":
         from . import prediction
         return prediction.rank_products

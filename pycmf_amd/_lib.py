@@ -85,6 +85,14 @@ PROTOTYPES = {
     "cmf_set_background_weight": [_vp, _i32, _dbl],
     "cmf_get_background_weight": [_vp, _i32, _pd],
     "cmf_als_residual_sq": [_vp, _pd, _pd],
+    "cmf_set_biases": [_vp, _i32, _i32, _dbl, _dbl],
+    "cmf_get_biases": [_vp, _i32, _pd, _pd, C.POINTER(C.c_int)],
+    "cmf_set_bias_f64": [_vp, _i32, _i32, _pd],
+    "cmf_get_bias_f64": [_vp, _i32, _i32, _pd],
+    "cmf_als_bias_step": [_vp, _dbl, _i32, _i32, _i32, _i32],
+    "cmf_als_bias_rows": [_vp, _i32, _i32, _pf],
+    "cmf_als_bias_targets": [_vp, _i32, _i32, _i64, _pf, _pf],
+    "cmf_predict_pairs": [_vp, _i32, _i32, _i64, _pi64, _pi64, _pf],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_data_pass_launches": [_vp, _pi64],
     "cmf_mu_v_partials": [_vp, _vp],
@@ -614,6 +622,70 @@ class Context:
         ex, ey = C.c_double(0), C.c_double(0)
         check(self._lib.cmf_als_residual_sq(self._h, C.byref(ex) if want_x else None, C.byref(ey) if want_y else None))
         return ex.value, ey.value
+
+    # ---- ALS for explicit ratings: offset, row and column biases (csrc/cmf_als_bias.hip.h)
+    def _bias_len(self, which, axis):
+        m, d, p, _ = self.shape
+        return ((m, d), (d, p))[which][axis]
+
+    def set_biases(self, which, enable=True, mu=0.0, lb=0.0):
+        """Bind (or with ``enable=False`` free) the bias terms of relation ``which`` (0 X | 1 Y), which must have CSR weights and
+        no background weight: the fixed offset ``mu``, zeroed row and column biases, their regulariser ``lb`` >= 0."""
+        check(self._lib.cmf_set_biases(self._h, which, 1 if enable else 0, float(mu), float(lb)))
+
+    def get_biases(self, which):
+        """(mu, lb, enabled) of relation ``which``."""
+        mu, lb, on = C.c_double(0), C.c_double(0), C.c_int(0)
+        check(self._lib.cmf_get_biases(self._h, which, C.byref(mu), C.byref(lb), C.byref(on)))
+        return mu.value, lb.value, bool(on.value)
+
+    def set_bias(self, which, axis, v):
+        """The row (``axis=0``) or column (``axis=1``) biases of relation ``which`` from a float64 vector."""
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (self._bias_len(which, axis),):
+            raise ValueError("set_bias: expected %d values, got an array of shape %s" % (self._bias_len(which, axis), v.shape))
+        check(self._lib.cmf_set_bias_f64(self._h, which, axis, v.ctypes.data_as(_pd)))
+
+    def get_bias(self, which, axis):
+        out = np.zeros(self._bias_len(which, axis), dtype=np.float64)
+        check(self._lib.cmf_get_bias_f64(self._h, which, axis, out.ctypes.data_as(_pd)))
+        return out
+
+    def als_bias_step(self, l2, nn_mask=0, mask=7, cg_steps=0, nn_sweeps=0):
+        """One iteration of the biased model: the sweeps of ``als_cg_step`` (``cg_steps=0`` and ``nn_sweeps=0``: of ``als_step``)
+        on the adjusted targets t - mu - r_i - c_j, then per biased relation the exact row and column bias sweeps ``mask`` allows
+        (r_x with U, c_x and r_y with V, c_y with Z)."""
+        check(self._lib.cmf_als_bias_step(self._h, l2, nn_mask, mask, cg_steps, nn_sweeps))
+
+    def als_bias_rows(self, which, axis):
+        """float32 vector: the biases one bias sweep of relation ``which`` along ``axis`` would write from the current state;
+        nothing is changed."""
+        out = np.zeros(self._bias_len(which, axis), dtype=np.float32)
+        check(self._lib.cmf_als_bias_rows(self._h, which, axis, out.ctypes.data_as(_pf)))
+        return out
+
+    def als_bias_targets(self, which, image, nnz):
+        """(bt, bp) float32[nnz]: the adjusted targets t - mu - r_i - c_j and w times them of the pattern (``image=0``) or its
+        transpose (1) in stored order, as the factor sweeps read them; ``nnz`` must be the stored entries of the pattern
+        (``ValueError`` otherwise: the library writes that many).  For the tests."""
+        nnz = int(nnz)
+        if nnz < 0:
+            raise ValueError("als_bias_targets: nnz must be the number of stored entries, got %d" % nnz)
+        bt, bp = np.zeros(nnz, dtype=np.float32), np.zeros(nnz, dtype=np.float32)
+        check(self._lib.cmf_als_bias_targets(self._h, which, image, nnz, bt.ctypes.data_as(_pf), bp.ctypes.data_as(_pf)))
+        return bt, bp
+
+    def predict_pairs(self, which, rows, cols, link="linear"):
+        """float32[n]: f(offset + r[row] + c[col] + a_row . b_col) of the pairs, a = U, b = V for relation 0 and V, Z for relation 1;
+        the bias terms only when biases are bound on the relation.  Nothing is changed."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).ravel()
+        cols = np.ascontiguousarray(cols, dtype=np.int64).ravel()
+        if rows.shape != cols.shape:
+            raise ValueError("predict_pairs: rows and cols must have one length, got %d and %d" % (rows.size, cols.size))
+        out = np.zeros(rows.size, dtype=np.float32)
+        check(self._lib.cmf_predict_pairs(self._h, which, LINKS[link] if isinstance(link, str) else int(link), rows.size,
+                                          rows.ctypes.data_as(_pi64), cols.ctypes.data_as(_pi64), out.ctypes.data_as(_pf)))
+        return out
 
     def mu_step_error(self, l1, l2, mask=7):
         """One MU iteration and the squared residuals (ex2, ey2) of the factors it leaves, from the step's own products."""

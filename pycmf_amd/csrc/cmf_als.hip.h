@@ -445,7 +445,7 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin
     memset(&a, 0, sizeof a);
     for (int s = 0; s < sw.nobs; ++s) {
         const WCsrDev &M = *sw.obs[s].M;
-        (s == 0 ? a.s0 : a.s1) = AlsSide{M.idx, M.pv, als_side_weights(M), sw.obs[s].B};
+        (s == 0 ? a.s0 : a.s1) = AlsSide{M.idx, als_side_targets(M), als_side_weights(M), sw.obs[s].B};
     }
     float *Hc = (float *)c->als_h.p, *Hp = (float *)c->als_part.p, *grad = (float *)c->als_g.p;
     a.Hp = Hp;
@@ -606,7 +606,7 @@ static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begi
     CHK(als_fetch_indptr(c, sw, r_begin, r_end, ip));
     for (int s = 0; s < sw.nobs; ++s) {
         const WCsrDev &M = *sw.obs[s].M;
-        (s == 0 ? a.s0 : a.s1) = AlsCgSide{M.indptr, M.idx, M.pv, als_side_weights(M), sw.obs[s].B};
+        (s == 0 ? a.s0 : a.s1) = AlsCgSide{M.indptr, M.idx, als_side_targets(M), als_side_weights(M), sw.obs[s].B};
     }
     const int64_t cap_max = als_cg_lds_bytes(c) / als_cg_entry_bytes(kp);
     int64_t caps[ALS_CG_CLASSES + 1];

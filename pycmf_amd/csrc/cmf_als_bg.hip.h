@@ -130,6 +130,8 @@ __global__ __launch_bounds__(256) void als_bg_dot64_kernel(const double *a, cons
 
 // the weights the row kernels read for an observed side: the excess w - c0 under a background, w itself otherwise
 static const float *als_side_weights(const WCsrDev &M) { return M.ev ? M.ev : M.wv; }
+// the products w t they read: w times the adjusted targets under biases (cmf_als_bias.hip.h), p = w t otherwise
+static const float *als_side_targets(const WCsrDev &M) { return M.bp ? M.bp : M.pv; }
 
 // The part of a sweep's systems that all its rows share: *S = sum_sides coef Gram(B_side) (coef: c0 of a side with a background,
 // 1 of a full side; null when no side has either) and *N = T B of the full side (or null).  Without a background S is the Gram of
@@ -176,6 +178,9 @@ extern "C" int cmf_set_background_weight(cmf_ctx *c, int which, double c0) {
     const float cf = (float)c0;
     if (!(c0 >= 0.0) || !std::isfinite(c0) || !std::isfinite(cf))
         return fail(CMF_EINVAL, "cmf_set_background_weight: the background weight must be finite and >= 0 (in float32), got %g", c0);
+    if (cf > 0.f && c->als_bias[which].on)
+        return fail(CMF_EUNSUPPORTED, "cmf_set_background_weight: %s has biases bound; biases and a background weight are not built together: "
+                                      "clear them with cmf_set_biases(ctx, %d, 0, 0, 0)", nm, which);
     DeviceGuard dg(c->device);
     HIPCHK(hipStreamSynchronize(c->stream));
     if (cf == 0.f) {
@@ -227,6 +232,10 @@ extern "C" int cmf_get_background_weight(cmf_ctx *c, int which, double *c0) {
 
 // E of one relation with CSR weights into *out (file header); without a background: the weighted residual, the same launches
 static int als_bg_residual_side(cmf_ctx *c, int which, double *out) {
+    if (c->als_bias[which].on) {   // (never together with a background) the residual of the biased model: bt where the pass reads t
+        CHK(als_bias_refresh(c, which));
+        return wm_residual_side(c, which, out, c->wm_sp[which][0].bt);
+    }
     if (!(c->wm_bg[which] > 0.0)) return wm_residual_side(c, which, out);
     const int fa = which == 0 ? CMF_U : CMF_V, fb = which == 0 ? CMF_V : CMF_Z;
     const float *A = c->F[fa], *B = c->F[fb];

@@ -1,0 +1,461 @@
+// cmf_als_bias.hip.h -- ALS for explicit ratings: a fixed offset mu and row / column biases on a relation whose weights are bound as
+// CSR.  Its term of the objective is
+//   1/2 sum_{O} w_ij (t_ij - mu - r_i - c_j - a_i . b_j)^2  +  lb/2 (|r|^2 + |c|^2),        lb >= 0, mu fixed
+// One iteration is block coordinate descent: the factor sweeps of cmf_als.hip.h on the ADJUSTED targets bt = t - mu - r_i - c_j
+// (the row kernels run unchanged: they read bp = w bt where they read pv = w t), then per biased relation r and c, each the exact
+// minimiser of its block:   r_i = sum_{j in O_i} w (t - mu - c_j - a_i . b_j) / (sum_{j in O_i} w + lb),   0 for a row without
+// stored entries or with a zero denominator.  What this file adds:
+//   als_bias_piece_kernel<GL>   one 256-thread workgroup per PIECE (at most L consecutive stored entries of one row of a CSR image;
+//                          option "als_bias_piece").  GL = k_pad / 4 lanes gather one row of B, a float4 per lane (the lane layout of
+//                          wmu_res_csr_kernel); the 256 / GL lane groups deal the piece's entries among themselves round-robin, two
+//                          gathers in flight per group.  Per entry the term w (t - mu - other[idx] - a . b) in float32; every group
+//                          sums its terms and its weights in float64; the groups are added in group order and the workgroup writes
+//                          one (num, wsum) pair of doubles.  No group ever walks a whole long row.  512 bytes of static LDS
+//   als_bias_combine_kernel  per row: its pieces added in piece order, bias = (float)(num / (wsum + lb)), or 0
+//   als_bias_targets_kernel  bt = ((t - mu) - rowbias[row]) - colbias[idx] and bp = w bt of one image, each operation rounded once in
+//                          float32; one wave per piece (on the transposed image the roles of r and c are swapped by the caller)
+//   predict_pairs_kernel<GL>  out = f(((offset + rowbias[row]) + colbias[col]) + a_row . b_col) for arbitrary pairs, one lane group per
+//                          pair, f linear or sigmoid; the k-sum in the fixed order of group_sum
+// Every cross-workgroup sum is a kernel boundary; no atomics, no grid-wide barrier, vector stores only: a repeated call from the
+// same state is bit-identical, and a row's bias depends on the row and on L alone.
+#ifndef CMF_ALS_BIAS_KERNELS
+#define CMF_ALS_BIAS_KERNELS
+#include "cmf_kernels.hip.h"
+
+namespace cmfk {
+
+struct AlsBiasPiece {
+    int64_t beg;   // first stored entry
+    int32_t len;   // 1 .. L
+    int32_t row;   // of the image
+};
+
+struct AlsBiasArgs {
+    const AlsBiasPiece *pieces;
+    const int32_t *idx;
+    const float *tv, *wv;
+    const float *A, *B;      // the factor of the image's rows, the gathered factor; pitch kp
+    const float *other;      // the bias of the image's columns
+    float mu;
+    int kp;
+    double *part;            // [pieces][2]: num, wsum
+};
+
+template <int GL>
+__global__ __launch_bounds__(256) void als_bias_piece_kernel(AlsBiasArgs g) {
+#pragma clang fp contract(off)
+    constexpr int NG = 256 / GL;
+    const AlsBiasPiece pc = g.pieces[blockIdx.x];
+    const int gl = threadIdx.x % GL, grp = threadIdx.x / GL;
+    const f32x4 a = *reinterpret_cast<const f32x4 *>(g.A + (int64_t)pc.row * g.kp + 4 * gl);
+    const int32_t *idx = g.idx + pc.beg;
+    const float *tv = g.tv + pc.beg, *wv = g.wv + pc.beg;
+    double num = 0.0, ws = 0.0;
+    // every group runs the same number of rounds (a round past the piece's end reads its last entry again and adds nothing): the
+    // lanes of a wave stay together through group_sum
+    for (int base = 0; base < pc.len; base += 2 * NG) {
+        const int e0 = base + grp, e1 = e0 + NG;
+        const int q0 = min(e0, pc.len - 1), q1 = min(e1, pc.len - 1);
+        const int32_t j0 = idx[q0], j1 = idx[q1];
+        const f32x4 b0 = *reinterpret_cast<const f32x4 *>(g.B + (int64_t)j0 * g.kp + 4 * gl);
+        const f32x4 b1 = *reinterpret_cast<const f32x4 *>(g.B + (int64_t)j1 * g.kp + 4 * gl);
+        const float t0 = tv[q0], t1 = tv[q1], w0 = wv[q0], w1 = wv[q1], o0 = g.other[j0], o1 = g.other[j1];
+        float d0 = a[0] * b0[0] + a[1] * b0[1] + a[2] * b0[2] + a[3] * b0[3];
+        float d1 = a[0] * b1[0] + a[1] * b1[1] + a[2] * b1[2] + a[3] * b1[3];
+        d0 = group_sum<GL>(d0);
+        d1 = group_sum<GL>(d1);
+        const float x0 = w0 * (((t0 - g.mu) - o0) - d0), x1 = w1 * (((t1 - g.mu) - o1) - d1);
+        if (e0 < pc.len) {
+            num += (double)x0;
+            ws += (double)w0;
+        }
+        if (e1 < pc.len) {
+            num += (double)x1;
+            ws += (double)w1;
+        }
+    }
+    __shared__ double red[2][NG];
+    if (gl == 0) {
+        red[0][grp] = num;
+        red[1][grp] = ws;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double n = red[0][0], w = red[1][0];
+        for (int q = 1; q < NG; ++q) {
+            n += red[0][q];
+            w += red[1][q];
+        }
+        g.part[2 * (int64_t)blockIdx.x] = n;
+        g.part[2 * (int64_t)blockIdx.x + 1] = w;
+    }
+}
+
+// first[row] .. first[row + 1]: the pieces of the row
+__global__ __launch_bounds__(256) void als_bias_combine_kernel(const double *part, const int64_t *first, int64_t rows, double lb, float *bias) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    const int64_t p0 = first[row], p1 = first[row + 1];
+    double n = 0.0, w = 0.0;
+    for (int64_t p = p0; p < p1; ++p) {
+        n += part[2 * p];
+        w += part[2 * p + 1];
+    }
+    const double den = w + lb;
+    bias[row] = (p1 > p0 && den > 0.0) ? (float)(n / den) : 0.f;
+}
+
+__global__ __launch_bounds__(256) void als_bias_targets_kernel(const AlsBiasPiece *pieces, int64_t npieces, const int32_t *idx, const float *tv, const float *wv,
+                                                               const float *rowbias, const float *colbias, float mu, float *bt, float *bp) {
+#pragma clang fp contract(off)
+    const int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (p >= npieces) return;
+    const AlsBiasPiece pc = pieces[p];
+    const float rb = rowbias[pc.row];
+    for (int e = threadIdx.x & 63; e < pc.len; e += 64) {
+        const int64_t q = pc.beg + e;
+        const float v = ((tv[q] - mu) - rb) - colbias[idx[q]];
+        bt[q] = v;
+        bp[q] = wv[q] * v;
+    }
+}
+
+// link: CMF_LINK_LINEAR | CMF_LINK_LOGIT (f = sigmoid).  rowbias / colbias may be null (no such term)
+template <int GL>
+__global__ __launch_bounds__(256) void predict_pairs_kernel(const int64_t *rows, const int64_t *cols, int64_t n, const float *A, const float *B, int kp,
+                                                            const float *rowbias, const float *colbias, float offset, int link, float *out) {
+#pragma clang fp contract(off)
+    constexpr int NG = 256 / GL;
+    const int gl = threadIdx.x % GL, grp = threadIdx.x / GL;
+    const int64_t p = (int64_t)blockIdx.x * NG + grp, pq = min(p, n - 1);   // a group past the end repeats the last pair and stores nothing
+    const int64_t i = rows[pq], j = cols[pq];
+    const f32x4 a = *reinterpret_cast<const f32x4 *>(A + i * kp + 4 * gl);
+    const f32x4 b = *reinterpret_cast<const f32x4 *>(B + j * kp + 4 * gl);
+    float d = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
+    d = group_sum<GL>(d);
+    float s = offset;
+    if (rowbias) s = s + rowbias[i];
+    if (colbias) s = s + colbias[j];
+    s = s + d;
+    if (link) s = sigmoidf_(s);
+    if (gl == 0 && p < n) out[p] = s;
+}
+
+} // namespace cmfk
+#endif // CMF_ALS_BIAS_KERNELS
+
+// ------------------------------------------------------------------ host side (included by cmf_api.hip behind cmf_als.hip.h)
+#if defined(CMF_ALS_BIAS_HOST) && !defined(CMF_ALS_BIAS_HOST_DONE)
+#define CMF_ALS_BIAS_HOST_DONE
+
+enum { ALS_BIAS_PIECE_DEFAULT = 2048 };
+// entries per piece ("als_bias_piece": > 0 rounded up to 16; 0 the default; < 0 every row is one piece)
+static int64_t als_bias_piece_len(const cmf_ctx *c) {
+    if (c->opt_als_bias_piece < 0) return INT32_MAX;
+    return c->opt_als_bias_piece > 0 ? rup(c->opt_als_bias_piece, 16) : (int64_t)ALS_BIAS_PIECE_DEFAULT;
+}
+
+static bool als_bias_any(const cmf_ctx *c) { return c->als_bias[0].on || c->als_bias[1].on; }
+
+// the piece lists of both images of a relation, from the row lengths (the pattern lives on the device only)
+static int als_bias_plan(cmf_ctx *c, int which) {
+    AlsBias &b = c->als_bias[which];
+    const int64_t L = als_bias_piece_len(c);
+    for (int t = 0; t < 2; ++t) {
+        const WCsrDev &M = c->wm_sp[which][t];
+        std::vector<int64_t> ip((size_t)M.rows + 1, 0), first((size_t)M.rows + 1, 0);
+        HIPCHK(hipMemcpyAsync(ip.data(), M.indptr, ip.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        std::vector<cmfk::AlsBiasPiece> pieces;
+        for (int64_t r = 0; r < M.rows; ++r) {
+            first[(size_t)r] = (int64_t)pieces.size();
+            for (int64_t q = ip[(size_t)r]; q < ip[(size_t)r + 1]; q += L)
+                pieces.push_back(cmfk::AlsBiasPiece{q, (int32_t)std::min<int64_t>(L, ip[(size_t)r + 1] - q), (int32_t)r});
+        }
+        first[(size_t)M.rows] = (int64_t)pieces.size();
+        if ((int64_t)pieces.size() > INT32_MAX) return fail(CMF_EUNSUPPORTED, "cmf_set_biases: more than 2^31 - 1 pieces (als_bias_piece too small)");
+        dev_free(c, b.pieces[t]); dev_free(c, b.first[t]);
+        b.pieces[t] = nullptr; b.first[t] = nullptr;
+        CHK(dev_alloc(c, (void **)&b.pieces[t], std::max<size_t>(16, pieces.size() * sizeof(cmfk::AlsBiasPiece)), false));
+        CHK(dev_alloc(c, (void **)&b.first[t], first.size() * sizeof(int64_t), false));
+        if (!pieces.empty()) HIPCHK(hipMemcpyAsync(b.pieces[t], pieces.data(), pieces.size() * sizeof(cmfk::AlsBiasPiece), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(b.first[t], first.data(), first.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream)); // the host vectors may go
+        b.npieces[t] = (int64_t)pieces.size();
+    }
+    b.L = L;
+    return CMF_OK;
+}
+static int als_bias_replan(cmf_ctx *c, int which) {   // the option may have changed since the lists were built
+    return c->als_bias[which].L == als_bias_piece_len(c) ? CMF_OK : als_bias_plan(c, which);
+}
+
+// bt and bp of both images from the current biases
+static int als_bias_refresh(cmf_ctx *c, int which) {
+    AlsBias &b = c->als_bias[which];
+    if (!b.on || !b.dirty) return CMF_OK;
+    CHK(als_bias_replan(c, which));
+    for (int t = 0; t < 2; ++t) {
+        WCsrDev &M = c->wm_sp[which][t];
+        if (b.npieces[t] == 0) continue;
+        Timed tm(c, CMF_K_ELEMWISE);
+        hipLaunchKernelGGL(cmfk::als_bias_targets_kernel, dim3((unsigned)((b.npieces[t] + 3) / 4)), dim3(256), 0, c->stream,
+                           (const cmfk::AlsBiasPiece *)b.pieces[t], b.npieces[t], (const int32_t *)M.idx, (const float *)M.tv, (const float *)M.wv,
+                           (const float *)(t == 0 ? b.r : b.c), (const float *)(t == 0 ? b.c : b.r), (float)b.mu, M.bt, M.bp);
+        HIPCHK(hipGetLastError());
+    }
+    b.dirty = false;
+    return CMF_OK;
+}
+
+// one bias sweep of relation `which` along `axis` (0 rows, 1 columns) into out (device, rows of that image)
+static int als_bias_sweep(cmf_ctx *c, int which, int axis, float *out) {
+    AlsBias &b = c->als_bias[which];
+    CHK(als_bias_replan(c, which));
+    const WCsrDev &M = c->wm_sp[which][axis];
+    const int fa = which == 0 ? (axis == 0 ? CMF_U : CMF_V) : (axis == 0 ? CMF_V : CMF_Z);
+    const int fb = which == 0 ? (axis == 0 ? CMF_V : CMF_U) : (axis == 0 ? CMF_Z : CMF_V);
+    const int64_t np = b.npieces[axis];
+    CHK(kl_ensure(c, c->als_bias_part, std::max<size_t>(16, (size_t)np * 2 * sizeof(double))));
+    cmfk::AlsBiasArgs a;
+    a.pieces = b.pieces[axis];
+    a.idx = M.idx; a.tv = M.tv; a.wv = M.wv;
+    a.A = c->F[fa]; a.B = c->F[fb];
+    a.other = axis == 0 ? b.c : b.r;
+    a.mu = (float)b.mu;
+    a.kp = c->kp;
+    a.part = (double *)c->als_bias_part.p;
+    Timed tm(c, CMF_K_KLMU, 2.0 * (double)M.nnz * (double)c->kp);
+    if (np > 0) {
+        const dim3 grid((unsigned)np), block(256);
+        switch (c->kp) {
+        case 32: hipLaunchKernelGGL((cmfk::als_bias_piece_kernel<8>), grid, block, 0, c->stream, a); break;
+        case 64: hipLaunchKernelGGL((cmfk::als_bias_piece_kernel<16>), grid, block, 0, c->stream, a); break;
+        case 128: hipLaunchKernelGGL((cmfk::als_bias_piece_kernel<32>), grid, block, 0, c->stream, a); break;
+        default: hipLaunchKernelGGL((cmfk::als_bias_piece_kernel<64>), grid, block, 0, c->stream, a); break;
+        }
+    }
+    if (M.rows > 0)
+        hipLaunchKernelGGL(cmfk::als_bias_combine_kernel, dim3((unsigned)((M.rows + 255) / 256)), dim3(256), 0, c->stream, (const double *)a.part,
+                           (const int64_t *)b.first[axis], M.rows, b.lb, out);
+    HIPCHK(hipGetLastError());
+    return CMF_OK;
+}
+
+static int als_bias_which_ok(const char *what, int which) {
+    if (which != 0 && which != 1) return fail(CMF_EINVAL, "%s: which must be 0 (X) or 1 (Y)", what);
+    return CMF_OK;
+}
+
+extern "C" int cmf_set_biases(cmf_ctx *c, int which, int enable, double mu, double lb) {
+    NEED_PROBLEM(c);
+    CHK(als_bias_which_ok("cmf_set_biases", which));
+    const char *nm = which == 0 ? "X" : "Y";
+    DeviceGuard dg(c->device);
+    if (!enable) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        als_bias_free(c, which);
+        return CMF_OK;
+    }
+    if (c->wm_kind[which] != WM_CSR) return fail(CMF_EINVAL, "cmf_set_biases: %s has no CSR weights bound (cmf_set_weighted_csr first)", nm);
+    if (!std::isfinite(mu) || !std::isfinite((float)mu) || !(lb >= 0.0) || !std::isfinite(lb))
+        return fail(CMF_EINVAL, "cmf_set_biases: mu must be finite (in float32) and lb finite and >= 0, got mu = %g, lb = %g", mu, lb);
+    if (c->kp > 256) return fail(CMF_EUNSUPPORTED, "cmf_set_biases: n_components <= 256 only (k_pad = %d)", c->kp);
+    if (c->wm_bg[which] > 0.0)
+        return fail(CMF_EUNSUPPORTED, "cmf_set_biases: %s has a background weight bound; biases and a background weight are not built together: "
+                                      "clear it with cmf_set_background_weight(ctx, %d, 0)", nm, which);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    als_bias_free(c, which);
+    AlsBias &b = c->als_bias[which];
+    WCsrDev &M0 = c->wm_sp[which][0], &M1 = c->wm_sp[which][1];
+    const int64_t nnz = M0.nnz;
+    // t in the stored order of the transpose: the counting sort of cmf_set_weighted_csr again, from the images on the device
+    {
+        std::vector<int64_t> ip((size_t)M0.rows + 1), ipt((size_t)M1.rows + 1);
+        std::vector<int32_t> ix((size_t)nnz);
+        std::vector<float> t((size_t)nnz), tt((size_t)nnz);
+        HIPCHK(hipMemcpyAsync(ip.data(), M0.indptr, ip.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(ipt.data(), M1.indptr, ipt.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (nnz) {
+            HIPCHK(hipMemcpyAsync(ix.data(), M0.idx, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(t.data(), M0.tv, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));
+        std::vector<int64_t> pos(ipt.begin(), ipt.end() - 1);
+        for (int64_t i = 0; i < M0.rows; ++i)
+            for (int64_t q = ip[(size_t)i]; q < ip[(size_t)i + 1]; ++q) tt[(size_t)pos[(size_t)ix[(size_t)q]]++] = t[(size_t)q];
+        int rc = dev_alloc(c, (void **)&M1.tv, std::max<size_t>(16, (size_t)nnz * sizeof(float)), false);
+        if (rc == CMF_OK && nnz) {
+            hipError_t he = hipMemcpyAsync(M1.tv, tt.data(), (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, c->stream);
+            if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+            if (he != hipSuccess) rc = fail(CMF_EHIP, "cmf_set_biases: %s", hipGetErrorString(he));
+        }
+        if (rc != CMF_OK) {
+            als_bias_free(c, which);
+            return rc;
+        }
+    }
+    int rc = dev_alloc(c, (void **)&b.r, std::max<size_t>(16, (size_t)M0.rows * sizeof(float)));
+    if (rc == CMF_OK) rc = dev_alloc(c, (void **)&b.c, std::max<size_t>(16, (size_t)M0.cols * sizeof(float)));
+    for (int t = 0; t < 2 && rc == CMF_OK; ++t) {
+        rc = dev_alloc(c, (void **)&c->wm_sp[which][t].bt, std::max<size_t>(16, (size_t)nnz * sizeof(float)));
+        if (rc == CMF_OK) rc = dev_alloc(c, (void **)&c->wm_sp[which][t].bp, std::max<size_t>(16, (size_t)nnz * sizeof(float)));
+    }
+    b.mu = mu; b.lb = lb;
+    if (rc == CMF_OK) rc = als_bias_plan(c, which);
+    if (rc != CMF_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        als_bias_free(c, which);
+        return rc;
+    }
+    b.on = true;
+    b.dirty = true;
+    return als_bias_refresh(c, which);   // bt / bp are never stale when an entry point returns: every step reads them
+}
+
+extern "C" int cmf_get_biases(cmf_ctx *c, int which, double *mu, double *lb, int *enabled) {
+    NEED_PROBLEM(c);
+    CHK(als_bias_which_ok("cmf_get_biases", which));
+    const AlsBias &b = c->als_bias[which];
+    if (mu) *mu = b.on ? b.mu : 0.0;
+    if (lb) *lb = b.on ? b.lb : 0.0;
+    if (enabled) *enabled = b.on ? 1 : 0;
+    return CMF_OK;
+}
+
+static int als_bias_vector(cmf_ctx *c, const char *what, int which, int axis, float **vec, int64_t *n) {
+    CHK(als_bias_which_ok(what, which));
+    if (axis != 0 && axis != 1) return fail(CMF_EINVAL, "%s: axis must be 0 (rows) or 1 (columns)", what);
+    AlsBias &b = c->als_bias[which];
+    if (!b.on) return fail(CMF_EINVAL, "%s: %s has no biases bound (cmf_set_biases first)", what, which == 0 ? "X" : "Y");
+    *vec = axis == 0 ? b.r : b.c;
+    *n = c->wm_sp[which][axis].rows;
+    return CMF_OK;
+}
+
+extern "C" int cmf_set_bias_f64(cmf_ctx *c, int which, int axis, const double *v) {
+    NEED_PROBLEM(c);
+    float *dst; int64_t n;
+    CHK(als_bias_vector(c, "cmf_set_bias_f64", which, axis, &dst, &n));
+    if (!v && n > 0) return fail(CMF_EINVAL, "cmf_set_bias_f64: null pointer");
+    std::vector<float> h((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        h[(size_t)i] = (float)v[i];
+        if (!std::isfinite(h[(size_t)i])) return fail(CMF_EINVAL, "cmf_set_bias_f64: entry %lld is not finite in float32", (long long)i);
+    }
+    DeviceGuard dg(c->device);
+    if (n) HIPCHK(hipMemcpyAsync(dst, h.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->als_bias[which].dirty = true;
+    return als_bias_refresh(c, which);
+}
+
+extern "C" int cmf_get_bias_f64(cmf_ctx *c, int which, int axis, double *v) {
+    NEED_PROBLEM(c);
+    float *src; int64_t n;
+    CHK(als_bias_vector(c, "cmf_get_bias_f64", which, axis, &src, &n));
+    if (!v && n > 0) return fail(CMF_EINVAL, "cmf_get_bias_f64: null pointer");
+    std::vector<float> h((size_t)n);
+    DeviceGuard dg(c->device);
+    if (n) HIPCHK(hipMemcpyAsync(h.data(), src, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < n; ++i) v[i] = (double)h[(size_t)i];
+    return CMF_OK;
+}
+
+extern "C" int cmf_als_bias_rows(cmf_ctx *c, int which, int axis, float *host_out) {
+    NEED_PROBLEM(c);
+    float *vec; int64_t n;
+    CHK(als_bias_vector(c, "cmf_als_bias_rows", which, axis, &vec, &n));
+    if (!host_out && n > 0) return fail(CMF_EINVAL, "cmf_als_bias_rows: null output");
+    DeviceGuard dg(c->device);
+    CHK(kl_ensure(c, c->als_bias_ws, std::max<size_t>(16, (size_t)n * sizeof(float))));
+    CHK(als_bias_sweep(c, which, axis, (float *)c->als_bias_ws.p));
+    if (n) HIPCHK(hipMemcpyAsync(host_out, c->als_bias_ws.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CMF_OK;
+}
+
+// test entry beside it: the adjusted targets bt and bp = w bt of one image (0 the pattern, 1 its transpose); nnz: the entries the
+// caller's buffers hold, which must be the stored entries of the pattern
+extern "C" int cmf_als_bias_targets(cmf_ctx *c, int which, int image, int64_t nnz, float *host_bt, float *host_bp) {
+    NEED_PROBLEM(c);
+    float *vec; int64_t n;
+    CHK(als_bias_vector(c, "cmf_als_bias_targets", which, image, &vec, &n));
+    const WCsrDev &M = c->wm_sp[which][image];
+    if (nnz != M.nnz)
+        return fail(CMF_EINVAL, "cmf_als_bias_targets: the caller's buffers hold %lld entries, the pattern stores %lld", (long long)nnz, (long long)M.nnz);
+    DeviceGuard dg(c->device);
+    CHK(als_bias_refresh(c, which));
+    if (M.nnz && host_bt) HIPCHK(hipMemcpyAsync(host_bt, M.bt, (size_t)M.nnz * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (M.nnz && host_bp) HIPCHK(hipMemcpyAsync(host_bp, M.bp, (size_t)M.nnz * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CMF_OK;
+}
+
+extern "C" int cmf_als_bias_step(cmf_ctx *c, double l2, int nn_mask, int mask, int cg_steps, int nn_sweeps) {
+    NEED_PROBLEM(c);
+    CHK(als_check(c, "cmf_als_bias_step", l2, mask));
+    CHK(als_count_ok("cmf_als_bias_step", "cg_steps", cg_steps, 0));
+    CHK(als_count_ok("cmf_als_bias_step", "nn_sweeps", nn_sweeps, 0));
+    if (!als_bias_any(c)) return als_step(c, l2, nn_mask, mask, nn_sweeps, cg_steps);
+    DeviceGuard dg(c->device);
+    for (int w = 0; w < 2; ++w) CHK(als_bias_refresh(c, w));   // (written when the biases last changed: nothing to do)
+    CHK(als_step(c, l2, nn_mask, mask, nn_sweeps, cg_steps));
+    // r_x follows U, c_x and r_y follow V, c_y follows Z; r first, then c from the new r
+    const int bit[2][2] = {{CMF_UPD_U, CMF_UPD_V}, {CMF_UPD_V, CMF_UPD_Z}};
+    for (int w = 0; w < 2; ++w) {
+        AlsBias &b = c->als_bias[w];
+        if (!b.on) continue;
+        for (int axis = 0; axis < 2; ++axis) {
+            if (!(mask & bit[w][axis])) continue;
+            CHK(als_bias_sweep(c, w, axis, axis == 0 ? b.r : b.c));
+            b.dirty = true;
+        }
+        CHK(als_bias_refresh(c, w));   // the adjusted targets of the next step, and of cmf_als_residual_sq
+    }
+    return CMF_OK;
+}
+
+extern "C" int cmf_predict_pairs(cmf_ctx *c, int which, int link, int64_t n, const int64_t *rows, const int64_t *cols, float *out) {
+    NEED_PROBLEM(c);
+    CHK(als_bias_which_ok("cmf_predict_pairs", which));
+    if (link != CMF_LINK_LINEAR && link != CMF_LINK_LOGIT) return fail(CMF_EINVAL, "cmf_predict_pairs: link must be CMF_LINK_LINEAR or CMF_LINK_LOGIT");
+    if (n < 0) return fail(CMF_EINVAL, "cmf_predict_pairs: negative pair count");
+    if (c->kp > 256) return fail(CMF_EUNSUPPORTED, "cmf_predict_pairs: n_components <= 256 only (k_pad = %d)", c->kp);
+    if (n == 0) return CMF_OK;
+    if (!rows || !cols || !out) return fail(CMF_EINVAL, "cmf_predict_pairs: null pointer");
+    const int fa = which == 0 ? CMF_U : CMF_V, fb = which == 0 ? CMF_V : CMF_Z;
+    for (int64_t q = 0; q < n; ++q)
+        if (rows[q] < 0 || rows[q] >= c->frows[fa] || cols[q] < 0 || cols[q] >= c->frows[fb])
+            return fail(CMF_EINVAL, "cmf_predict_pairs: pair %lld = (%lld, %lld) lies outside the %lld x %lld relation", (long long)q, (long long)rows[q],
+                        (long long)cols[q], (long long)c->frows[fa], (long long)c->frows[fb]);
+    DeviceGuard dg(c->device);
+    const size_t ibytes = (size_t)n * sizeof(int64_t);
+    CHK(kl_ensure(c, c->als_bias_ws, 2 * ibytes + (size_t)n * sizeof(float)));
+    int64_t *dr = (int64_t *)c->als_bias_ws.p, *dc = dr + n;
+    float *dout = (float *)(dc + n);
+    HIPCHK(hipMemcpyAsync(dr, rows, ibytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dc, cols, ibytes, hipMemcpyHostToDevice, c->stream));
+    const AlsBias &b = c->als_bias[which];
+    const float *rb = b.on ? b.r : nullptr, *cb = b.on ? b.c : nullptr;
+    const float off = b.on ? (float)b.mu : 0.f;
+    {
+        Timed tm(c, CMF_K_KLMU, 2.0 * (double)n * (double)c->kp);
+        const int gl = c->kp / 4, ng = 256 / gl;
+        const dim3 grid((unsigned)((n + ng - 1) / ng)), block(256);
+        const float *A = c->F[fa], *B = c->F[fb];
+        switch (c->kp) {
+        case 32: hipLaunchKernelGGL((cmfk::predict_pairs_kernel<8>), grid, block, 0, c->stream, dr, dc, n, A, B, c->kp, rb, cb, off, link, dout); break;
+        case 64: hipLaunchKernelGGL((cmfk::predict_pairs_kernel<16>), grid, block, 0, c->stream, dr, dc, n, A, B, c->kp, rb, cb, off, link, dout); break;
+        case 128: hipLaunchKernelGGL((cmfk::predict_pairs_kernel<32>), grid, block, 0, c->stream, dr, dc, n, A, B, c->kp, rb, cb, off, link, dout); break;
+        default: hipLaunchKernelGGL((cmfk::predict_pairs_kernel<64>), grid, block, 0, c->stream, dr, dc, n, A, B, c->kp, rb, cb, off, link, dout); break;
+        }
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CMF_OK;
+}
+
+#endif // CMF_ALS_BIAS_HOST

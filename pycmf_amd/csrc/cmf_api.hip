@@ -90,7 +90,21 @@ struct WCsrDev {
     int32_t *idx = nullptr;
     float *pv = nullptr, *wv = nullptr, *tv = nullptr;
     float *ev = nullptr;   // excess weights w - c0 under a background weight (cmf_als_bg.hip.h), or null
+    float *bt = nullptr, *bp = nullptr; // adjusted targets t - mu - r_i - c_j and w times them under biases (cmf_als_bias.hip.h), or null
     int64_t rows = 0, cols = 0, nnz = 0;
+};
+
+// Biases of a relation with CSR weights (cmf_als_bias.hip.h): mu, lb, the row and column biases and the piece lists of both images;
+// the adjusted targets live in the images (WCsrDev::bt / bp), t of the transposed image in its tv
+namespace cmfk { struct AlsBiasPiece; }
+struct AlsBias {
+    bool on = false, dirty = false;   // dirty: the biases changed since bt / bp were written
+    double mu = 0.0, lb = 0.0;
+    float *r = nullptr, *c = nullptr;
+    cmfk::AlsBiasPiece *pieces[2] = {nullptr, nullptr};
+    int64_t *first[2] = {nullptr, nullptr};
+    int64_t npieces[2] = {0, 0};
+    int64_t L = 0;                    // the piece length the lists were built for
 };
 
 // A captured update step: replayed with hipGraphLaunch while the key (hyper-parameters baked into
@@ -156,6 +170,9 @@ struct cmf_ctx {
     int64_t als_cg_last[2] = {0, 0};      // long rows and pieces of the last CG sweep (cmf_als_cg_last, tests)
     double wm_bg[2] = {0.0, 0.0};         // background weight c0 of X / Y on the cells outside a CSR pattern (cmf_als_bg.hip.h; 0: none)
     DevBuf als_bg_s, als_bg64;            // ... the shared matrix sum coef Gram of a sweep; float64 Grams of the error's trace term
+    AlsBias als_bias[2];                  // mu and row / column biases of X / Y (cmf_als_bias.hip.h; off: none)
+    int opt_als_bias_piece = 0;           // ... stored entries per piece of a row in the bias passes (0: the default, 2048; > 0 rounded up to 16; < 0: every row is one piece)
+    DevBuf als_bias_part, als_bias_ws;    // ... (num, wsum) of every piece; cmf_als_bias_rows' result / the pairs and values of cmf_predict_pairs
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
     int opt_chol = 1;      // Cholesky fast path of the safe inverse (0: always Jacobi)
     int opt_chol_mfma = 1; // k_pad = 256 per-row solves: blocked Cholesky on the matrix pipe (0: the rank-1 register kernel chol_solve_kernel<16>)
@@ -351,6 +368,21 @@ static void dev_free(cmf_ctx *c, void *p) {
     if (it != c->owned.end()) c->owned.erase(it);
     (void)hipFree(p);
 }
+// the biases of a relation and everything cmf_set_biases allocated for them: the state of a context that never had any
+static void als_bias_free(cmf_ctx *c, int which) {
+    AlsBias &b = c->als_bias[which];
+    dev_free(c, b.r); dev_free(c, b.c);
+    for (int t = 0; t < 2; ++t) {
+        dev_free(c, b.pieces[t]); dev_free(c, b.first[t]);
+        WCsrDev &M = c->wm_sp[which][t];
+        dev_free(c, M.bt); dev_free(c, M.bp);
+        M.bt = M.bp = nullptr;
+    }
+    dev_free(c, c->wm_sp[which][1].tv);   // t in the stored order of the transpose exists under biases only
+    c->wm_sp[which][1].tv = nullptr;
+    b = AlsBias();
+}
+static int als_bias_refresh(cmf_ctx *c, int which);   // cmf_als_bias.hip.h: bt / bp of both images from the current biases
 static void drop_graph(StepGraph &g) {
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
     g = StepGraph();
@@ -787,7 +819,9 @@ static void release_problem(cmf_ctx *c) {
     c->als_h = DevBuf(); c->als_part = DevBuf(); c->als_g = DevBuf(); c->als_sol = DevBuf(); c->als_desc = DevBuf(); c->als_nnls_ws = DevBuf(); c->als_cg_ws = DevBuf();
     c->als_cg_long = DevBuf(); c->als_cg_last[0] = c->als_cg_last[1] = 0;
     c->als_bg_s = DevBuf(); c->als_bg64 = DevBuf();
+    c->als_bias_part = DevBuf(); c->als_bias_ws = DevBuf();
     for (int w = 0; w < 2; ++w) {
+        c->als_bias[w] = AlsBias();
         c->wm_bg[w] = 0.0;
         c->wm_kind[w] = 0; c->wm_w[w] = c->wm_p[w] = nullptr;
         c->wm_sp[w][0] = WCsrDev(); c->wm_sp[w][1] = WCsrDev();
@@ -950,6 +984,8 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
         c->opt_als_cg_lds = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "als_cg_piece")) {
         c->opt_als_cg_piece = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 30));
+    } else if (!strcmp(name, "als_bias_piece")) {
+        c->opt_als_bias_piece = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 30));
     } else if (!strcmp(name, "topk_split")) {
         c->opt_topk_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "sparse_mode")) {
@@ -1896,3 +1932,5 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_hals.hip.h"
 #define CMF_ALS_HOST
 #include "cmf_als.hip.h"
+#define CMF_ALS_BIAS_HOST
+#include "cmf_als_bias.hip.h"

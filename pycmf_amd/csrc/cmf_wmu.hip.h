@@ -400,6 +400,7 @@ static const WmPass WM_U{0, false, CMF_U, CMF_V}, WM_VX{0, true, CMF_V, CMF_U}, 
 static float *wm_data(const cmf_ctx *c, int which) { return which == 0 ? c->X : c->Y; }
 
 static void wm_free_side(cmf_ctx *c, int which) {
+    als_bias_free(c, which);   // biases (cmf_als_bias.hip.h) go with the weights they were set on, as a background weight does
     dev_free(c, c->wm_w[which]); dev_free(c, c->wm_p[which]);
     c->wm_w[which] = c->wm_p[which] = nullptr;
     for (int t = 0; t < 2; ++t) {
@@ -540,6 +541,10 @@ extern "C" int cmf_mu_weighted_step(cmf_ctx *c, double l1, double l2, int mask) 
         if (c->wm_bg[w] > 0.0 && (mask & ((w == 0 ? CMF_UPD_U : CMF_UPD_Z) | CMF_UPD_V)))
             return fail(CMF_EUNSUPPORTED, "cmf_mu_weighted_step: %s has a background weight bound, which only the ALS steps honour; "
                                           "clear it with cmf_set_background_weight(ctx, %d, 0)", w == 0 ? "X" : "Y", w);
+    for (int w = 0; w < 2; ++w)
+        if (c->als_bias[w].on && (mask & ((w == 0 ? CMF_UPD_U : CMF_UPD_Z) | CMF_UPD_V)))
+            return fail(CMF_EUNSUPPORTED, "cmf_mu_weighted_step: %s has biases bound, which only cmf_als_bias_step honours; "
+                                          "clear them with cmf_set_biases(ctx, %d, 0, 0, 0)", w == 0 ? "X" : "Y", w);
     DeviceGuard dg(c->device);
     CHK(kl_ensure(c, c->wm_slab, wm_slab_bytes(c, mask)));
     float *base = (float *)c->wm_slab.p;
@@ -560,14 +565,15 @@ extern "C" int cmf_mu_weighted_step(cmf_ctx *c, double l1, double l2, int mask) 
 }
 
 // sum of w (t - s)^2 over one relation into *out
-static int wm_residual_side(cmf_ctx *c, int which, double *out) {
+// (targets: what the CSR pass reads as t -- the adjusted targets of a biased relation for cmf_als_residual_sq; null: t itself)
+static int wm_residual_side(cmf_ctx *c, int which, double *out, const float *targets = nullptr) {
     const int fa = which == 0 ? CMF_U : CMF_V, fb = which == 0 ? CMF_V : CMF_Z;
     const float *A = c->F[fa], *B = c->F[fb];
     CHK(kl_ensure(c, c->wm_small, 64));
     double *sum = (double *)c->wm_small.p;
     if (c->wm_kind[which] == WM_CSR) {
         const WCsrDev &M = c->wm_sp[which][0];
-        WCsrView v{M.indptr, M.idx, M.pv, M.wv, M.tv, M.rows};
+        WCsrView v{M.indptr, M.idx, M.pv, M.wv, targets ? targets : M.tv, M.rows};
         const int gl = c->kp / 4, rpw = 64 / gl;
         const unsigned blocks = (unsigned)std::max<int64_t>(1, ((M.rows + rpw - 1) / rpw + 3) / 4);
         CHK(kl_ensure(c, c->wm_part, (size_t)blocks * sizeof(double)));

@@ -13,7 +13,7 @@ from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
 from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_entry_weights, check_hals,
-                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_background_weight)
+                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_background_weight, check_biases, check_bias_l2)
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -42,7 +42,8 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                     hessian_pertubation=0.2, sg_sample_ratio=1.,
                                     device=0, sg_sampler="numpy", n_gpus=1, _return_solver=False, loss="frobenius",
                                     x_entry_weights=None, y_entry_weights=None, als_nn_sweeps=0, als_cg_steps=0,
-                                    x_background_weight=0.0, y_background_weight=0.0):
+                                    x_background_weight=0.0, y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None,
+                                    _x_bias_init=None, _y_bias_init=None):
     """Factorise X ~ f(U V^T) and Y ~ f(V Z^T) with a shared V on an MI355X.
 
     Same contract as the reference function (pycmf/cmf.py:215-456): returns
@@ -90,6 +91,13 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     the stored entries alone (``HipALSSolver``; ``pycmf_amd.implicit_confidence`` makes targets and confidences from counts).
     ``ValueError`` before any device is touched: a non-zero value with another solver, without entry weights for that relation or
     with dense ones; a bool, a non-finite or a negative value; a stored weight below the background.
+
+    ``x_biases`` / ``y_biases``: False | True (``solver='als'`` only) -- explicit ratings: the relation is fitted as
+    mu + r_i + c_j + a_i.b_j, mu the weighted mean of its stored targets, r and c fitted under the regulariser ``bias_l2`` (None:
+    ``l2_reg``) by exact block minimisation in every iteration (``HipALSSolver``).  The relation's entry weights must be a SciPy
+    sparse W or ``'observed'``, and it must have no background weight.  ``ValueError`` before any device is touched: True with
+    another solver, without such entry weights or with a background weight; a ``bias_l2`` that is not None or a finite number >= 0.
+    The fitted biases are on the solver object (``x_bias`` / ``y_bias``) and on the estimator (``CMF.x_bias_`` / ``y_bias_``).
     """
     if n_components is None:
         n_components = max(X.shape[1], Y.shape[1])
@@ -101,6 +109,11 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                                                  (Z_non_negative, update_Z)) if upd])
     x_background_weight = check_background_weight(x_background_weight, "x", solver, x_entry_weights)
     y_background_weight = check_background_weight(y_background_weight, "y", solver, y_entry_weights)
+    x_biases = check_biases(x_biases, "x", solver, x_entry_weights, x_background_weight)
+    y_biases = check_biases(y_biases, "y", solver, y_entry_weights, y_background_weight)
+    bias_l2 = check_bias_l2(bias_l2)
+    if bias_l2 is not None and solver != "als":
+        raise ValueError("bias_l2 is the bias regulariser of solver='als': it must be None with solver=%r" % (solver,))
 
     if update_U or update_V:
         X = check_array(X, accept_sparse=('csr', 'csc'), dtype=float)
@@ -148,7 +161,9 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                           "link arguments will be ignored")
         solver_object = HipALSSolver(U_non_negative=U_non_negative, V_non_negative=V_non_negative, Z_non_negative=Z_non_negative,
                                      x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, nn_sweeps=als_nn_sweeps, cg_steps=als_cg_steps,
-                                     x_background_weight=x_background_weight, y_background_weight=y_background_weight, **common)
+                                     x_background_weight=x_background_weight, y_background_weight=y_background_weight,
+                                     x_biases=x_biases, y_biases=y_biases, bias_l2=bias_l2, x_bias_init=_x_bias_init,
+                                     y_bias_init=_y_bias_init, **common)
         solver_object.check_weights(X, Y)
     else:
         raise ValueError("No such solver: %s" % solver)
@@ -235,6 +250,23 @@ def initial_factors(X, Y, U, V, Z, x_init, y_init, n_components, random_state, x
     elif Z_non_negative and not U_non_negative:
         V = V_from_y
     return U, V, Z
+
+
+class FittedBias:
+    """The bias terms of one relation of a fitted model: ``offset`` (mu), ``rows`` and ``cols`` (float64 vectors)."""
+
+    def __init__(self, offset, rows, cols):
+        self.offset, self.rows, self.cols = float(offset), np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.float64)
+
+    def as_tuple(self):
+        return self.offset, self.rows, self.cols
+
+    def __repr__(self):
+        return "FittedBias(offset=%r, rows=<%d>, cols=<%d>)" % (self.offset, self.rows.size, self.cols.size)
+
+
+def _fitted_bias(triple):
+    return None if triple is None else FittedBias(*triple)
 
 
 def _writable_f64(F):
@@ -327,12 +359,16 @@ class CMF(BaseEstimator, TransformerMixin):
                     loss=self.loss, als_nn_sweeps=self.als_nn_sweeps, als_cg_steps=self.als_cg_steps)
 
     def fit_transform(self, X, Y, U=None, V=None, Z=None, x_entry_weights=None, y_entry_weights=None, x_background_weight=0.0,
-                      y_background_weight=0.0):
+                      y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None):
         """``x_entry_weights`` / ``y_entry_weights``: per-entry weights of X / Y for this fit (``collective_matrix_factorization``);
         ``reconstruction_err_`` is then sqrt(sum Wx (X - U V^T)^2) + sqrt(sum Wy (Y - V Z^T)^2).
         ``x_background_weight`` / ``y_background_weight`` (``solver='als'``, sparse entry weights): the weight of the cells outside
         the weights' pattern, for implicit feedback; ``reconstruction_err_`` is then sqrt(E_x) + sqrt(E_y) with
-        E = sum_O w (t - a.b)^2 + c0 sum_{not O} (a.b)^2."""
+        E = sum_O w (t - a.b)^2 + c0 sum_{not O} (a.b)^2.
+        ``x_biases`` / ``y_biases`` / ``bias_l2`` (``solver='als'``, sparse entry weights, no background weight): fit the relation as
+        mu + r_i + c_j + a_i.b_j (``collective_matrix_factorization``).  The model then carries ``x_bias_`` / ``y_bias_`` (None, or an
+        object with ``.offset``, ``.rows``, ``.cols``), which ``predict``, ``score_entries``, ``top_n``, ``ranks`` and ``transform``
+        honour."""
         X = check_array(X, accept_sparse=('csr', 'csc'), dtype=float)
         Y = check_array(Y, accept_sparse=('csr', 'csc'), dtype=float)
         if X.shape[1] != Y.shape[0]:
@@ -342,10 +378,14 @@ class CMF(BaseEstimator, TransformerMixin):
             X=X, Y=Y, U=U, V=V, Z=Z, n_components=self.n_components,
             x_init=self.x_init, y_init=self.y_init, alpha=self.alpha, n_gpus=self.n_gpus,
             _return_solver=True, x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights,
-            x_background_weight=x_background_weight, y_background_weight=y_background_weight, **self._kwargs())
+            x_background_weight=x_background_weight, y_background_weight=y_background_weight, x_biases=x_biases, y_biases=y_biases,
+            bias_l2=bias_l2, **self._kwargs())
         # unweighted sum of the two residual norms, evaluated on the device where the
         # data and the final factors still live (cmf.py:697-698)
         self.reconstruction_err_ = solver_object.reconstruction_error()
+        self.x_bias_ = _fitted_bias(getattr(solver_object, "x_bias", None))
+        self.y_bias_ = _fitted_bias(getattr(solver_object, "y_bias", None))
+        self.bias_l2_ = bias_l2
         solver_object.release()
         self.n_components_ = U.shape[1]
         self.x_weights = U
@@ -362,22 +402,69 @@ class CMF(BaseEstimator, TransformerMixin):
         """Re-fit U and/or Z with the learnt components V held fixed; pass ``None`` for
         the side that should be left alone (cmf.py:726-747).  ``x_entry_weights`` / ``y_entry_weights``: per-entry weights of
         the given X / Y, as in ``fit_transform``; ``x_background_weight`` / ``y_background_weight`` likewise: with them this is
-        the fold-in of new users (rows of X) against the fixed V under the implicit-feedback model."""
+        the fold-in of new users (rows of X) against the fixed V under the implicit-feedback model.
+
+        On a model fitted with biases the given relation is folded in under the same model: the fitted offset and the biases on V's
+        axis (the columns of X, the rows of Y) stay fixed, the biases of the new rows of X (columns of Y) start at 0 and are fitted
+        with U (Z).  The return value is unchanged; those biases are left on ``transform_x_row_bias_`` /
+        ``transform_y_col_bias_`` (None for a side without biases).  Such a relation needs its ``*_entry_weights`` here too."""
         assert hasattr(self, "components")
         update_U = X is not None
         update_Z = Y is not None
         alpha = 1 if Y is None else 0 if X is None else "auto"
         U = None if update_U else self.x_weights
         Z = None if update_Z else self.y_weights
-        U, V, Z, _ = collective_matrix_factorization(
+        bx = getattr(self, "x_bias_", None) if update_U else None
+        by = getattr(self, "y_bias_", None) if update_Z else None
+        U, V, Z, _, solver_object = collective_matrix_factorization(
             X=X, Y=Y, U=U, V=self.components, Z=Z, n_components=self.n_components,
             x_init="custom", y_init="custom", alpha=alpha,
             update_U=update_U, update_V=False, update_Z=update_Z, x_entry_weights=x_entry_weights,
             y_entry_weights=y_entry_weights, x_background_weight=x_background_weight, y_background_weight=y_background_weight,
-            **self._kwargs())
+            x_biases=bx is not None, y_biases=by is not None, bias_l2=getattr(self, "bias_l2_", None),
+            _x_bias_init=None if bx is None else (bx.offset, None, bx.cols),
+            _y_bias_init=None if by is None else (by.offset, by.rows, None),
+            _return_solver=True, **self._kwargs())
+        self.transform_x_row_bias_ = None if bx is None else solver_object.x_bias[1]
+        self.transform_y_col_bias_ = None if by is None else solver_object.y_bias[2]
+        if hasattr(solver_object, "release"):
+            solver_object.release()
         return U, V, Z
 
-    def top_n(self, relation="x", axis=0, rows=None, n=10, exclude=None, queries=None):
+    def _relation(self, relation):
+        if relation not in ("x", "y"):
+            raise ValueError("relation must be 'x' or 'y', got %r" % (relation,))
+        if relation == "x":
+            return self.x_weights, self.components, self.x_link, getattr(self, "x_bias_", None)
+        return self.components, self.y_weights, self.y_link, getattr(self, "y_bias_", None)
+
+    def predict(self, rows, cols, relation="x"):
+        """float32[n]: the fitted value of the cells ``(rows[q], cols[q])`` of ``relation`` -- 'x': f(U V^T), 'y': f(V Z^T), f the
+        estimator's own link, plus offset, row and column bias on a model fitted with biases.  Works for a model of any solver;
+        the product is never formed (float32 on GPU ``self.device``, ``pycmf_amd.predict_products``)."""
+        assert hasattr(self, "components")
+        from .prediction import predict_products
+        A, B, link, bias = self._relation(relation)
+        kw = {} if bias is None else dict(offset=bias.offset, row_bias=bias.rows, col_bias=bias.cols)
+        return predict_products(A, B, rows, cols, link=link, device=self.device, **kw)
+
+    def score_entries(self, held_out, relation="x"):
+        """``{'rmse', 'mae', 'n'}`` of ``predict`` over the stored entries of the SciPy sparse ``held_out`` (the relation's shape;
+        stored zeros count); the reduction runs in float64 on the host."""
+        assert hasattr(self, "components")
+        import scipy.sparse as sp
+        A, B, _, _ = self._relation(relation)
+        if not sp.issparse(held_out):
+            raise ValueError("held_out must be a SciPy sparse matrix whose stored entries are the cells to score, got %s" % type(held_out).__name__)
+        if held_out.shape != (A.shape[0], B.shape[0]):
+            raise ValueError("held_out must have shape %r, got %r" % ((A.shape[0], B.shape[0]), held_out.shape))
+        H = held_out.tocoo()
+        if H.nnz == 0:
+            return {"rmse": float("nan"), "mae": float("nan"), "n": 0}
+        e = self.predict(H.row.astype(np.int64), H.col.astype(np.int64), relation=relation).astype(np.float64) - np.asarray(H.data, dtype=np.float64)
+        return {"rmse": float(np.sqrt(np.mean(e * e))), "mae": float(np.mean(np.abs(e))), "n": int(H.nnz)}
+
+    def top_n(self, relation="x", axis=0, rows=None, n=10, exclude=None, queries=None, query_bias=None):
         """The ``n`` highest entries per row (``axis=0``) or per column (``axis=1``) of the fitted reconstruction of
         ``relation`` -- 'x': f(U V^T), 'y': f(V Z^T), f the estimator's own ``x_link`` / ``y_link`` -- as
         ``(idx int32[nq, n], val float32[nq, n])``, best first, equal scores by smaller index.  The product is never formed: scores
@@ -387,13 +474,19 @@ class CMF(BaseEstimator, TransformerMixin):
         matrix of the relation's shape whose stored entries are skipped (pass the training ``X``: what a user has already seen);
         a row with fewer than n candidates left has ``-1 / -inf`` in the remaining places.  ``queries``: an (nq x k) array used
         instead of the fitted rows -- the ``U`` that ``transform`` returned for new rows; ``exclude`` then has nq rows (columns
-        for ``axis=1``).  ``rows`` together with ``queries`` is a ``ValueError``."""
+        for ``axis=1``).  ``rows`` together with ``queries`` is a ``ValueError``.
+
+        On a model fitted with biases on ``relation`` the scores include offset and biases (``val`` is the prediction itself, the
+        order includes the candidate's bias; needs ``n_components + 2 <= 256``), and ``queries`` take an optional ``query_bias``
+        (one value per query, default 0: what ``transform`` left on ``transform_x_row_bias_``)."""
         assert hasattr(self, "components")
         from .prediction import model_top_n
+        bias = self._relation(relation)[3] if relation in ("x", "y") else None
         return model_top_n(self.x_weights, self.components, self.y_weights, self.x_link, self.y_link, self.device,
-                           relation=relation, axis=axis, rows=rows, n=n, exclude=exclude, queries=queries)
+                           relation=relation, axis=axis, rows=rows, n=n, exclude=exclude, queries=queries,
+                           bias=None if bias is None else bias.as_tuple(), query_bias=query_bias)
 
-    def ranks(self, held_out, relation="x", axis=0, exclude=None, rows=None, queries=None):
+    def ranks(self, held_out, relation="x", axis=0, exclude=None, rows=None, queries=None, query_bias=None):
         """The exact rank of every entry ``held_out`` stores in the fitted reconstruction of ``relation``, per row (``axis=0``) or
         per column (``axis=1``): ``(indptr int64[nq + 1], indices int32, rank int32, eligible int32[nq])`` -- the canonical CSR
         order of ``held_out`` (of its transpose for ``axis=1``), ``rank[e]`` = how many candidates of the row that ``exclude``
@@ -407,17 +500,20 @@ class CMF(BaseEstimator, TransformerMixin):
         ``queries``); ``rows`` together with ``queries`` is a ``ValueError``."""
         assert hasattr(self, "components")
         from .prediction import model_ranks
+        bias = self._relation(relation)[3] if relation in ("x", "y") else None
         return model_ranks(self.x_weights, self.components, self.y_weights, self.device, held_out, relation=relation, axis=axis,
-                           exclude=exclude, rows=rows, queries=queries)
+                           exclude=exclude, rows=rows, queries=queries, bias=None if bias is None else bias.as_tuple(),
+                           query_bias=query_bias)
 
-    def evaluate(self, held_out, n=(10,), relation="x", axis=0, exclude=None, rows=None, queries=None):
+    def evaluate(self, held_out, n=(10,), relation="x", axis=0, exclude=None, rows=None, queries=None, query_bias=None):
         """Ranking metrics of the fitted model on the entries ``held_out`` stores: ``ranks`` with the same keywords, then
         ``pycmf_amd.ranking_metrics`` at the cut-offs ``n`` -- a dict with ``hit_rate@n``, ``recall@n``, ``precision@n``,
         ``ndcg@n`` per cut-off, ``mrr``, ``map``, ``auc`` and the row counts."""
         assert hasattr(self, "components")
         from .evaluation import ranking_metrics, _check_cutoffs
         _check_cutoffs(n)
-        indptr, _, rank, eligible = self.ranks(held_out, relation=relation, axis=axis, exclude=exclude, rows=rows, queries=queries)
+        indptr, _, rank, eligible = self.ranks(held_out, relation=relation, axis=axis, exclude=exclude, rows=rows, queries=queries,
+                                               query_bias=query_bias)
         return ranking_metrics(indptr, rank, eligible, n=n)
 
     def print_topic_terms(self, vectorizer, topn_words=10, importances=True):

@@ -72,6 +72,86 @@ def _check_rows(rows, nrows):
     return r
 
 
+def _augmented(factors, qf, cf, bias, axis, rows, queries, query_bias):
+    """(queries, candidates) of a biased relation for the top-n and rank kernels, which know dot products only:
+    query rows [f | 1 | offset + own bias], candidate rows [f | candidate bias | 1] -- so that q . c is the prediction itself and
+    the order includes the candidate's bias.  ``bias``: (offset, rows, cols) of the relation; ``axis`` 1 swaps their roles."""
+    offset, rb, cb = bias
+    qb, kb = (rb, cb) if axis == 0 else (cb, rb)
+    C = np.asarray(factors[cf], dtype=np.float64)
+    k = C.shape[1]
+    if k + 2 > 256:
+        raise NotImplementedError("top_n / ranks on a model with biases need n_components + 2 <= 256, got n_components = %d" % k)
+    if queries is not None:
+        Q = queries
+        own = np.zeros(Q.shape[0]) if query_bias is None else np.asarray(query_bias, dtype=np.float64).ravel()
+        if own.shape != (Q.shape[0],):
+            raise ValueError("query_bias must hold one value per query (%d), got shape %r" % (Q.shape[0], np.shape(query_bias)))
+    else:
+        if query_bias is not None:
+            raise ValueError("query_bias goes with queries: the fitted rows have their fitted biases")
+        Q = np.asarray(factors[qf], dtype=np.float64)
+        own = np.asarray(qb, dtype=np.float64)
+        if rows is not None:
+            Q, own = Q[rows], own[rows]
+    Qa = np.concatenate([Q, np.ones((Q.shape[0], 1)), (float(offset) + own)[:, None]], axis=1)
+    Ca = np.concatenate([C, np.asarray(kb, dtype=np.float64)[:, None], np.ones((C.shape[0], 1))], axis=1)
+    return Qa, Ca
+
+
+def _problem_rows(cf, ncand):
+    """Row counts of a problem whose candidate factor has ``ncand`` rows (the others are placeholders of one row)."""
+    rows = [1, 1, 1]
+    rows[cf] = ncand
+    return rows
+
+
+def predict_products(A, B, rows, cols, link="linear", row_bias=None, col_bias=None, offset=0.0, device=0):
+    """float32[n]: ``f(offset + row_bias[i] + col_bias[j] + a_i . b_j)`` for the pairs ``(i, j) = (rows[q], cols[q])`` of rows of
+    ``A`` (m x k) and ``B`` (d x k).  ``link``: 'linear' | 'logit' (sigmoid); ``row_bias`` / ``col_bias``: vectors of m / d values or
+    None (zeros).  Float32 arithmetic on GPU ``device`` (csrc/cmf_als_bias.hip.h, one lane group per pair); the m x d product is
+    never formed.  Everything that can fail on its arguments fails before a device is touched."""
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1] or A.shape[1] < 1 or A.shape[0] < 1 or B.shape[0] < 1:
+        raise ValueError("A and B must be non-empty (m, k) and (d, k) arrays, got shapes %r and %r" % (A.shape, B.shape))
+    if A.shape[1] > 256:
+        raise NotImplementedError("predict_products is built for at most 256 components, got %d" % A.shape[1])
+    _check_link(link)
+    rows, cols = np.asarray(rows), np.asarray(cols)
+    if rows.ndim != 1 or cols.ndim != 1 or rows.shape != cols.shape:
+        raise ValueError("rows and cols must be 1-d index arrays of one length, got shapes %r and %r" % (rows.shape, cols.shape))
+    if rows.size and not (np.issubdtype(rows.dtype, np.integer) and np.issubdtype(cols.dtype, np.integer)):
+        raise ValueError("rows and cols must be integer index arrays")
+    rows, cols = rows.astype(np.int64), cols.astype(np.int64)
+    if rows.size and (rows.min() < 0 or rows.max() >= A.shape[0] or cols.min() < 0 or cols.max() >= B.shape[0]):
+        raise ValueError("rows must lie in [0, %d) and cols in [0, %d)" % (A.shape[0], B.shape[0]))
+    offset = float(offset)
+    if not np.isfinite(offset):
+        raise ValueError("offset must be finite, got %r" % (offset,))
+    biased = row_bias is not None or col_bias is not None or offset != 0.0
+    vecs = []
+    for v, n, nm in ((row_bias, A.shape[0], "row_bias"), (col_bias, B.shape[0], "col_bias")):
+        v = np.zeros(n) if v is None else np.asarray(v, dtype=np.float64).ravel()
+        if v.shape != (n,) or not np.isfinite(v).all():
+            raise ValueError("%s must hold %d finite values" % (nm, n))
+        vecs.append(v)
+    if rows.size == 0:
+        return np.zeros(0, dtype=np.float32)
+    ctx = _lib.Context(device)
+    try:
+        ctx.set_problem(A.shape[0], B.shape[0], 1, A.shape[1])
+        ctx.set_factor(_lib.CMF_U, A)
+        ctx.set_factor(_lib.CMF_V, B)
+        if biased:   # the bias terms live on a relation with CSR weights: an empty pattern carries them
+            ctx.set_weighted_csr(0, np.zeros(A.shape[0] + 1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0), np.zeros(0))
+            ctx.set_biases(0, True, offset, 0.0)
+            ctx.set_bias(0, 0, vecs[0])
+            ctx.set_bias(0, 1, vecs[1])
+        return ctx.predict_pairs(0, rows, cols, link=link)
+    finally:
+        ctx.close()
+
+
 def top_n_products(A, B, n, link="linear", exclude=None, device=0):
     """For every row a_i of ``A`` (nq x k) the ``n`` rows b_j of ``B`` (C x k) with the largest ``f(a_i . b_j)``:
     ``(idx int32[nq, n], val float32[nq, n])``, best first, equal scores by smaller j.  ``link``: 'linear' | 'logit' (sigmoid).
@@ -93,8 +173,10 @@ def top_n_products(A, B, n, link="linear", exclude=None, device=0):
         ctx.close()
 
 
-def model_top_n(U, V, Z, x_link, y_link, device, relation="x", axis=0, rows=None, n=10, exclude=None, queries=None):
-    """``CMF.top_n`` on explicit factors (see there)."""
+def model_top_n(U, V, Z, x_link, y_link, device, relation="x", axis=0, rows=None, n=10, exclude=None, queries=None, bias=None,
+                query_bias=None):
+    """``CMF.top_n`` on explicit factors (see there).  ``bias``: (offset, rows, cols) of a relation fitted with biases -- the
+    kernels then run on augmented factors (``_augmented``), ``query_bias`` the biases of ``queries`` (default 0)."""
     if relation not in ("x", "y"):
         raise ValueError("relation must be 'x' or 'y', got %r" % (relation,))
     if axis not in (0, 1):
@@ -116,8 +198,16 @@ def model_top_n(U, V, Z, x_link, y_link, device, relation="x", axis=0, rows=None
     excl = None
     if exclude is not None:
         excl = exclusion_lists(exclude, (nrows, ncand), rows=rows, transpose=(axis == 1))
+    if bias is None and query_bias is not None:
+        raise ValueError("query_bias needs a model fitted with biases on relation %r" % (relation,))
+    if bias is not None:
+        Qa, Ca = _augmented(factors, qf, cf, bias, axis, rows, queries, query_bias)
     ctx = _lib.Context(device)
     try:
+        if bias is not None:
+            ctx.set_problem(*_problem_rows(cf, ncand), k + 2)
+            ctx.set_factor(cf, Ca)
+            return ctx.topk(qf, cf, n, link=link, exclude=excl, queries=Qa)
         ctx.set_problem(U.shape[0], V.shape[0], Z.shape[0], k)
         ctx.set_factor(cf, factors[cf])
         if queries is None:
@@ -171,8 +261,8 @@ def rank_products(A, B, held_out, exclude=None, device=0):
     return held[0], held[1], rank, eligible
 
 
-def model_ranks(U, V, Z, device, held_out, relation="x", axis=0, exclude=None, rows=None, queries=None):
-    """``CMF.ranks`` on explicit factors (see there)."""
+def model_ranks(U, V, Z, device, held_out, relation="x", axis=0, exclude=None, rows=None, queries=None, bias=None, query_bias=None):
+    """``CMF.ranks`` on explicit factors (see there); ``bias`` / ``query_bias`` as in ``model_top_n``."""
     if relation not in ("x", "y"):
         raise ValueError("relation must be 'x' or 'y', got %r" % (relation,))
     if axis not in (0, 1):
@@ -194,8 +284,17 @@ def model_ranks(U, V, Z, device, held_out, relation="x", axis=0, exclude=None, r
     if exclude is not None:
         excl = exclusion_lists(exclude, (nrows, ncand), rows=rows, transpose=(axis == 1))
     _check_no_leak(held, excl, ncand)
+    if bias is None and query_bias is not None:
+        raise ValueError("query_bias needs a model fitted with biases on relation %r" % (relation,))
+    if bias is not None:
+        Qa, Ca = _augmented(factors, qf, cf, bias, axis, rows, queries, query_bias)
     ctx = _lib.Context(device)
     try:
+        if bias is not None:
+            ctx.set_problem(*_problem_rows(cf, ncand), k + 2)
+            ctx.set_factor(cf, Ca)
+            rank, _, eligible = ctx.rank(qf, cf, held, exclude=excl, queries=Qa)
+            return held[0], held[1], rank, eligible
         ctx.set_problem(U.shape[0], V.shape[0], Z.shape[0], k)
         ctx.set_factor(cf, factors[cf])
         if queries is None:

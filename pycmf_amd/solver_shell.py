@@ -152,6 +152,53 @@ def check_background_weight(value, name, solver="als", entry_weights="observed")
     return value
 
 
+def check_biases(flag, name, solver="als", entry_weights="observed", background_weight=0.0):
+    """``x_biases`` / ``y_biases`` (``name`` 'x' | 'y'): a bool; True with solver='als' only, for a relation whose entry weights
+    resolve to a CSR pattern (a SciPy sparse W or 'observed') and that has no background weight.  Returns the flag as a bool; no
+    device is touched."""
+    if not isinstance(flag, (bool, np.bool_)):
+        raise ValueError("%s_biases must be True or False, got %r" % (name, flag))
+    if not flag:
+        return False
+    if solver != "als":
+        raise ValueError("%s_biases is the rating model of solver='als' (mu + row bias + column bias + u.v): it must be False with "
+                         "solver=%r; pass solver='als'" % (name, solver))
+    import scipy.sparse as sp
+    if entry_weights is None or not (isinstance(entry_weights, str) or sp.issparse(entry_weights)):
+        raise ValueError("%s_biases=True needs %s_entry_weights that name the observed entries: pass %s_entry_weights='observed' (a SciPy "
+                         "sparse %s) or a SciPy sparse W; biases of a relation that counts in every cell are not built" % (name, name, name, name.upper()))
+    if background_weight:
+        raise ValueError("%s_biases=True together with %s_background_weight=%r is not built: pass %s_background_weight=0 (ratings), or "
+                         "%s_biases=False (implicit feedback)" % (name, name, background_weight, name, name))
+    return True
+
+
+def check_bias_l2(bias_l2):
+    """``bias_l2``: None (the fit's l2_reg) or a finite number >= 0; returns it as None or a float.  No device is touched."""
+    if bias_l2 is None:
+        return None
+    if isinstance(bias_l2, (bool, np.bool_)) or not isinstance(bias_l2, (numbers.Real, np.integer, np.floating)) or \
+            not np.isfinite(float(bias_l2)) or float(bias_l2) < 0:
+        raise ValueError("bias_l2 must be None (use l2_reg) or a finite number >= 0, got %r; pass bias_l2=0 for unregularised biases" % (bias_l2,))
+    return float(bias_l2)
+
+
+def _check_bias_init(init, shape, name):
+    """A starting point (offset, rows, cols) of a relation's biases -- rows / cols may be None (zeros) -- as float64."""
+    if init is None:
+        return None
+    offset, rows, cols = init
+    out = [float(offset)]
+    if not np.isfinite(out[0]):
+        raise ValueError("%s_bias_init: the offset must be finite, got %r" % (name, offset))
+    for v, n, what in ((rows, shape[0], "rows"), (cols, shape[1], "cols")):
+        v = np.zeros(n) if v is None else np.asarray(v, dtype=np.float64).ravel()
+        if v.shape != (n,) or not np.isfinite(v).all():
+            raise ValueError("%s_bias_init: %s must hold %d finite values" % (name, what, n))
+        out.append(v)
+    return tuple(out)
+
+
 def check_background_floor(ew, value, name):
     """Every stored weight of the resolved ``ew`` must be >= the background weight, compared as the device does, in float32."""
     if not value or ew is None:
@@ -610,24 +657,56 @@ class HipALSSolver(HipMUSolver):
     error of such a relation is sqrt(sum_O w e^2 + c0 sum_{not O} (a.b)^2) (``cmf_als_residual_sq``).  On patterns with a few very
     long columns keep the exact route for V (``cg_steps=0``), as without a background.
 
+    ``x_biases=True`` / ``y_biases=True`` (default False): the rating model  t ~ mu + r_i + c_j + a_i.b_j  on that relation, which
+    must have sparse entry weights (or ``'observed'``) and no background weight.  mu is fixed at the weighted mean of the stored
+    targets; r and c are fitted by exact block minimisation after the factor sweeps of every iteration, under the regulariser
+    ``bias_l2`` (None: ``l2_reg``), and the factor sweeps -- whichever route ``nn_sweeps`` / ``cg_steps`` name -- read the targets
+    minus the bias terms (``cmf_als_bias_step``); the descent stays monotone.  After a fit or a step ``x_bias`` / ``y_bias`` hold
+    ``(offset, rows, cols)`` as float64; ``x_bias_init`` / ``y_bias_init`` start from such a triple (rows / cols may be None:
+    zeros).  The bias blocks follow the update flag of the factor on their axis (r_x: U; c_x, r_y: V; c_y: Z), so a fold-in of new
+    rows against a fixed V fits their own biases too.  The error of such a relation is the weighted residual of the biased model.
+
     Like MU it ignores alpha and the links.  The error metric is the one of a weighted MU fit, sqrt(sum wx e^2) +
     sqrt(sum wy e^2); the loop stays on the host (``cmf_run`` knows the MU and Newton steps only)."""
 
     _densify_unweighted = False
 
     def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, cg_steps=0, x_background_weight=0.0,
-                 y_background_weight=0.0, **kwargs):
+                 y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None, x_bias_init=None, y_bias_init=None, **kwargs):
         check_als_nn_sweeps(nn_sweeps)
         check_als_cg_steps(cg_steps)
         self.x_background_weight = check_background_weight(x_background_weight, "x", "als", x_entry_weights)
         self.y_background_weight = check_background_weight(y_background_weight, "y", "als", y_entry_weights)
+        self.x_biases = check_biases(x_biases, "x", "als", x_entry_weights, self.x_background_weight)
+        self.y_biases = check_biases(y_biases, "y", "als", y_entry_weights, self.y_background_weight)
+        self.bias_l2 = check_bias_l2(bias_l2)
+        for init, flag, nm in ((x_bias_init, self.x_biases, "x"), (y_bias_init, self.y_biases, "y")):
+            if init is not None and not flag:
+                raise ValueError("%s_bias_init needs %s_biases=True" % (nm, nm))
+        self.x_bias_init, self.y_bias_init = x_bias_init, y_bias_init
+        self.x_bias = self.y_bias = None     # (offset, rows, cols) as float64 after a fit or a step
         super().__init__(*args, loss="frobenius", x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, **kwargs)
         check_als(self.l1_reg, self.l2_reg)
         self.nn_sweeps = int(nn_sweeps)
         self.cg_steps = int(cg_steps)
 
     def _weights_key(self):
-        return super()._weights_key() + (self.x_background_weight, self.y_background_weight)
+        return super()._weights_key() + (self.x_background_weight, self.y_background_weight, self.x_biases, self.y_biases)
+
+    def _bias_l2(self):
+        return self.bias_l2 if self.bias_l2 is not None else float(self.l2_reg)
+
+    def _pull_biases(self):
+        for which, flag, name in ((0, self.x_biases, "x_bias"), (1, self.y_biases, "y_bias")):
+            if flag and self._ctx is not None:
+                setattr(self, name, (self._ctx.get_biases(which)[0], self._ctx.get_bias(which, 0), self._ctx.get_bias(which, 1)))
+
+    def _fit_end(self):
+        self._pull_biases()
+
+    def update_step(self, X, Y, U, V, Z, l1_reg, l2_reg, alpha):
+        super().update_step(X, Y, U, V, Z, l1_reg, l2_reg, alpha)
+        self._pull_biases()     # (the biases stay on the device between calls on the same X, Y; x_bias / y_bias follow them)
 
     def _resolve_weights(self, X, Y):
         key = (id(X), id(Y))
@@ -635,6 +714,20 @@ class HipALSSolver(HipMUSolver):
             self._als_resolved = tuple(_weights_as_pattern(ew) for ew in super()._resolve_weights(X, Y))
             check_background_floor(self._als_resolved[0], self.x_background_weight, "x")
             check_background_floor(self._als_resolved[1], self.y_background_weight, "y")
+            shapes = ((None if X is None else X.shape), (None if Y is None else Y.shape))
+            self._bias_start = []
+            for ew, flag, init, shape, nm in ((self._als_resolved[0], self.x_biases, self.x_bias_init, shapes[0], "x"),
+                                              (self._als_resolved[1], self.y_biases, self.y_bias_init, shapes[1], "y")):
+                if not flag:
+                    self._bias_start.append(None)
+                    continue
+                if ew is None or shape is None:
+                    raise ValueError("%s_biases=True needs the relation and its %s_entry_weights" % (nm, nm))
+                init = _check_bias_init(init, shape, nm)
+                if init is None:   # mu: the weighted mean of the stored targets, in float64
+                    w, t = np.asarray(ew.w, dtype=np.float64), np.asarray(ew.t, dtype=np.float64)
+                    init = (float((w * t).sum() / w.sum()) if w.sum() > 0 else 0.0, None, None)
+                self._bias_start.append(init)
             self._als_resolved_for = key
         return self._als_resolved
 
@@ -646,11 +739,19 @@ class HipALSSolver(HipMUSolver):
             for which, c0 in ((0, self.x_background_weight), (1, self.y_background_weight)):
                 if c0:
                     ctx.set_background_weight(which, c0)
+            for which, start in enumerate(self._bias_start):
+                if start is not None:
+                    ctx.set_biases(which, True, start[0], self._bias_l2())
+                    for axis in (0, 1):
+                        if start[1 + axis] is not None:
+                            ctx.set_bias(which, axis, start[1 + axis])
         return ctx
 
     def _device_step(self, l1_reg, l2_reg, alpha):
         check_als(l1_reg, l2_reg)
-        if self.cg_steps:
+        if self.x_biases or self.y_biases:
+            self._ctx.als_bias_step(l2_reg, self._nn_mask(), self._update_mask(), self.cg_steps, self.nn_sweeps)
+        elif self.cg_steps:
             self._ctx.als_cg_step(l2_reg, self._nn_mask(), self._update_mask(), self.cg_steps, self.nn_sweeps)
         elif self.nn_sweeps:
             self._ctx.als_nnls_step(l2_reg, self._nn_mask(), self._update_mask(), self.nn_sweeps)
@@ -661,7 +762,8 @@ class HipALSSolver(HipMUSolver):
         X, Y = self._XY
         wx, wy = self.x_entry_weights is not None, self.y_entry_weights is not None
         ex2 = ey2 = 0.0
-        if self.x_background_weight or self.y_background_weight:
+        if self.x_background_weight or self.y_background_weight or self.x_biases or self.y_biases:
+            # (biases: the residual of the biased model, t - mu - r - c - a.b, from the same call)
             # E = sum_O w (t - s)^2 + c0 (<A^T A, B^T B> - sum_O s^2): the error over every cell; a side without a background
             # gets the bits of the weighted residual from the same call
             ex2, ey2 = self._ctx.als_residual_sq(wx and X is not None, wy and Y is not None)
