@@ -464,6 +464,13 @@ int cmf_mu_v_partials(cmf_ctx *ctx, float *dev_buf);
  * 512-thread gemm_kernel, [1] / [2] the TN / NN form of the 256-thread workgroup, [3] / [4] their forms with the factor in a
  * register ring (option "data_pass_wg").  Launches are counted where they are issued: a replayed graph adds none.           */
 int cmf_data_pass_launches(cmf_ctx *ctx, int64_t *out5);
+/* (tests, read-only) what the routes of cmf_mu_step and of the row-blocked entry points below have launched on this context so
+ * far, by form: out8[0] gemm_kernel with the fused EPI_MU epilogue (256-row tiles), [1] factor_update_kernel (64-row tiles, any
+ * epilogue), [2] factor_update2_kernel (U and Z in one launch), [3] gemm_pair_kernel (two data passes in one launch), [4] small
+ * Grams (one per gram32_partial_kernel + gram32_reduce_kernel pair), [5] sum_slabs_kernel (any caller), [6] mu_apply_kernel,
+ * [7] copies of the column-tile image of an in-place fused update over its factor (option "narrow_update").  Counted where the
+ * launches are issued: a replayed graph adds none.  The counters change no launch and no result.                            */
+int cmf_mu_route_launches(cmf_ctx *ctx, int64_t *out8);
 /* the partial of cmf_mu_v_partials for a 256-aligned block of V rows only (dense X, Y), the Gram part when with_gram: lets a
  * sharded driver compute block c + 1 while block c is all-reduced in the background (cmf_comm_allreduce_f32_bg)              */
 int cmf_mu_v_partials_rows(cmf_ctx *ctx, float *dev_buf, int64_t row0, int64_t nrows, int with_gram);

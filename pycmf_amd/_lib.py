@@ -95,6 +95,7 @@ PROTOTYPES = {
     "cmf_predict_pairs": [_vp, _i32, _i32, _i64, _pi64, _pi64, _pf],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_data_pass_launches": [_vp, _pi64],
+    "cmf_mu_route_launches": [_vp, _pi64],
     "cmf_mu_v_partials": [_vp, _vp],
     "cmf_mu_v_apply": [_vp, _vp, _dbl, _dbl],
     "cmf_mu_v_partials_rows": [_vp, _vp, _i64, _i64, _i32],
@@ -704,6 +705,16 @@ class Context:
         out = np.zeros(5, dtype=np.int64)
         check(self._lib.cmf_data_pass_launches(self._h, out.ctypes.data_as(_pi64)))
         return tuple(int(v) for v in out)
+
+    MU_ROUTE_FORMS = ("epi_mu", "factor_update", "factor_update2", "pair", "gram32", "sum_slabs", "mu_apply", "narrow_copy")
+
+    def mu_route_launches(self):
+        """Launches of the plain MU step's routes so far, by form (``MU_ROUTE_FORMS``: gemm_kernel with the fused MU epilogue,
+        factor_update_kernel, factor_update2_kernel, gemm_pair_kernel, small-Gram kernel pairs, sum_slabs_kernel, mu_apply_kernel,
+        copies of a column-tile image over its factor).  Read-only; for the tests."""
+        out = np.zeros(8, dtype=np.int64)
+        check(self._lib.cmf_mu_route_launches(self._h, out.ctypes.data_as(_pi64)))
+        return dict(zip(self.MU_ROUTE_FORMS, (int(v) for v in out)))
 
     def mu_v_partials(self, dev_ptr):
         check(self._lib.cmf_mu_v_partials(self._h, _vp(dev_ptr)))

@@ -145,6 +145,8 @@ struct cmf_ctx {
                                // bit 2 (with bit 0): the TN form takes the factor from a register ring too -- no LDS, no barrier; bit 3 (with bit 1): the NN form does, X alone
                                // in LDS; both with buffer loads (C4: 60.81 -> 58.07 ms, profiles/HISTORY.md section 13).  Same bits out whatever the value
     int64_t data_pass_launches[5] = {0, 0, 0, 0, 0}; // BN = 256 data passes launched by this context (cmf_data_pass_launches, tests): gemm_kernel | wg256 TN | wg256 NN | TN ring | NN ring
+    int64_t mu_route_launches[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // launches of the plain MU step's routes by this context (cmf_mu_route_launches, tests): gemm_kernel with EPI_MU |
+                               // factor_update_kernel | factor_update2_kernel | gemm_pair_kernel | gram32 partial + reduce | sum_slabs_kernel | mu_apply_kernel | narrow_tmp alias copy
     int opt_pair = 1;      // k_pad = 128, dense X and Y: the two data passes of an MU half-iteration as one balanced launch (cmf_gemm_pair.hip.h) | 0: two split launches
     int opt_arith_min_tiles = 8;   // ... only for operands of at least this many 256-row tiles
     int opt_arith = 0;     // data passes at k_pad = 256: 0 fp32 MFMA | 1 bf16x6 (three bf16 planes per operand, fp32-equivalent)
@@ -493,6 +495,7 @@ static int sum_slabs(cmf_ctx *c, float *dst, const float *src, int64_t n, int ns
     const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
     hipLaunchKernelGGL(sum_slabs_kernel, dim3(blocks), dim3(256), 0, c->stream, dst, src, n4, nslab, stride,
                        accumulate ? 1 : 0);
+    ++c->mu_route_launches[5];
     HIPCHK(hipGetLastError());
     return CMF_OK;
 }
@@ -581,7 +584,11 @@ static int gemm(cmf_ctx *c, int mode, const float *A, int64_t lda, const float *
             else CHK((launch_gemm<MODE_TN, 1>(c, a, pl)));
         }
     }
-    if (alias_out) HIPCHK(hipMemcpyAsync(alias_out, c->narrow_tmp.p, (size_t)rup(mout, 256) * n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (mu && mu->kind == EPI_MU) ++c->mu_route_launches[0];
+    if (alias_out) {
+        HIPCHK(hipMemcpyAsync(alias_out, c->narrow_tmp.p, (size_t)rup(mout, 256) * n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        ++c->mu_route_launches[7];
+    }
     if (!mu && pl.nsplit > 1) {
         if (defer && !accumulate) { // the consumer sums the slabs (valid until the next GEMM reuses the slab workspace)
             defer->base = (const float *)slabbuf.p; defer->nslab = pl.nsplit; defer->stride = a.slab_stride;
@@ -609,6 +616,7 @@ static int gram32(cmf_ctx *c, const float *F, int64_t rows_pad, float *G) {
     hipLaunchKernelGGL(gram32_partial_kernel, dim3((unsigned)ntile, (unsigned)nsplit), dim3(256), 0, c->stream, F, c->kp, rows_pad, chunk, (float *)c->gslab32.p);
     hipLaunchKernelGGL(gram32_reduce_kernel, dim3((unsigned)std::min(64, (c->kp * c->kp + 255) / 256)), dim3(256), 0, c->stream, (const float *)c->gslab32.p,
                        c->kp, (int)nsplit, G);
+    ++c->mu_route_launches[4];
     HIPCHK(hipGetLastError());
     return CMF_OK;
 }
@@ -639,6 +647,7 @@ static int factor_update2(cmf_ctx *c, const float *A0, const Epilogue &e0, int64
     const size_t lds = (size_t)(128 * 128 + 64 * 132) * sizeof(float);
     CHK(allow_big_lds(c, reinterpret_cast<const void *>(&factor_update2_kernel<128>), (int)lds));
     hipLaunchKernelGGL((factor_update2_kernel<128>), dim3((unsigned)((rows0 + rows1) / 64)), dim3(256), lds, c->stream, g0, g1, (int)(rows0 / 64));
+    ++c->mu_route_launches[2];
     HIPCHK(hipGetLastError());
     return CMF_OK;
 }
@@ -655,6 +664,7 @@ static int factor_update(cmf_ctx *c, const float *A, const float *B, const Epilo
         const size_t lds = (size_t)(64 * 64 + 64 * 68) * sizeof(float);
         hipLaunchKernelGGL((factor_update_kernel<64>), grid, dim3(256), lds, c->stream, g);
     }
+    ++c->mu_route_launches[1];
     HIPCHK(hipGetLastError());
     return CMF_OK;
 }
@@ -732,6 +742,7 @@ static int mu_apply(cmf_ctx *c, float *F, const float *num, const float *den, in
     const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
     hipLaunchKernelGGL(mu_apply_kernel, dim3(blocks), dim3(256), 0, c->stream, F, num, den, n4, (float)l1, (float)l2,
                        1.1920928955078125e-07f);
+    ++c->mu_route_launches[6];
     HIPCHK(hipGetLastError());
     return CMF_OK;
 }
@@ -1426,6 +1437,13 @@ extern "C" int cmf_data_pass_launches(cmf_ctx *c, int64_t *out5) {
     return CMF_OK;
 }
 
+// test entry: what the routes of the plain MU step have launched on this context, by form (a replayed graph launches none here)
+extern "C" int cmf_mu_route_launches(cmf_ctx *c, int64_t *out8) {
+    if (!c || !out8) return fail(CMF_EINVAL, "cmf_mu_route_launches: null context or output");
+    for (int f = 0; f < 8; ++f) out8[f] = c->mu_route_launches[f];
+    return CMF_OK;
+}
+
 // ------------------------------------------------------------------ MU solver
 // V numerator/Gram partials of this shard: cmf_solvers.py:244-245
 extern "C" int cmf_mu_v_partials(cmf_ctx *c, float *buf) {
@@ -1523,6 +1541,7 @@ static int data_times_pair(cmf_ctx *c, const PairSide &a0, const PairSide &a1, S
     CHK(allow_big_lds(c, reinterpret_cast<const void *>(&gemm_pair_kernel), (int)lds));
     Timed tm(c, CMF_K_GEMM_PAIR, flops * c->flop_scale);
     hipLaunchKernelGGL(gemm_pair_kernel, dim3((unsigned)nwg), dim3(512), lds, c->stream, g);
+    ++c->mu_route_launches[3];
     HIPCHK(hipGetLastError());
     return CMF_OK;
 }
