@@ -430,11 +430,11 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin
         cuts.push_back(e);
         r = e;
     }
-    CHK(kl_ensure(c, c->als_h, (size_t)std::max<int64_t>(1, max_rows) * kk * sizeof(float)));
-    CHK(kl_ensure(c, c->als_part, (size_t)std::max<int64_t>(1, max_pieces) * (kk + kp) * sizeof(float)));
-    CHK(kl_ensure(c, c->als_g, (size_t)rows_pad * kp * sizeof(float)));
+    CHK(ensure_scratch(c, c->als_h, (size_t)std::max<int64_t>(1, max_rows) * kk * sizeof(float)));
+    CHK(ensure_scratch(c, c->als_part, (size_t)std::max<int64_t>(1, max_pieces) * (kk + kp) * sizeof(float)));
+    CHK(ensure_scratch(c, c->als_g, (size_t)rows_pad * kp * sizeof(float)));
     const size_t pbytes = std::max<size_t>(16, pl.pieces.size() * sizeof(AlsPiece)), fbytes = pl.first.size() * sizeof(int64_t);
-    CHK(kl_ensure(c, c->als_desc, pbytes + fbytes));
+    CHK(ensure_scratch(c, c->als_desc, pbytes + fbytes));
     AlsPiece *dpieces = (AlsPiece *)c->als_desc.p;
     int64_t *dfirst = (int64_t *)((char *)c->als_desc.p + pbytes);
     if (!pl.pieces.empty()) HIPCHK(hipMemcpyAsync(dpieces, pl.pieces.data(), pl.pieces.size() * sizeof(AlsPiece), hipMemcpyHostToDevice, c->stream));
@@ -480,7 +480,7 @@ struct AlsNewtonStateGuard {
 
 // rows exact: the Cholesky solves of every chunk into c->als_sol -- the plain route of the per-row Newton sweeps
 static int als_rows_solve(cmf_ctx *c, const AlsSweep &sw, double l2) {
-    CHK(kl_ensure(c, c->als_sol, (size_t)c->frows_pad[sw.f] * c->kp * sizeof(float)));
+    CHK(ensure_scratch(c, c->als_sol, (size_t)c->frows_pad[sw.f] * c->kp * sizeof(float)));
     // the threshold of that route, well below l2 <= lambda_min(H_i): its test (a Cholesky of H_i - pert I whose pivots must exceed
     // 4e-6 max H_jj) passes unless cond(H_i) is above ~2e5, where a float32 factorisation has nothing left to give
     const double pert = l2 / 16.0;
@@ -641,7 +641,7 @@ static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begi
     for (int q = 0; q <= ALS_CG_CLASSES; ++q) all.insert(all.end(), list[q].begin(), list[q].end());
     // descriptors, once per sweep: the rows of the class launches | the long rows | their pieces
     const size_t rbytes = std::max<size_t>(16, all.size() * sizeof(int64_t)), lbytes = longs.size() * sizeof(AlsCgLongRow);
-    CHK(kl_ensure(c, c->als_desc, rbytes + lbytes + pieces.size() * sizeof(AlsCgPiece)));
+    CHK(ensure_scratch(c, c->als_desc, rbytes + lbytes + pieces.size() * sizeof(AlsCgPiece)));
     int64_t *drows = (int64_t *)c->als_desc.p;
     AlsCgLongRow *dlongs = (AlsCgLongRow *)((char *)c->als_desc.p + rbytes);
     AlsCgPiece *dpieces = (AlsCgPiece *)((char *)dlongs + lbytes);
@@ -661,7 +661,7 @@ static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begi
     memset(&pa, 0, sizeof pa);
     if (!longs.empty()) {   // scratch of the long rows: state [3][k_pad] per row | partials [k_pad] per piece | r.r | alive flags
         const size_t nl = longs.size(), sfloats = (3 * nl + pieces.size()) * (size_t)kp;
-        CHK(kl_ensure(c, c->als_cg_long, (sfloats + 2 * nl) * sizeof(float)));
+        CHK(ensure_scratch(c, c->als_cg_long, (sfloats + 2 * nl) * sizeof(float)));
         pa.s0 = a.s0; pa.s1 = a.s1;
         pa.pieces = dpieces; pa.rows = dlongs;
         pa.S = a.S; pa.N = a.N; pa.Fin = a.Fin; pa.Fout = Fout; pa.out_row0 = out_row0;
@@ -747,7 +747,7 @@ extern "C" int cmf_als_cg_rows(cmf_ctx *c, int which, int64_t row0, int64_t nrow
     if (!host_f) return fail(CMF_EINVAL, "cmf_als_cg_rows: null output");
     DeviceGuard dg(c->device);
     const size_t bytes = (size_t)nrows * c->kp * sizeof(float);
-    CHK(kl_ensure(c, c->als_cg_ws, bytes));
+    CHK(ensure_scratch(c, c->als_cg_ws, bytes));
     HIPCHK(hipMemsetAsync(c->als_cg_ws.p, 0, bytes, c->stream));
     CHK(als_cg_rows(c, sw, l2, row0, row0 + nrows, cg_steps, (float *)c->als_cg_ws.p, row0));
     HIPCHK(hipMemcpyAsync(host_f, c->als_cg_ws.p, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -772,7 +772,7 @@ extern "C" int cmf_als_nnls_rows(cmf_ctx *c, int64_t nrows, const float *host_H,
     if (nrows == 0) return CMF_OK;
     DeviceGuard dg(c->device);
     const int64_t kp = c->kp, nh = nrows * kp * kp, nv = nrows * kp;
-    CHK(kl_ensure(c, c->als_nnls_ws, (size_t)(nh + 2 * nv) * sizeof(float)));
+    CHK(ensure_scratch(c, c->als_nnls_ws, (size_t)(nh + 2 * nv) * sizeof(float)));
     float *H = (float *)c->als_nnls_ws.p, *g = H + nh, *f = g + nv;
     HIPCHK(hipMemcpyAsync(H, host_H, (size_t)nh * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(g, host_g, (size_t)nv * sizeof(float), hipMemcpyHostToDevice, c->stream));

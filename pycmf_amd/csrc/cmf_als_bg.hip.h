@@ -11,9 +11,10 @@
 //                          values live; 16 bytes of static LDS
 //   als_bg_combine_kernel  S = coef G, or S = S + coef G for the second side of a V sweep: products and sums rounded one by one (no
 //                          fma), so the result does not depend on how a compiler pairs them and a repeated call is bit-identical
-//   als_bg_res_csr_kernel<GL, CH>  wmu_res_csr_kernel with a second sum: one pass over the row image forms s = a_i . b_c in float32
-//                          and accumulates sum w (t - s)^2 AND sum s^2 in float64, one partial of each per workgroup in fixed
-//                          slots (summed in slot order by sum_doubles_kernel); 64 bytes of static LDS
+//   als_bg_res_csr_kernel<GL>  wmu_res_csr_kernel's term with a second sum (policy AlsBgResCsr of csr_reduce, cmf_pairpass.hip.h):
+//                          one pass over the row image forms s = a_i . b_c in float32 and accumulates sum w (t - s)^2 AND sum s^2 in
+//                          float64, one partial of each per workgroup in fixed slots (summed in slot order by sum_doubles_kernel);
+//                          64 bytes of static LDS
 //   als_bg_dot64_kernel    <G_a, G_b>_F of two float64 Grams in one workgroup, fixed order; 2 KB of static LDS
 // The error of such a relation:  E = sum_O w (t - s)^2 + c0 (<A^T A, B^T B>_F - sum_O s^2),  clamped at 0.
 // No atomics; nothing here writes through a scalar path.  c0 = 0 frees the excess arrays: every route is then the code without
@@ -60,52 +61,18 @@ __global__ void als_bg_combine_kernel(float *S, const float *G, float coef, int 
     }
 }
 
-// partials[b] = this workgroup's share of sum w (t - s)^2, partials[gridDim.x + b] = of sum s^2, both over the stored entries
-template <int GL, int CH>
-__global__ __launch_bounds__(256) void als_bg_res_csr_kernel(WCsrView T, const float *A, const float *B, int kp, double *partials) {
-    constexpr int RPW = 64 / GL;
-    const int lane = threadIdx.x & 63;
-    const int gl = lane % GL, gsub = lane / GL;
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int64_t row = wave * RPW + gsub;
-    double acc = 0.0, acs = 0.0;
-    if (row < T.rows) {
-        f32x4 a[CH];
-#pragma unroll
-        for (int c = 0; c < CH; ++c) a[c] = *reinterpret_cast<const f32x4 *>(A + row * kp + 4 * (gl + GL * c));
-        const int64_t beg = T.indptr[row], end = T.indptr[row + 1];
-        for (int64_t q = beg; q < end; ++q) {
-            const int32_t j = T.idx[q];
-            const float t = T.tv[q], w = T.wv[q];
-            float d = 0.f;
-#pragma unroll
-            for (int c = 0; c < CH; ++c) {
-                const f32x4 b = *reinterpret_cast<const f32x4 *>(B + (int64_t)j * kp + 4 * (gl + GL * c));
-                d += a[c][0] * b[0] + a[c][1] * b[1] + a[c][2] * b[2] + a[c][3] * b[3];
-            }
-            d = group_sum<GL>(d);
-            const float e = t - d;
-            if (gl == 0) {
-                acc += (double)(w * (e * e));
-                acs += (double)(d * d);
-            }
-        }
+// sum w (t - s)^2 AND sum s^2 over the stored entries, s = a_i . b_c in float32
+struct AlsBgResCsr {
+    enum { NS = 2, NV = 2 };
+    static __device__ __forceinline__ void add(const float *tw, float d, double *acc) {
+        const float e = tw[0] - d;
+        acc[0] += (double)(tw[1] * (e * e));
+        acc[1] += (double)(d * d);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        acc += __shfl_down(acc, off, 64);
-        acs += __shfl_down(acs, off, 64);
-    }
-    __shared__ double red[2][4];
-    if (lane == 0) {
-        red[0][threadIdx.x >> 6] = acc;
-        red[1][threadIdx.x >> 6] = acs;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partials[blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        partials[gridDim.x + blockIdx.x] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    }
+};
+template <int GL>
+__global__ __launch_bounds__(256) void als_bg_res_csr_kernel(PairCsrView T, const float *A, const float *B, int kp, double *partials) {
+    csr_reduce<GL, AlsBgResCsr>(T, A, B, kp, partials);
 }
 
 __global__ __launch_bounds__(256) void als_bg_dot64_kernel(const double *a, const double *b, int64_t n, double *out) {
@@ -141,7 +108,7 @@ static int als_shared_terms(cmf_ctx *c, const AlsSweep &sw, const float **S, con
     bool bg = false;
     for (int s = 0; s < sw.nrel; ++s) bg = bg || (sw.observed[s] && c->wm_bg[sw.rel[s].which] > 0.0);
     const int n4 = c->kp * c->kp / 4;
-    if (bg) CHK(kl_ensure(c, c->als_bg_s, (size_t)n4 * 16));
+    if (bg) CHK(ensure_scratch(c, c->als_bg_s, (size_t)n4 * 16));
     for (int s = 0; s < sw.nrel; ++s) {   // the order of als_rels: the sum of a V sweep is (coef_x G_u) + (coef_y G_z)
         const AlsRel &r = sw.rel[s];
         if (sw.observed[s] && !(c->wm_bg[r.which] > 0.0)) continue;
@@ -194,7 +161,7 @@ extern "C" int cmf_set_background_weight(cmf_ctx *c, int which, double c0) {
         const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(1024, ((M.nnz >> 2) + 255) / 256));
         if (t == 0) blocks0 = blocks;
         int rc = dev_alloc(c, (void **)&ev[t], std::max<size_t>((size_t)M.nnz * sizeof(float), 16), false);
-        if (rc == CMF_OK) rc = kl_ensure(c, c->wm_part, 2 * 1024 * sizeof(float));
+        if (rc == CMF_OK) rc = ensure_scratch(c, c->wm_part, 2 * 1024 * sizeof(float));
         if (rc != CMF_OK) {
             dev_free(c, ev[0]); dev_free(c, ev[1]);
             return rc;
@@ -240,26 +207,18 @@ static int als_bg_residual_side(cmf_ctx *c, int which, double *out) {
     const int fa = which == 0 ? CMF_U : CMF_V, fb = which == 0 ? CMF_V : CMF_Z;
     const float *A = c->F[fa], *B = c->F[fb];
     const int64_t kk = (int64_t)c->kp * c->kp;
-    CHK(kl_ensure(c, c->wm_small, 64));
-    CHK(kl_ensure(c, c->als_bg64, (size_t)2 * kk * sizeof(double)));
+    CHK(ensure_scratch(c, c->wm_small, 64));
+    CHK(ensure_scratch(c, c->als_bg64, (size_t)2 * kk * sizeof(double)));
     double *sum = (double *)c->wm_small.p, *Ga = (double *)c->als_bg64.p, *Gb = Ga + kk;
     const WCsrDev &M = c->wm_sp[which][0];
-    cmfk::WCsrView v{M.indptr, M.idx, M.pv, M.wv, M.tv, M.rows};
-    const int gl = c->kp / 4, rpw = 64 / gl;
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, ((M.rows + rpw - 1) / rpw + 3) / 4);
-    CHK(kl_ensure(c, c->wm_part, (size_t)2 * blocks * sizeof(double)));
-    double *part = (double *)c->wm_part.p;
+    cmfk::PairCsrView v{M.indptr, M.idx, M.pv, M.wv, M.tv, M.rows};
+    CHK(ensure_scratch(c, c->wm_part, (size_t)2 * csr_reduce_blocks(c, M.rows) * sizeof(double)));
     {
         Timed tm(c, CMF_K_KLMU, 2.0 * (double)M.nnz * (double)c->kp);
-        switch (c->kp) {
-        case 32: hipLaunchKernelGGL((cmfk::als_bg_res_csr_kernel<8, 1>), dim3(blocks), dim3(256), 0, c->stream, v, A, B, c->kp, part); break;
-        case 64: hipLaunchKernelGGL((cmfk::als_bg_res_csr_kernel<16, 1>), dim3(blocks), dim3(256), 0, c->stream, v, A, B, c->kp, part); break;
-        case 128: hipLaunchKernelGGL((cmfk::als_bg_res_csr_kernel<32, 1>), dim3(blocks), dim3(256), 0, c->stream, v, A, B, c->kp, part); break;
-        default: hipLaunchKernelGGL((cmfk::als_bg_res_csr_kernel<64, 1>), dim3(blocks), dim3(256), 0, c->stream, v, A, B, c->kp, part); break;
-        }
-        hipLaunchKernelGGL(cmfk::sum_doubles_kernel, dim3(1), dim3(256), 0, c->stream, (const double *)part, (int64_t)blocks, sum);
-        hipLaunchKernelGGL(cmfk::sum_doubles_kernel, dim3(1), dim3(256), 0, c->stream, (const double *)(part + blocks), (int64_t)blocks, sum + 1);
-        HIPCHK(hipGetLastError());
+        double *part = (double *)c->wm_part.p;
+        CHK(csr_launch_reduce<2>(c, M.rows, part, sum, [&](auto gl, dim3 grid) {
+            hipLaunchKernelGGL((cmfk::als_bg_res_csr_kernel<decltype(gl)::value>), grid, dim3(256), 0, c->stream, v, A, B, c->kp, part);
+        }));
     }
     CHK(gram64(c, A, c->frows_pad[fa], Ga, nullptr));
     CHK(gram64(c, B, c->frows_pad[fb], Gb, nullptr));

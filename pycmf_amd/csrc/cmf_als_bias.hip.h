@@ -216,7 +216,7 @@ static int als_bias_sweep(cmf_ctx *c, int which, int axis, float *out) {
     const int fa = which == 0 ? (axis == 0 ? CMF_U : CMF_V) : (axis == 0 ? CMF_V : CMF_Z);
     const int fb = which == 0 ? (axis == 0 ? CMF_V : CMF_U) : (axis == 0 ? CMF_Z : CMF_V);
     const int64_t np = b.npieces[axis];
-    CHK(kl_ensure(c, c->als_bias_part, std::max<size_t>(16, (size_t)np * 2 * sizeof(double))));
+    CHK(ensure_scratch(c, c->als_bias_part, std::max<size_t>(16, (size_t)np * 2 * sizeof(double))));
     cmfk::AlsBiasArgs a;
     a.pieces = b.pieces[axis];
     a.idx = M.idx; a.tv = M.tv; a.wv = M.wv;
@@ -369,7 +369,7 @@ extern "C" int cmf_als_bias_rows(cmf_ctx *c, int which, int axis, float *host_ou
     CHK(als_bias_vector(c, "cmf_als_bias_rows", which, axis, &vec, &n));
     if (!host_out && n > 0) return fail(CMF_EINVAL, "cmf_als_bias_rows: null output");
     DeviceGuard dg(c->device);
-    CHK(kl_ensure(c, c->als_bias_ws, std::max<size_t>(16, (size_t)n * sizeof(float))));
+    CHK(ensure_scratch(c, c->als_bias_ws, std::max<size_t>(16, (size_t)n * sizeof(float))));
     CHK(als_bias_sweep(c, which, axis, (float *)c->als_bias_ws.p));
     if (n) HIPCHK(hipMemcpyAsync(host_out, c->als_bias_ws.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -432,7 +432,7 @@ extern "C" int cmf_predict_pairs(cmf_ctx *c, int which, int link, int64_t n, con
                         (long long)cols[q], (long long)c->frows[fa], (long long)c->frows[fb]);
     DeviceGuard dg(c->device);
     const size_t ibytes = (size_t)n * sizeof(int64_t);
-    CHK(kl_ensure(c, c->als_bias_ws, 2 * ibytes + (size_t)n * sizeof(float)));
+    CHK(ensure_scratch(c, c->als_bias_ws, 2 * ibytes + (size_t)n * sizeof(float)));
     int64_t *dr = (int64_t *)c->als_bias_ws.p, *dc = dr + n;
     float *dout = (float *)(dc + n);
     HIPCHK(hipMemcpyAsync(dr, rows, ibytes, hipMemcpyHostToDevice, c->stream));

@@ -30,6 +30,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace cmfk;
@@ -406,6 +407,32 @@ static int ensure(cmf_ctx *c, DevBuf &b, size_t bytes) {
     CHK(dev_alloc(c, &b.p, bytes, false));
     b.bytes = bytes;
     return CMF_OK;
+}
+// grow-only scratch buffer of a solver's own: unlike ensure() it leaves the captured graphs of the Frobenius steps alone (nothing
+// of theirs points into it)
+static int ensure_scratch(cmf_ctx *c, DevBuf &b, size_t bytes) {
+    if (b.bytes >= bytes) return CMF_OK;
+    if (b.p) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        dev_free(c, b.p);
+        b.p = nullptr;
+        b.bytes = 0;
+    }
+    CHK(dev_alloc(c, &b.p, bytes, false));
+    b.bytes = bytes;
+    return CMF_OK;
+}
+
+// the runtime factor width as a template argument: f(std::integral_constant<int, KP>()) with KP = k_pad for the widths the fused
+// kernels are built for, 32 | 64 | 128 | 256 (callers have refused wider factors)
+template <class F>
+static void with_kp(int kp, F &&f) {
+    switch (kp) {
+    case 32: f(std::integral_constant<int, 32>()); break;
+    case 64: f(std::integral_constant<int, 64>()); break;
+    case 128: f(std::integral_constant<int, 128>()); break;
+    default: f(std::integral_constant<int, 256>()); break;
+    }
 }
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: remember it per context, not per process
@@ -1941,6 +1968,7 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_comm.hip.h"
 #define CMF_TOPK_HOST
 #include "cmf_topk.hip.h"
+#define CMF_PAIRPASS_HOST   // cmf_pairpass.hip.h, which the next two include
 #define CMF_KLMU_HOST
 #include "cmf_klmu.hip.h"
 #define CMF_WMU_HOST

@@ -212,7 +212,7 @@ extern "C" int cmf_hals_sweep(cmf_ctx *c, int which, const double *N, const doub
     float *hg = host.data() + (size_t)rp * kp;
     for (int i = 0; i < k; ++i)
         for (int j = 0; j < k; ++j) hg[(size_t)i * kp + j] = (float)G[(size_t)i * k + j];
-    CHK(kl_ensure(c, c->hals_ws, host.size() * sizeof(float)));
+    CHK(ensure_scratch(c, c->hals_ws, host.size() * sizeof(float)));
     float *dev = (float *)c->hals_ws.p;
     HIPCHK(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     const int rc = hals_sweep(c, which, dev, dev + (size_t)rp * kp, l1, l2);

@@ -2,13 +2,13 @@
 
     python tools/wmu_timing.py [--out profiles/wmu_timing.json] [--reps 5] [--shapes 65536,256 16384,128] [--csr c5] [--csr-rows N]
 
-The weighted denominator pass (W .* (A B^T)) B is kl_quotient_kernel with w s in place of t / s: the same flops (4 m d k), the
+The weighted denominator pass (W .* (A B^T)) B is the quotient pass's kernel (pairpass_kernel) with w s in place of t / s: the same flops (4 m d k), the
 same tiles, the same 4 bytes per cell streamed.  So the yardstick of every figure is the KL pass on the same context and factors.
 Dense, for every shape (m = d, k), p = 256, synthetic |N(0,1)| data, a Bernoulli(0.3) mask as weights on X, after a warm-up call,
 median and spread of `reps` device-timed repetitions, profiler off:
-  kl_pass_kernel_ms        class "klmu" of a U-only cmf_mu_kl_step: one launch of kl_quotient_kernel
-  wmu_den_kernel_ms        class "klmu" of a U-only cmf_mu_weighted_step: one launch of wmu_pass_kernel<.., WM_DEN>
-  wmu_num_kernel_ms        class "gemm_nn" of the same step: the numerator pass P V (wmu_pass_kernel<.., WM_NUM>)
+  kl_pass_kernel_ms        class "klmu" of a U-only cmf_mu_kl_step: one launch of pairpass_kernel<.., KlQuotient>
+  wmu_den_kernel_ms        class "klmu" of a U-only cmf_mu_weighted_step: one launch of pairpass_kernel<.., WmDen>
+  wmu_num_kernel_ms        class "gemm_nn" of the same step: the numerator pass P V (pairpass_kernel<.., WmNum>)
   wmu_den1_kernel_ms       the denominator pass of the unweighted relation of a weighted fit (W == 1 flag, no W loads)
   wmu_den_over_kl          ratio of the medians; aim: wmu median <= 1.05 x the slowest KL repetition
   step wall times          a full weighted step beside a full KL step and a full Frobenius step (timing off)
