@@ -222,6 +222,35 @@ int cmf_mu_kl_step(cmf_ctx *ctx, double l1, double l2, int update_mask);
 int cmf_kl_divergence(cmf_ctx *ctx, double *dx, double *dy);
 int cmf_mu_kl_layout(cmf_ctx *ctx, int64_t *out4);
 
+/* ---- MU solver, beta-divergence objective (0 <= beta <= 2) -------------------------------------------------------------------
+ *   minimise  D_beta(X || U V^T) + D_beta(Y || V Z^T) + l1 (sum U + sum V + sum Z) + l2 / 2 (|U|^2 + |V|^2 + |Z|^2)
+ *   d_beta(t | s) = (t^beta + (beta - 1) s^beta - beta t s^(beta - 1)) / (beta (beta - 1));  beta = 0 (Itakura-Saito):
+ *   t / s - log(t / s) - 1;  beta = 1: the Kullback-Leibler term above;  t = 0: s^beta / beta
+ * by sklearn's multiplicative update for that beta_loss applied to each block, sweep order V, U, Z with the new V for U and Z.
+ * With EPS = 2^-23, S = A B^T and P = max(S, EPS)^(beta - 2):
+ *   num = (T .* P) B      den = (S .* P) B      F <- F .* (num / reg(den, F))^gamma
+ *   gamma = 1 / (2 - beta) for beta < 1, 1 for 1 <= beta <= 2          reg(den, F) = den + l1 + l2 F, then den == 0 -> EPS
+ * (den takes the unclamped S: it equals sklearn's max(S, EPS)^(beta - 1) wherever S >= EPS, and an all-zero row gives an exact 0).
+ * PRECONDITION: non-negative data and factors, and no zero in the data at beta = 0 (not checked here; the Python layer refuses both).
+ * Both products of a sweep come from ONE pass over A B^T with two accumulator sets (csrc/cmf_betamu.hip.h; 6 m d k flops, against
+ * 8 m d k for two passes); S .* P is never materialised.  Dense images only: a relation held only as native CSR gives
+ * CMF_EUNSUPPORTED (give it a dense image, sparse_mode 1), and so do bound entry weights, a background weight or biases on a relation
+ * the call reads, and k_pad > 256.  beta outside [0, 2], or a sweep whose data has not been set: CMF_EINVAL.  The context stays usable
+ * after each refusal.  No floating-point atomics: a repeated call from the same state is bit-identical.  The call leaves every option,
+ * captured graph and buffer of the other steps as it was; cmf_run is not extended.
+ *   cmf_beta_divergence: *dx = D_beta(X || U V^T) = sum over the valid cells of d_beta(t | max(s, EPS)), *dy likewise (either may be
+ *   NULL); terms in float32, float64 accumulation.
+ *   cmf_mu_beta_products: the two products of one sweep (0 = U, 1 = V, 2 = Z) from the factors on the device into host buffers of
+ *   rows x k_pad floats each (rows of that factor), the slabs of the shares summed in slab order; nothing is updated (tests, the
+ *   timing tool).
+ *   cmf_mu_beta_layout: out4 as cmf_mu_kl_layout (option "kl_split" forces the shares here too); the scratch is the numerator and
+ *   denominator slabs, twice the KL step's.  Option "beta_route" 0 (default: the route the width ships) | 1 the dual-output pass |
+ *   2 two single-output passes.                                                                                                   */
+int cmf_mu_beta_step(cmf_ctx *ctx, double beta, double l1, double l2, int update_mask);
+int cmf_beta_divergence(cmf_ctx *ctx, double beta, double *dx, double *dy);
+int cmf_mu_beta_products(cmf_ctx *ctx, double beta, int sweep, float *num, float *den);
+int cmf_mu_beta_layout(cmf_ctx *ctx, int64_t *out4);
+
 /* ---- MU solver, Frobenius objective with per-entry weights ---------------------------------------------------------------
  * The reference lists "Add support for weight matrices on relations" as an open item (its README).  Here, with fixed
  * non-negative Wx (m x d) and Wy (d x p) -- a 0/1 mask restricts the loss to the observed entries:

@@ -63,6 +63,10 @@ PROTOTYPES = {
     "cmf_mu_kl_step": [_vp, _dbl, _dbl, _i32],
     "cmf_kl_divergence": [_vp, _pd, _pd],
     "cmf_mu_kl_layout": [_vp, _pi64],
+    "cmf_mu_beta_step": [_vp, _dbl, _dbl, _dbl, _i32],
+    "cmf_beta_divergence": [_vp, _dbl, _pd, _pd],
+    "cmf_mu_beta_products": [_vp, _dbl, _i32, _pf, _pf],
+    "cmf_mu_beta_layout": [_vp, _pi64],
     "cmf_set_weight_f64": [_vp, _i32, _pd, _i64, _i64],
     "cmf_set_weight_f32": [_vp, _i32, _pf, _i64, _i64],
     "cmf_set_weighted_csr": [_vp, _i32, _pi64, _pi32, _pd, _pd],
@@ -478,6 +482,30 @@ class Context:
         """(shares of the U sweep, of the V sweep, of the Z sweep, device scratch bytes of a step) of the KL passes."""
         out = (C.c_int64 * 4)()
         check(self._lib.cmf_mu_kl_layout(self._h, out))
+        return tuple(out)
+
+    def mu_beta_step(self, beta, l1, l2, mask=7):
+        """One multiplicative-update iteration (V, U, Z) for the beta-divergence objective, 0 <= beta <= 2."""
+        check(self._lib.cmf_mu_beta_step(self._h, float(beta), l1, l2, mask))
+
+    def beta_divergence(self, beta, want_x=True, want_y=True):
+        """(D_beta(X || U V^T), D_beta(Y || V Z^T)) of the factors on the device; a side that is not asked for comes back as 0.0."""
+        dx, dy = C.c_double(0), C.c_double(0)
+        check(self._lib.cmf_beta_divergence(self._h, float(beta), C.byref(dx) if want_x else None, C.byref(dy) if want_y else None))
+        return dx.value, dy.value
+
+    def mu_beta_products(self, beta, sweep):
+        """(num, den) of one sweep (0 = U, 1 = V, 2 = Z) from the factors on the device, float32 arrays of rows x k_pad; no update."""
+        m, d, p, _ = self.shape
+        rows, kp = (m, d, p)[sweep] if sweep in (0, 1, 2) else 1, self.geometry()[3]
+        num, den = np.zeros((rows, kp), dtype=np.float32), np.zeros((rows, kp), dtype=np.float32)
+        check(self._lib.cmf_mu_beta_products(self._h, float(beta), int(sweep), num.ctypes.data_as(_pf), den.ctypes.data_as(_pf)))
+        return num, den
+
+    def mu_beta_layout(self):
+        """(shares of the U sweep, of the V sweep, of the Z sweep, device scratch bytes of a step) of the beta-divergence passes."""
+        out = (C.c_int64 * 4)()
+        check(self._lib.cmf_mu_beta_layout(self._h, out))
         return tuple(out)
 
     # ---- MU with per-entry weights (csrc/cmf_wmu.hip.h)

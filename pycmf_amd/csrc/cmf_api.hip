@@ -157,6 +157,8 @@ struct cmf_ctx {
     int opt_topk_split = 0; // top-n (cmf_topk.hip.h): force the number of candidate shares (<= 0: fill the chip); the result does not depend on it
     int opt_kl_split = 0;  // KL passes (cmf_klmu.hip.h): force the number of shares of the streamed dimension (<= 0: one workgroup per CU); S = 1 and S > 1 differ in rounding only
     DevBuf kl_slab, kl_small, kl_part; // ... their numerator slabs, column sums (+ partials), float64 partials of the divergence
+    int opt_beta_route = 0; // beta-divergence passes (cmf_betamu.hip.h): 0 the shipped route of the width | 1 the dual-output pass | 2 the two single-output twins (timing tool, tests)
+    DevBuf beta_slab, beta_small, beta_part; // ... their numerator + denominator slabs, the divergence's sum and its float64 partials
     int opt_wmu_split = 0; // weighted passes (cmf_wmu.hip.h): force the number of shares of the streamed dimension, as kl_split does for the KL passes
     int wm_kind[2] = {0, 0};              // per-entry weights of X / Y: 0 none | 1 dense image | 2 CSR (the loss runs over the stored pattern)
     float *wm_w[2] = {nullptr, nullptr}, *wm_p[2] = {nullptr, nullptr}; // dense weights W and P = W .* T, the relation's padded shape
@@ -853,6 +855,7 @@ static void release_problem(cmf_ctx *c) {
     c->spmm_bar = DevBuf(); c->spmm_part = DevBuf();
     c->kl_slab = DevBuf(); c->kl_small = DevBuf(); c->kl_part = DevBuf();
     c->wm_slab = DevBuf(); c->wm_small = DevBuf(); c->wm_part = DevBuf();
+    c->beta_slab = DevBuf(); c->beta_small = DevBuf(); c->beta_part = DevBuf();
     c->hals_ws = DevBuf();
     c->als_h = DevBuf(); c->als_part = DevBuf(); c->als_g = DevBuf(); c->als_sol = DevBuf(); c->als_desc = DevBuf(); c->als_nnls_ws = DevBuf(); c->als_cg_ws = DevBuf();
     c->als_cg_long = DevBuf(); c->als_cg_last[0] = c->als_cg_last[1] = 0;
@@ -1014,6 +1017,8 @@ extern "C" int cmf_set_option(cmf_ctx *c, const char *name, int64_t value) {
         c->opt_spmm_block_cols = std::max<int64_t>(0, value);
     } else if (!strcmp(name, "kl_split")) {
         c->opt_kl_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
+    } else if (!strcmp(name, "beta_route")) {
+        c->opt_beta_route = (int)std::max<int64_t>(0, std::min<int64_t>(value, 2));
     } else if (!strcmp(name, "wmu_split")) {
         c->opt_wmu_split = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     } else if (!strcmp(name, "als_piece")) {
@@ -1973,6 +1978,8 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_klmu.hip.h"
 #define CMF_WMU_HOST
 #include "cmf_wmu.hip.h"
+#define CMF_BETAMU_HOST
+#include "cmf_betamu.hip.h"
 #define CMF_RANK_HOST
 #include "cmf_rank.hip.h"
 #define CMF_HALS_HOST

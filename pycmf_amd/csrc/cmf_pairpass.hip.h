@@ -29,6 +29,12 @@
 //   static double term(s, x0, x1)  reduction: what one valid element adds to the float64 sum
 //   static constexpr bool ADDS     pass: a share may add to a slab another pass of the sweep wrote (acc_slabs is honoured); a
 //                                  policy whose solver keeps the passes of a sweep in slabs of their own says false
+// and optionally (absent: 1 and false -- every instantiation without them compiles to what it compiled to before they existed)
+//   static constexpr int OUTPUTS   2: the DUAL-OUTPUT pass.  static void map2(s, x0, param, float *n, float *d) turns a register into
+//                                  a PAIR; in step 3 every fragment b read from LDS is the A operand of two MFMAs, nacc += b n_r and
+//                                  dacc += b d_r, and the epilogue writes a second slab set (PairPassArgs::out2) laid out like the
+//                                  first.  A B^T is formed once for both products.  IMAGES <= 1, ADDS = false.
+//   static constexpr bool PARAM    map / term take PairPassArgs::param as their third argument instead of x1 (IMAGES <= 1)
 // Arithmetic lives in the policies in a literal form each: the library is built with the compiler's default contraction, so a
 // reshaped expression can round differently.
 //
@@ -57,7 +63,14 @@ struct PairPassArgs {
     // what only some policies read comes last
     const float *img1;       // the second image (IMAGES = 2)
     int acc_slabs;           // ADDS: shares below this one add to what their slab holds
+    float *out2;             // OUTPUTS = 2: the second slab set, [share][rows_pad][KP]
+    float param;             // PARAM / OUTPUTS = 2: the policy's float parameter (cmf_betamu.hip.h: beta)
 };
+
+template <class P, class = void> struct pp_outputs { static constexpr int value = 1; };
+template <class P> struct pp_outputs<P, std::void_t<decltype(P::OUTPUTS)>> { static constexpr int value = P::OUTPUTS; };
+template <class P, class = void> struct pp_param { static constexpr bool value = false; };
+template <class P> struct pp_param<P, std::void_t<decltype(P::PARAM)>> { static constexpr bool value = P::PARAM; };
 
 // sum of v over a 256-thread workgroup in a fixed order (lanes by the shuffle ladder, then the four waves); red: 4 doubles of LDS,
 // which may have held something else until now
@@ -73,6 +86,9 @@ __device__ __forceinline__ double block_sum64(double v, double *red) {
 template <int KP, int TRANS, class P, bool REDUCE>
 __device__ __forceinline__ void pairpass_body(const PairPassArgs &g, f32x4 *tile) {
     constexpr int NIMG = P::IMAGES;
+    constexpr bool DUAL = !REDUCE && pp_outputs<P>::value == 2;
+    constexpr bool PARAM = pp_param<P>::value;
+    static_assert(!(DUAL || PARAM) || NIMG <= 1, "a dual-output or parameterised policy reads at most one image");
     constexpr int CT = PP_TILE_FLOATS / KP;   // streamed rows per LDS tile (32 at KP = 256 ... 256 at KP = 32)
     constexpr int SLOTS = KP / 4;             // float4 slots per row
     constexpr int SW = (SLOTS < 16 ? SLOTS : 16) - 1; // slot ^ (row & SW): rows of one fragment read land on different banks
@@ -99,6 +115,11 @@ __device__ __forceinline__ void pairpass_body(const PairPassArgs &g, f32x4 *tile
     f32x16 nacc[REDUCE ? 1 : KB];
 #pragma unroll
     for (int kb = 0; kb < (REDUCE ? 1 : KB); ++kb) nacc[kb] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    f32x16 dacc[DUAL ? KB : 1]; // the second product of a dual-output pass
+    if constexpr (DUAL) {
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) dacc[kb] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    }
     double dsum = 0.0;
 
     // staging: float4 number i * 256 + tid of the tile (8 per thread)
@@ -167,12 +188,28 @@ __device__ __forceinline__ void pairpass_body(const PairPassArgs &g, f32x4 *tile
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int64_t col = cb + 8 * (r >> 2) + 4 * h + (r & 3);
-                    if (row < g.rows_valid && col < g.cols_valid)
-                        dsum += P::term(acc[r], NIMG > 0 ? x0[r >> 2][r & 3] : 0.f, NIMG > 1 ? x1[r >> 2][r & 3] : 0.f);
+                    if (row < g.rows_valid && col < g.cols_valid) {
+                        if constexpr (PARAM) dsum += P::term(acc[r], NIMG > 0 ? x0[r >> 2][r & 3] : 0.f, g.param);
+                        else dsum += P::term(acc[r], NIMG > 0 ? x0[r >> 2][r & 3] : 0.f, NIMG > 1 ? x1[r >> 2][r & 3] : 0.f);
+                    }
                 }
             } else {
+                f32x16 acc2; // DUAL: the registers of the second product
+                if constexpr (DUAL) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = P::map(acc[r], NIMG > 0 ? x0[r >> 2][r & 3] : 0.f, NIMG > 1 ? x1[r >> 2][r & 3] : 0.f);
+                    for (int r = 0; r < 16; ++r) {
+                        float n, d;
+                        P::map2(acc[r], NIMG > 0 ? x0[r >> 2][r & 3] : 0.f, g.param, &n, &d);
+                        acc[r] = n;
+                        acc2[r] = d;
+                    }
+                } else if constexpr (PARAM) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = P::map(acc[r], NIMG > 0 ? x0[r >> 2][r & 3] : 0.f, g.param);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = P::map(acc[r], NIMG > 0 ? x0[r >> 2][r & 3] : 0.f, NIMG > 1 ? x1[r >> 2][r & 3] : 0.f);
+                }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int brow = sub * 32 + 8 * (r >> 2) + 4 * h + (r & 3); // the streamed row register r stands for in this lane half
@@ -185,13 +222,21 @@ __device__ __forceinline__ void pairpass_body(const PairPassArgs &g, f32x4 *tile
                         if constexpr (W == 4) {
                             const f32x4 b = *(const f32x4 *)p;
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) nacc[jj * 4 + e] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[e], acc[r], nacc[jj * 4 + e], 0, 0, 0);
+                            for (int e = 0; e < 4; ++e) {
+                                nacc[jj * 4 + e] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[e], acc[r], nacc[jj * 4 + e], 0, 0, 0);
+                                if constexpr (DUAL) dacc[jj * 4 + e] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[e], acc2[r], dacc[jj * 4 + e], 0, 0, 0);
+                            }
                         } else if constexpr (W == 2) {
                             const f32x2 b = *(const f32x2 *)p;
                             nacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[0], acc[r], nacc[0], 0, 0, 0);
                             nacc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[1], acc[r], nacc[1], 0, 0, 0);
+                            if constexpr (DUAL) {
+                                dacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[0], acc2[r], dacc[0], 0, 0, 0);
+                                dacc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[1], acc2[r], dacc[1], 0, 0, 0);
+                            }
                         } else {
                             nacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(*p, acc[r], nacc[0], 0, 0, 0);
+                            if constexpr (DUAL) dacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(*p, acc2[r], dacc[0], 0, 0, 0);
                         }
                     }
                 }
@@ -233,11 +278,26 @@ __device__ __forceinline__ void pairpass_body(const PairPassArgs &g, f32x4 *tile
                     *p = v;
                 }
             }
+        if constexpr (DUAL) { // the second slab set: the same map, no adding (a dual policy keeps the passes of a sweep apart)
+            float *dst2 = g.out2 + (int64_t)blockIdx.y * g.slab_stride + row * KP;
+#pragma unroll
+            for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+                for (int r2 = 0; r2 < 16; ++r2) {
+                    const int i = (r2 & 3) + 8 * (r2 >> 2) + 4 * h;
+                    float *p = dst2 + W * (i + 32 * jj);
+                    if constexpr (W == 4) *(f32x4 *)p = f32x4{dacc[jj * 4][r2], dacc[jj * 4 + 1][r2], dacc[jj * 4 + 2][r2], dacc[jj * 4 + 3][r2]};
+                    else if constexpr (W == 2) *(f32x2 *)p = f32x2{dacc[0][r2], dacc[1][r2]};
+                    else *p = dacc[0][r2];
+                }
+        }
     }
 }
 
+// (a dual-output policy at KP = 64 holds two accumulator sets beside the transposed image's addresses: it takes the whole register
+// file of a SIMD, as every policy does from KP = 128 on; the single-output instantiations keep their bounds)
 template <int KP, int TRANS, class P>
-__global__ __launch_bounds__(256, KP >= 128 ? 1 : 2) void pairpass_kernel(PairPassArgs g) {
+__global__ __launch_bounds__(256, KP >= 128 || (KP == 64 && pp_outputs<P>::value == 2) ? 1 : 2) void pairpass_kernel(PairPassArgs g) {
     __shared__ __attribute__((aligned(16))) f32x4 pp_tile[PP_TILE_FLOATS / 4];
     pairpass_body<KP, TRANS, P, false>(g, pp_tile);
 }
@@ -339,9 +399,12 @@ __device__ __forceinline__ void csr_reduce(const PairCsrView &T, const float *A,
 // F <- F * num / reg(den, F), num = the sum of the nslab numerator slabs in slab order; den = the column sums `den[k_pad]`
 // broadcast over the rows (DEN_COLSUM) or the sum of nslab denominator slabs in slab order (DEN_SLABS);
 // reg(den, F) = den + l1 + l2 F, then den == 0 -> eps   (MUSolver._regularized_delta, cmf_solvers.py:212-228)
+// POW (the beta-divergence update, cmf_betamu.hip.h): F <- F * (num / reg(den, F))^gamma for gamma != 1 -- sqrtf at gamma = 1/2,
+// otherwise exp2(gamma log2(q)) on the raw v_log_f32 / v_exp_f32 (q = 0 gives an exact 0 either way)
 enum { DEN_COLSUM = 0, DEN_SLABS = 1 };
-template <int DEN>
-__global__ void pairpass_update_kernel(float *F, const float *num, const float *den, int nslab, int64_t stride, int kp, int64_t n4, float l1, float l2, float eps) {
+template <int DEN, bool POW = false>
+__global__ void pairpass_update_kernel(float *F, const float *num, const float *den, int nslab, int64_t stride, int kp, int64_t n4, float l1, float l2, float eps,
+                                       float gamma = 1.f) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         f32x4 f = reinterpret_cast<f32x4 *>(F)[i];
         f32x4 nu = reinterpret_cast<const f32x4 *>(num)[i];
@@ -356,7 +419,13 @@ __global__ void pairpass_update_kernel(float *F, const float *num, const float *
             if (l1 > 0.f) d += l1;
             if (l2 > 0.f) d = d + l2 * f[e];
             if (d == 0.f) d = eps;
-            f[e] = f[e] * (nu[e] / d);
+            if constexpr (POW) {
+                float q = nu[e] / d;
+                if (gamma == 0.5f) q = sqrtf(q);
+                else if (gamma != 1.f) q = __builtin_amdgcn_exp2f(gamma * __builtin_amdgcn_logf(q));
+                f[e] = f[e] * q;
+            } else
+                f[e] = f[e] * (nu[e] / d);
         }
         reinterpret_cast<f32x4 *>(F)[i] = f;
     }
@@ -433,14 +502,15 @@ static int csr_launch_reduce(cmf_ctx *c, int64_t rows, double *part, double *sum
     return CMF_OK;
 }
 
-// F[f] <- F[f] * num / reg(den, F[f])   (pairpass_update_kernel; den: k_pad column sums, or nslab slabs like num)
-template <int DEN>
-static int pp_update(cmf_ctx *c, int f, const float *num, const float *den, int nslab, double l1, double l2) {
+// F[f] <- F[f] * num / reg(den, F[f])   (pairpass_update_kernel; den: k_pad column sums, or nslab slabs like num; POW: the
+// quotient raised to gamma)
+template <int DEN, bool POW = false>
+static int pp_update(cmf_ctx *c, int f, const float *num, const float *den, int nslab, double l1, double l2, double gamma = 1.0) {
     const int64_t n4 = c->frows_pad[f] * c->kp / 4;
     Timed tm(c, CMF_K_ELEMWISE);
     const unsigned blocks = (unsigned)std::min<int64_t>((n4 + 255) / 256, 4096);
-    hipLaunchKernelGGL((pairpass_update_kernel<DEN>), dim3(blocks), dim3(256), 0, c->stream, c->F[f], num, den, nslab, c->frows_pad[f] * c->kp, c->kp, n4, (float)l1,
-                       (float)l2, CMF_MU_EPS);
+    hipLaunchKernelGGL((pairpass_update_kernel<DEN, POW>), dim3(blocks), dim3(256), 0, c->stream, c->F[f], num, den, nslab, c->frows_pad[f] * c->kp, c->kp, n4, (float)l1,
+                       (float)l2, CMF_MU_EPS, (float)gamma);
     HIPCHK(hipGetLastError());
     return CMF_OK;
 }

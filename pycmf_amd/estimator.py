@@ -12,7 +12,7 @@ from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
-from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_entry_weights, check_hals,
+from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_beta, check_beta_extras, check_beta_data, check_entry_weights, check_hals,
                            check_als, check_als_nn_sweeps, check_als_cg_steps, check_background_weight, check_biases, check_bias_l2)
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
@@ -58,7 +58,14 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     ``loss``: 'frobenius' (default) | 'kullback-leibler' -- the generalised Kullback-Leibler objective
     D(X || U V^T) + D(Y || V Z^T), the usual loss for count data (``sklearn.decomposition.NMF(beta_loss='kullback-leibler',
     solver='mu')`` per block); needs ``solver='mu'``, ``n_gpus=1`` and non-negative X and Y (``ValueError`` otherwise, before any
-    device is touched).  ``beta_loss`` keeps the reference's meaning: parsed and ignored.
+    device is touched).  ``beta_loss`` keeps the reference's meaning: parsed and ignored -- except under
+    ``loss='beta-divergence'``, the one value with which ``beta_loss`` selects the objective: 'itakura-saito' (0; spectra and other
+    scale-free positive data), 'kullback-leibler' (1), 'frobenius' (2) or a number in [0, 2] (0.5 and 1.5: the usual compromises
+    between count noise and Gaussian noise) -- ``sklearn.decomposition.NMF(solver='mu', beta_loss=...)`` per block.  Needs
+    ``solver='mu'``, ``n_gpus=1``, no entry weights, background weights or biases, non-negative X and Y, and at beta = 0 strictly
+    positive ones (a SciPy-sparse relation has implicit zeros) -- ``ValueError`` otherwise, before any device is touched.  A
+    sparse relation is uploaded dense for 0 < beta < 2, beta != 1; beta = 1 and beta = 2 run the Kullback-Leibler and Frobenius
+    paths and give their results bit for bit.
 
     ``x_entry_weights`` / ``y_entry_weights``: fixed non-negative weights per entry of X / Y; the fit then minimises
     1/2 |sqrt(Wx) .* (X - U V^T)|^2 + 1/2 |sqrt(Wy) .* (Y - V Z^T)|^2 -- with a 0/1 mask, the observed entries only, instead of
@@ -103,6 +110,9 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
         n_components = max(X.shape[1], Y.shape[1])
     _check_beta_loss(beta_loss)
     check_loss(loss, solver, n_gpus)
+    if loss == "beta-divergence":
+        beta = check_beta(beta_loss)
+        check_beta_extras(x_entry_weights, y_entry_weights, x_background_weight, y_background_weight, x_biases, y_biases)
     check_entry_weights(x_entry_weights, y_entry_weights, solver, loss, n_gpus)
     check_als_nn_sweeps(als_nn_sweeps, solver)
     check_als_cg_steps(als_cg_steps, solver, [nn for nn, upd in ((U_non_negative, update_U), (V_non_negative, update_V),
@@ -125,6 +135,8 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                          "found X.shape = {}, Y.shape = {}".format(X.shape[1], Y.shape[0]))
     if loss == "kullback-leibler":
         check_kl_data(X, Y)
+    if loss == "beta-divergence":
+        check_beta_data(X, Y, beta, update_U or update_V, update_Z or update_V)
     if x_link not in ("linear", "logit"):
         raise ValueError("No such link %s for x_link" % x_link)
     if y_link not in ("linear", "logit"):
@@ -303,6 +315,10 @@ class CMF(BaseEstimator, TransformerMixin):
     ``loss``: ``'frobenius'`` (default) or ``'kullback-leibler'``: multiplicative updates on the generalised Kullback-Leibler
     objective D(X || U V^T) + D(Y || V Z^T), for count data (the reference documents ``beta_loss='kullback-leibler'`` and does not
     implement it; ``beta_loss`` stays parsed-and-ignored here too).  Needs ``solver='mu'``, ``n_gpus=1`` and non-negative X, Y.
+    ``'beta-divergence'``: the one value under which ``beta_loss`` selects the objective -- ``'itakura-saito'`` (0),
+    ``'kullback-leibler'`` (1), ``'frobenius'`` (2) or a number in [0, 2]; multiplicative updates on D_beta(X || U V^T) +
+    D_beta(Y || V Z^T).  Needs ``solver='mu'``, ``n_gpus=1``, no entry weights, non-negative X, Y and, at beta = 0, strictly
+    positive ones (dense).
     ``reconstruction_err_`` is then sqrt(2 D_x) + sqrt(2 D_y), the stopping test the reference's on
     alpha sqrt(2 D_x) + (1 - alpha) sqrt(2 D_y).
 

@@ -27,14 +27,20 @@ import numpy as np
 from . import _lib
 
 
-LOSSES = ("frobenius", "kullback-leibler")
+LOSSES = ("frobenius", "kullback-leibler", "beta-divergence")
+BETA_NAMES = {"frobenius": 2.0, "kullback-leibler": 1.0, "itakura-saito": 0.0}
 
 
 def check_loss(loss, solver="mu", n_gpus=1):
-    """Validate the ``loss`` keyword (no device is touched): 'frobenius' | 'kullback-leibler'; the latter needs the MU solver and
-    one GPU."""
-    if loss not in LOSSES:
+    """Validate the ``loss`` keyword (no device is touched): 'frobenius' | 'kullback-leibler' | 'beta-divergence'; the latter two
+    need the MU solver and one GPU."""
+    if not isinstance(loss, str) or loss not in LOSSES:
         raise ValueError("Invalid loss parameter: got %r instead of one of %r" % (loss, list(LOSSES)))
+    if loss == "beta-divergence":
+        if solver != "mu":
+            raise ValueError("loss='beta-divergence' is implemented by the multiplicative-update solver only: solver='mu', got %r" % (solver,))
+        if n_gpus != 1:
+            raise ValueError("loss='beta-divergence' runs on one GPU: n_gpus must be 1, got %r (the sharded form is not built)" % (n_gpus,))
     if loss == "kullback-leibler":
         if solver != "mu":
             raise ValueError("loss='kullback-leibler' is implemented by the multiplicative-update solver only: solver='mu', got %r" % (solver,))
@@ -50,6 +56,48 @@ def check_kl_data(X, Y):
         vals = M.data if hasattr(M, "tocsr") else np.asarray(M)
         if vals.size and vals.min() < 0:
             raise ValueError("loss='kullback-leibler' needs non-negative data: %s has negative entries" % name)
+
+
+def check_beta(beta_loss):
+    """``beta_loss`` under ``loss='beta-divergence'`` as a float: 'frobenius' (2) | 'kullback-leibler' (1) | 'itakura-saito' (0) or
+    a finite number in [0, 2]; no device is touched."""
+    if isinstance(beta_loss, str):
+        if beta_loss not in BETA_NAMES:
+            raise ValueError("Invalid beta_loss parameter: got %r instead of one of %r, or a number in [0, 2]" % (beta_loss, list(BETA_NAMES)))
+        return BETA_NAMES[beta_loss]
+    if isinstance(beta_loss, (bool, np.bool_)) or not isinstance(beta_loss, (numbers.Real, np.integer, np.floating)):
+        raise ValueError("Invalid beta_loss parameter: got %r instead of one of %r, or a number in [0, 2]" % (beta_loss, list(BETA_NAMES)))
+    beta = float(beta_loss)
+    if not np.isfinite(beta) or beta < 0 or beta > 2:
+        raise ValueError("loss='beta-divergence' is built for beta_loss in [0, 2], got %r" % (beta_loss,))
+    return beta
+
+
+def check_beta_extras(x_entry_weights=None, y_entry_weights=None, x_background_weight=0.0, y_background_weight=0.0, x_biases=False, y_biases=False):
+    """Entry weights, background weights and biases belong to the Frobenius objective: none of them with loss='beta-divergence'."""
+    for name, v in (("x_entry_weights", x_entry_weights), ("y_entry_weights", y_entry_weights)):
+        if v is not None:
+            raise ValueError("%s is implemented for loss='frobenius' only, not with loss='beta-divergence'" % name)
+    for name, v in (("x_background_weight", x_background_weight), ("y_background_weight", y_background_weight), ("x_biases", x_biases), ("y_biases", y_biases)):
+        if v:
+            raise ValueError("%s belongs to solver='als' and the Frobenius objective: it must stay %r with loss='beta-divergence'" % (name, type(v)(0)))
+
+
+def check_beta_data(X, Y, beta, read_x=True, read_y=True):
+    """The beta-divergence needs non-negative data, and at beta = 0 (Itakura-Saito) no zero in any relation a sweep reads -- the
+    divergence is infinite there; a SciPy-sparse relation has implicit zeros (sklearn refuses the same case)."""
+    for name, M, read in (("X", X, read_x), ("Y", Y, read_y)):
+        if M is None:
+            continue
+        sparse = hasattr(M, "tocsr")
+        vals = M.data if sparse else np.asarray(M)
+        if vals.size and vals.min() < 0:
+            raise ValueError("loss='beta-divergence' needs non-negative data: %s has negative entries" % name)
+        if beta == 0 and read:
+            if sparse and M.nnz < M.shape[0] * M.shape[1]:
+                raise ValueError("beta_loss=0 (Itakura-Saito) needs strictly positive data: %s is sparse, its implicit zeros make the divergence infinite" % name)
+            if vals.size and vals.min() <= 0:
+                raise ValueError("beta_loss=0 (Itakura-Saito) needs strictly positive data: %s has zeros, which make the divergence infinite" % name)
 
 
 class EntryWeights:
@@ -244,7 +292,8 @@ class _HipIterativeSolver:
                  sg_sample_ratio=1., random_state=None, device=0, stream=None, sg_sampler="numpy",
                  cython_variant=False):
         # like the reference, any beta_loss sklearn can parse is accepted and then ignored: only the
-        # Frobenius objective is implemented by either solver (cmf_solvers.py:106, :166)
+        # Frobenius objective is implemented by either solver (cmf_solvers.py:106, :166).  The one exception is
+        # HipMUSolver(loss="beta-divergence"), which parses it into its attribute ``beta``
         if isinstance(beta_loss, str) and beta_loss not in ("frobenius", "kullback-leibler", "itakura-saito"):
             raise ValueError("Invalid beta_loss parameter: got %r" % (beta_loss,))
         self.max_iter = max_iter
@@ -312,6 +361,8 @@ class _HipIterativeSolver:
         key = (id(X), id(Y), m, d, p, k) + self._weights_key()
         if getattr(self, "loss", "frobenius") == "kullback-leibler" and self._bound != key:
             check_kl_data(X, Y)
+        if getattr(self, "loss", "frobenius") == "beta-divergence" and self._bound != key:
+            check_beta_data(X, Y, self.beta, self.update_U or self.update_V, self.update_Z or self.update_V)
         wx, wy = self._resolve_weights(X, Y) if self._bound != key else (None, None)   # ValueError before any device is opened
         if self._ctx is None:
             self._ctx = _lib.Context(self.device, self.stream)
@@ -336,6 +387,8 @@ class _HipIterativeSolver:
                     M = ew.data            # (a sparse relation under dense weights: densified on the host)
                 elif weighted and ew is None and hasattr(M, "tocsr") and self._densify_unweighted:
                     M = M.toarray()        # the unweighted side of a weighted fit takes part with W = 1 through its dense image
+                elif getattr(self, "_beta_path", False) and hasattr(M, "tocsr"):
+                    M = M.toarray()        # the beta-divergence passes read the dense image: the denominator needs every cell
                 self._ctx.set_data(which, M)
                 if ew is not None and ew.kind == "dense":
                     self._ctx.set_weight(which, ew.W)
@@ -486,13 +539,27 @@ class HipMUSolver(_HipIterativeSolver):
     ``x_entry_weights`` / ``y_entry_weights`` (``resolve_entry_weights``): fixed non-negative weights per entry of X / Y on the
     Frobenius objective, 1/2 |sqrt(Wx) .* (X - U V^T)|^2 + 1/2 |sqrt(Wy) .* (Y - V Z^T)|^2 (``cmf_mu_weighted_step``); a 0/1 mask
     or ``'observed'`` fits the observed entries only.  The error metric weighs the residuals the same way; the loop stays on the
-    host."""
+    host.
+
+    ``loss='beta-divergence'``: here, and only here, ``beta_loss`` means something -- 'itakura-saito' (0), 'kullback-leibler' (1),
+    'frobenius' (2) or a number in [0, 2], kept in the attribute ``beta`` (``beta_loss`` itself stays the constant 2.0).  The same
+    sweep order on D_beta(X || U V^T) + D_beta(Y || V Z^T) by sklearn's multiplicative update for that beta per block
+    (``cmf_mu_beta_step``: numerator and denominator from one fused dual-output pass); beta = 1 and beta = 2 are handed to the
+    Kullback-Leibler and Frobenius paths above and give their results bit for bit.  Dense images only (a sparse relation is
+    uploaded dense); no entry weights.  The error metric is sqrt(2 D_beta) per side; the loop stays on the host."""
 
     def __init__(self, *args, loss="frobenius", x_entry_weights=None, y_entry_weights=None, **kwargs):
         check_loss(loss)
-        check_entry_weights(x_entry_weights, y_entry_weights, "mu", loss)
+        self.beta = None
+        if loss == "beta-divergence":
+            self.beta = check_beta(kwargs.get("beta_loss", args[2] if len(args) > 2 else "frobenius"))
+            check_beta_extras(x_entry_weights, y_entry_weights)
+        check_entry_weights(x_entry_weights, y_entry_weights, "mu", "frobenius" if loss == "beta-divergence" else loss)
         super().__init__(*args, **kwargs)
         self.loss = loss
+        # which device path a step takes: beta = 2 and beta = 1 ARE the Frobenius and Kullback-Leibler paths
+        self._path = loss if loss != "beta-divergence" else {2.0: "frobenius", 1.0: "kullback-leibler"}.get(self.beta, "beta-divergence")
+        self._beta_path = self._path == "beta-divergence"
         self.x_entry_weights = x_entry_weights
         self.y_entry_weights = y_entry_weights
         self._weighted = x_entry_weights is not None or y_entry_weights is not None
@@ -515,8 +582,11 @@ class HipMUSolver(_HipIterativeSolver):
         if self._weighted:
             self._ctx.mu_weighted_step(l1_reg, l2_reg, self._update_mask())
             return
-        if self.loss == "kullback-leibler":
+        if self._path == "kullback-leibler":
             self._ctx.mu_kl_step(l1_reg, l2_reg, self._update_mask())
+            return
+        if self._beta_path:
+            self._ctx.mu_beta_step(self.beta, l1_reg, l2_reg, self._update_mask())
             return
         self._ctx.mu_step(l1_reg, l2_reg, self._update_mask())
 
@@ -525,21 +595,24 @@ class HipMUSolver(_HipIterativeSolver):
             X, Y = self._XY
             ex2, ey2 = self._ctx.weighted_residual_sq(X is not None, Y is not None)
             return np.sqrt(max(ex2, 0.0)), np.sqrt(max(ey2, 0.0))
-        if self.loss != "kullback-leibler":
+        if self._path == "frobenius":
             return super()._device_error()
         X, Y = self._XY
-        dx, dy = self._ctx.kl_divergence(X is not None, Y is not None)
+        if self._beta_path:
+            dx, dy = self._ctx.beta_divergence(self.beta, X is not None, Y is not None)
+        else:
+            dx, dy = self._ctx.kl_divergence(X is not None, Y is not None)
         return np.sqrt(2.0 * max(dx, 0.0)), np.sqrt(2.0 * max(dy, 0.0))
 
     def _device_step_error(self, l1_reg, l2_reg, alpha):
-        if self.loss == "kullback-leibler" or self._weighted:
+        if self._path != "frobenius" or self._weighted:
             return None
         ex2, ey2 = self._ctx.mu_step_error(l1_reg, l2_reg, self._update_mask())
         X, Y = self._XY
         return (np.sqrt(ex2) if X is not None else 0.0), (np.sqrt(ey2) if Y is not None else 0.0)
 
     def _run_params(self):
-        if self.loss == "kullback-leibler" or self._weighted:
+        if self._path != "frobenius" or self._weighted:
             return None
         return dict(solver="mu", l1=self.l1_reg, l2=self.l2_reg, alpha_err=self.alpha, update_mask=self._update_mask())
 
