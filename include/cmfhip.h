@@ -482,6 +482,41 @@ int cmf_als_bias_rows(cmf_ctx *ctx, int which, int axis, float *host_out);
 int cmf_als_bias_targets(cmf_ctx *ctx, int which, int image, int64_t nnz, float *host_bt, float *host_bp);
 int cmf_predict_pairs(cmf_ctx *ctx, int which, int link, int64_t n, const int64_t *rows, const int64_t *cols, float *out);
 
+/* ---- ALS with a logistic loss: reweighted row systems over an observed pattern ------------------------------------------------
+ * A relation with CSR weights may be fitted as sigmoid(a . b): labels, clicks, thumbs up / down on the cells that were observed.
+ * Its term of the ALS objective becomes the weighted cross-entropy over the stored pattern,
+ *   sum_O w [softplus(a . b) - t (a . b)],     t in [0, 1] (soft labels allowed), w >= 0,
+ * while the other relation keeps whatever it is (Frobenius observed, Frobenius full, or logistic too); the l2 term is unchanged.
+ * The Jaakkola-Jordan bound  w [softplus(s) - t s] <= 1/2 w kappa(xi) s^2 - w (t - 1/2) s + const,  kappa(xi) = tanh(xi / 2) / (2 xi)
+ * in (0, 1/4], is tight at s = +-xi.  With xi the score under the CURRENT row, the minimiser of the bound for row i solves
+ *   (sum_{e in O_i} w_e kappa_e b_e b_e^T + S + l2 I) f_i = sum_{e in O_i} w_e (t_e - 1/2) b_e + N_i
+ * -- cmf_als_step's system with w kappa for w and w (t - 1/2) for w t; S, N from a full Frobenius side as there.  EVERY ROW SOLVE
+ * LOWERS THE TRUE OBJECTIVE: the Cholesky rows of cmf_als_step with signed factors, and the coordinate-descent rows of
+ * cmf_als_nnls_step with non-negative ones (they start from the current row and never raise the bound).  No step size, no clamp.
+ * (With nn_mask and sweeps = 0 the solved row is only projected, as for the Frobenius loss: no descent guarantee.)
+ *   cmf_set_relation_loss(ctx, which, kind): `which` 0 = X | 1 = Y, kind CMF_LOSS_FROBENIUS (0, the default) | CMF_LOSS_LOGISTIC
+ *   (1).  CMF_EINVAL for another `which` or `kind`.  Cleared by cmf_set_problem.  cmf_get_relation_loss reads it back (CMF_EINVAL
+ *   for a null output).  The targets are not inspected: the caller keeps them in [0, 1].
+ * HONOURED BY cmf_als_step, cmf_als_nnls_step and cmf_als_normal, which returns the majoriser's system at the current row (tests).
+ * With no logistic relation they launch exactly what they launch without this block.  A step (or cmf_als_normal) that sweeps a
+ * logistic relation returns CMF_EUNSUPPORTED when the relation has no CSR weights bound (full, or dense weights: the logistic loss
+ * over every cell is not built), a background weight, or biases; cmf_als_cg_step / cmf_als_cg_rows (the conjugate-gradient rows
+ * would need a per-entry reweighting pass of their own) and cmf_als_bias_step return CMF_EUNSUPPORTED whenever they sweep one.
+ * NOT HONOURED by the MU, HALS and Newton steps, cmf_weighted_residual_sq and cmf_als_residual_sq: they read the relation as the
+ * Frobenius one it also is.  One GPU; cmf_run is not extended.
+ *   cmf_als_logistic_loss(ctx, lx, ly): *lx / *ly = sum_O w [max(s, 0) + log1p(exp(-|s|)) - t s] of X / Y with the factors on the
+ *   device, 0 for a Frobenius relation; a null pointer skips that side.  CMF_EUNSUPPORTED as above for a logistic relation that is
+ *   not observed; k_pad > 256.
+ * The kernels (csrc/cmf_als_logit.hip.h): als_logit_normal_kernel is the normal-equation kernel with the current row in registers
+ * beside every gathered row -- per gathered row one k-long dot product, a fixed-order lane reduction and one tanh; a Frobenius
+ * side's pieces of a mixed V sweep run in the same launch.  The loss cuts every row into pieces of at most 2048 stored entries,
+ * float64 partial sums added in piece order behind a kernel boundary.  No atomics: a repeated call from the same state is
+ * bit-identical.  Kernel time: the normal equations go to CMF_K_ROWHESS (2 nnz k^2 + 2 nnz k flops), the loss to CMF_K_KLMU.   */
+enum { CMF_LOSS_FROBENIUS = 0, CMF_LOSS_LOGISTIC = 1 };
+int cmf_set_relation_loss(cmf_ctx *ctx, int which, int kind);
+int cmf_get_relation_loss(cmf_ctx *ctx, int which, int *kind);
+int cmf_als_logistic_loss(cmf_ctx *ctx, double *lx, double *ly);
+
 /* sharded form: rank g holds rows of X/U and columns of
  * Y/Z, V replicated.  buf is a DEVICE buffer of cmf_v_buf_elems() floats:
  *   [ X_g^T U_g + Y_g Z_g  (d_pad x k_pad) | U_g^T U_g + Z_g^T Z_g (k_pad x k_pad) ]

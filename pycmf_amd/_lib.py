@@ -15,6 +15,7 @@ CMF_U, CMF_V, CMF_Z = 0, 1, 2
 CMF_UPD_U, CMF_UPD_V, CMF_UPD_Z = 1, 2, 4   # update_mask bits (include/cmfhip.h)
 CMF_NN_U, CMF_NN_V, CMF_NN_Z = 1, 2, 4      # nn_mask bits
 LINKS = {"linear": 0, "logit": 1}
+RELATION_LOSSES = {"frobenius": 0, "logistic": 1}   # cmf_set_relation_loss (include/cmfhip.h)
 UPD_U, UPD_V, UPD_Z = 1, 2, 4
 K_GEMM_NN, K_GEMM_TN, K_GEMM_NT, K_ELEMWISE, K_EIGEN = 0, 1, 2, 3, 4
 KERNEL_CLASSES = {"gemm_nn": 0, "gemm_tn": 1, "gemm_nt": 2, "elementwise": 3, "eigen": 4, "gemm_small": 5, "spmm": 6, "rowhess": 7, "gemm_pair": 8, "topk": 9, "klmu": 10}
@@ -97,6 +98,9 @@ PROTOTYPES = {
     "cmf_als_bias_rows": [_vp, _i32, _i32, _pf],
     "cmf_als_bias_targets": [_vp, _i32, _i32, _i64, _pf, _pf],
     "cmf_predict_pairs": [_vp, _i32, _i32, _i64, _pi64, _pi64, _pf],
+    "cmf_set_relation_loss": [_vp, _i32, _i32],
+    "cmf_get_relation_loss": [_vp, _i32, C.POINTER(C.c_int)],
+    "cmf_als_logistic_loss": [_vp, _pd, _pd],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_data_pass_launches": [_vp, _pi64],
     "cmf_mu_route_launches": [_vp, _pi64],
@@ -703,6 +707,25 @@ class Context:
         bt, bp = np.zeros(nnz, dtype=np.float32), np.zeros(nnz, dtype=np.float32)
         check(self._lib.cmf_als_bias_targets(self._h, which, image, nnz, bt.ctypes.data_as(_pf), bp.ctypes.data_as(_pf)))
         return bt, bp
+
+    # ---- ALS with a logistic loss on an observed relation (csrc/cmf_als_logit.hip.h)
+    def set_relation_loss(self, which, kind):
+        """The loss of relation ``which`` (0 X | 1 Y) under ``als_step`` / ``als_nnls_step`` / ``als_normal``: 'frobenius' (0, the
+        default) or 'logistic' (1: weighted cross-entropy of sigmoid(a . b) over the CSR pattern of its weights).  Cleared by
+        ``set_problem``."""
+        check(self._lib.cmf_set_relation_loss(self._h, which, RELATION_LOSSES.get(kind, kind)))
+
+    def get_relation_loss(self, which):
+        kind = C.c_int(0)
+        check(self._lib.cmf_get_relation_loss(self._h, which, C.byref(kind)))
+        return kind.value
+
+    def als_logistic_loss(self, want_x=True, want_y=True):
+        """(L_x, L_y), L = sum_O w [softplus(s) - t s] of the logistic relations with the factors on the device; 0.0 for a
+        Frobenius relation and for a side that is not asked for."""
+        lx, ly = C.c_double(0), C.c_double(0)
+        check(self._lib.cmf_als_logistic_loss(self._h, C.byref(lx) if want_x else None, C.byref(ly) if want_y else None))
+        return lx.value, ly.value
 
     def predict_pairs(self, which, rows, cols, link="linear"):
         """float32[n]: f(offset + r[row] + c[col] + a_row . b_col) of the pairs, a = U, b = V for relation 0 and V, Z for relation 1;

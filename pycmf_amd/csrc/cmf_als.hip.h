@@ -285,6 +285,8 @@ __global__ void als_apply_kernel(float *F, const float *sol, int64_t rows, int k
 
 } // namespace cmfk
 
+#include "cmf_als_logit.hip.h"   // a logistic loss on an observed relation: the reweighted twin of als_normal_kernel, and the loss
+
 // ------------------------------------------------------------------ host side (included by cmf_api.hip behind cmf_ctx)
 #ifdef CMF_ALS_HOST
 
@@ -385,6 +387,9 @@ static int als_plan(cmf_ctx *c, const AlsSweep &sw, int64_t r0, int64_t r1, AlsP
     return CMF_OK;
 }
 
+#define CMF_ALS_LOGIT_HOST
+#include "cmf_als_logit.hip.h"   // relation losses: als_logit_sweep, als_logit_pieces, als_logit_launch_normal and the entry points of its own
+
 static int als_launch_normal(cmf_ctx *c, const cmfk::AlsArgs &a, int64_t npieces, int64_t nnz) {
     if (npieces <= 0) return CMF_OK;
     Timed tm(c, CMF_K_ROWHESS, 2.0 * (double)nnz * c->k * c->k);
@@ -419,6 +424,10 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin
     CHK(als_shared_terms(c, sw, &S, &N));
     AlsPlan pl;
     CHK(als_plan(c, sw, r_begin, r_end, pl));
+    // a sweep that reads a logistic relation: the same pieces with their rows, to als_logit_normal_kernel (cmf_als_logit.hip.h)
+    const bool lg = als_logit_sweep(c, sw);
+    std::vector<AlsLogitPiece> lpieces;
+    if (lg) als_logit_pieces(pl, r_begin, lpieces);
     const int64_t nrows = r_end - r_begin;
     int64_t max_rows = 0, max_pieces = 0;
     std::vector<int64_t> cuts{0};
@@ -433,11 +442,13 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin
     CHK(ensure_scratch(c, c->als_h, (size_t)std::max<int64_t>(1, max_rows) * kk * sizeof(float)));
     CHK(ensure_scratch(c, c->als_part, (size_t)std::max<int64_t>(1, max_pieces) * (kk + kp) * sizeof(float)));
     CHK(ensure_scratch(c, c->als_g, (size_t)rows_pad * kp * sizeof(float)));
-    const size_t pbytes = std::max<size_t>(16, pl.pieces.size() * sizeof(AlsPiece)), fbytes = pl.first.size() * sizeof(int64_t);
+    const size_t pbytes = std::max<size_t>(16, pl.pieces.size() * (lg ? sizeof(AlsLogitPiece) : sizeof(AlsPiece))), fbytes = pl.first.size() * sizeof(int64_t);
     CHK(ensure_scratch(c, c->als_desc, pbytes + fbytes));
     AlsPiece *dpieces = (AlsPiece *)c->als_desc.p;
+    AlsLogitPiece *dlpieces = (AlsLogitPiece *)c->als_desc.p;   // (one list or the other)
     int64_t *dfirst = (int64_t *)((char *)c->als_desc.p + pbytes);
-    if (!pl.pieces.empty()) HIPCHK(hipMemcpyAsync(dpieces, pl.pieces.data(), pl.pieces.size() * sizeof(AlsPiece), hipMemcpyHostToDevice, c->stream));
+    if (lg && !lpieces.empty()) HIPCHK(hipMemcpyAsync(dlpieces, lpieces.data(), lpieces.size() * sizeof(AlsLogitPiece), hipMemcpyHostToDevice, c->stream));
+    if (!lg && !pl.pieces.empty()) HIPCHK(hipMemcpyAsync(dpieces, pl.pieces.data(), pl.pieces.size() * sizeof(AlsPiece), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(dfirst, pl.first.data(), fbytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream)); // the host vectors may go
 
@@ -450,13 +461,24 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin
     float *Hc = (float *)c->als_h.p, *Hp = (float *)c->als_part.p, *grad = (float *)c->als_g.p;
     a.Hp = Hp;
     a.gp = Hp + std::max<int64_t>(1, max_pieces) * kk;
+    AlsLogitArgs la;
+    memset(&la, 0, sizeof la);
+    if (lg) {
+        la.s0 = a.s0; la.s1 = a.s1;
+        la.Hp = a.Hp; la.gp = a.gp;
+        la.F = c->F[sw.f];
+        for (int s = 0, o = 0; s < sw.nrel; ++s)
+            if (sw.observed[s]) (o++ == 0 ? la.logit0 : la.logit1) = als_logit_rel(c, sw.rel[s].which) ? 1 : 0;
+    }
     for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
         const int64_t c0 = cuts[ci], c1 = cuts[ci + 1], nr = c1 - c0, row0 = r_begin + c0;
         const int64_t pbase = pl.first[(size_t)c0], np = pl.first[(size_t)c1] - pbase;
         a.pieces = dpieces + pbase;
+        la.pieces = dlpieces + pbase;
         int64_t nnz = 0;
         for (int64_t p = pbase; p < pbase + np; ++p) nnz += pl.pieces[(size_t)p].len;
-        CHK(als_launch_normal(c, a, np, nnz));
+        if (lg) CHK(als_logit_launch_normal(c, la, np, nnz));
+        else CHK(als_launch_normal(c, a, np, nnz));
         {
             Timed tm(c, CMF_K_ELEMWISE);
             hipLaunchKernelGGL(als_finish_kernel, dim3((unsigned)nr), dim3(256), 0, c->stream, (const float *)Hp, (const float *)a.gp, (const int64_t *)(dfirst + c0),
@@ -533,6 +555,7 @@ static int als_check(cmf_ctx *c, const char *what, double l2, int mask) {
     if (!(l2 > 0.0) || !std::isfinite(l2)) return fail(CMF_EINVAL, "%s: l2 must be positive (a row with fewer than k observations is singular otherwise), got %g", what, l2);
     if (mask <= 0 || mask > 7) return fail(CMF_EINVAL, "%s: update_mask must name at least one of U, V, Z (got %d)", what, mask);
     if (c->kp > 256) return fail(CMF_EUNSUPPORTED, "%s: n_components <= 256 only (k_pad = %d)", what, c->kp);
+    CHK(als_logit_check(c, what, mask));
     if (mask & (CMF_UPD_U | CMF_UPD_V)) CHK(als_relation_ok(c, what, 0));
     if (mask & (CMF_UPD_Z | CMF_UPD_V)) CHK(als_relation_ok(c, what, 1));
     return CMF_OK;
@@ -731,6 +754,7 @@ extern "C" int cmf_als_cg_step(cmf_ctx *c, double l2, int nn_mask, int mask, int
     CHK(als_check(c, "cmf_als_cg_step", l2, mask));
     CHK(als_count_ok("cmf_als_cg_step", "cg_steps", cg_steps));
     CHK(als_count_ok("cmf_als_cg_step", "nn_sweeps", nn_sweeps, 0));
+    CHK(als_logit_check(c, "cmf_als_cg_step", mask, true));
     return als_step(c, l2, nn_mask, mask, nn_sweeps, cg_steps);
 }
 
@@ -740,6 +764,7 @@ extern "C" int cmf_als_cg_rows(cmf_ctx *c, int which, int64_t row0, int64_t nrow
     if (which < 0 || which > 2) return fail(CMF_EINVAL, "cmf_als_cg_rows: bad factor selector");
     CHK(als_check(c, "cmf_als_cg_rows", l2, 1 << which));
     CHK(als_count_ok("cmf_als_cg_rows", "cg_steps", cg_steps));
+    CHK(als_logit_check(c, "cmf_als_cg_rows", 1 << which, true));
     if (row0 < 0 || nrows < 0 || row0 + nrows > c->frows[which]) return fail(CMF_EINVAL, "cmf_als_cg_rows: rows out of range");
     const AlsSweep sw = als_sweep(c, which);
     if (!als_observed(sw)) return fail(CMF_EINVAL, "cmf_als_cg_rows: this sweep has no observed relation: one shared matrix, no per-row systems");

@@ -398,6 +398,9 @@ extern "C" int cmf_als_bias_step(cmf_ctx *c, double l2, int nn_mask, int mask, i
     CHK(als_check(c, "cmf_als_bias_step", l2, mask));
     CHK(als_count_ok("cmf_als_bias_step", "cg_steps", cg_steps, 0));
     CHK(als_count_ok("cmf_als_bias_step", "nn_sweeps", nn_sweeps, 0));
+    if (als_logit_swept(c, mask))
+        return fail(CMF_EUNSUPPORTED, "cmf_als_bias_step: a swept relation has a logistic loss (cmf_set_relation_loss); biases under a logit link are not built: "
+                                      "use cmf_als_step or cmf_als_nnls_step");
     if (!als_bias_any(c)) return als_step(c, l2, nn_mask, mask, nn_sweeps, cg_steps);
     DeviceGuard dg(c->device);
     for (int w = 0; w < 2; ++w) CHK(als_bias_refresh(c, w));   // (written when the biases last changed: nothing to do)

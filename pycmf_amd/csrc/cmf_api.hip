@@ -175,6 +175,7 @@ struct cmf_ctx {
     int64_t als_cg_last[2] = {0, 0};      // long rows and pieces of the last CG sweep (cmf_als_cg_last, tests)
     double wm_bg[2] = {0.0, 0.0};         // background weight c0 of X / Y on the cells outside a CSR pattern (cmf_als_bg.hip.h; 0: none)
     DevBuf als_bg_s, als_bg64;            // ... the shared matrix sum coef Gram of a sweep; float64 Grams of the error's trace term
+    int rel_loss[2] = {0, 0};             // loss of X / Y under the ALS steps (cmf_als_logit.hip.h): CMF_LOSS_FROBENIUS | CMF_LOSS_LOGISTIC
     AlsBias als_bias[2];                  // mu and row / column biases of X / Y (cmf_als_bias.hip.h; off: none)
     int opt_als_bias_piece = 0;           // ... stored entries per piece of a row in the bias passes (0: the default, 2048; > 0 rounded up to 16; < 0: every row is one piece)
     DevBuf als_bias_part, als_bias_ws;    // ... (num, wsum) of every piece; cmf_als_bias_rows' result / the pairs and values of cmf_predict_pairs
@@ -863,6 +864,7 @@ static void release_problem(cmf_ctx *c) {
     c->als_bias_part = DevBuf(); c->als_bias_ws = DevBuf();
     for (int w = 0; w < 2; ++w) {
         c->als_bias[w] = AlsBias();
+        c->rel_loss[w] = 0;
         c->wm_bg[w] = 0.0;
         c->wm_kind[w] = 0; c->wm_w[w] = c->wm_p[w] = nullptr;
         c->wm_sp[w][0] = WCsrDev(); c->wm_sp[w][1] = WCsrDev();

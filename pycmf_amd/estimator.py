@@ -13,7 +13,7 @@ from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
 from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_beta, check_beta_extras, check_beta_data, check_entry_weights, check_hals,
-                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_background_weight, check_biases, check_bias_l2)
+                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_background_weight, check_biases, check_bias_l2, check_logistic)
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -82,6 +82,15 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     minimisation and monotone descent hold for signed factors (``U/V/Z_non_negative=False``); with ``*_non_negative=True`` and
     ``als_nn_sweeps=0`` (default) the solved rows are only projected, which is much weaker.
 
+    ``loss='logistic'`` (``solver='als'``, ``n_gpus=1``): the relations whose link is ``'logit'`` -- at least one -- are fitted as
+    sigmoid(a.b) under the weighted cross-entropy over their OBSERVED entries, sum_O w [softplus(a.b) - t a.b], targets in [0, 1]
+    (soft labels allowed); a relation with a linear link keeps its Frobenius term.  Each logistic relation needs
+    ``*_entry_weights`` that are a SciPy sparse W or ``'observed'`` (labelled subsets, class weights, thumbs up / down), and takes
+    no ``als_cg_steps``, ``*_background_weight`` or ``*_biases`` (``ValueError``, before any device is touched).  Every row solves
+    the Jaakkola-Jordan bound of its loss exactly: monotone descent without a step size, with signed factors and with non-negative
+    ones under ``als_nn_sweeps > 0`` (``HipALSSolver``).  THE STOPPING TEST AND ``reconstruction_err_`` then take from a logistic
+    relation its cross-entropy SUM and from a Frobenius relation what it contributes under ``loss='frobenius'``.
+
     ``als_nn_sweeps``: 0 | n in 1 .. 1024 (``solver='als'`` only; ``ValueError`` otherwise, before any device is touched).  n >= 1:
     the rows of a non-negative factor run n passes of cyclic coordinate descent on their own non-negative least-squares problems
     instead of solve-and-project -- monotone descent with non-negative factors; 4 is the documented choice (``HipALSSolver``).
@@ -141,6 +150,9 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
         raise ValueError("No such link %s for x_link" % x_link)
     if y_link not in ("linear", "logit"):
         raise ValueError("No such link %s for y_link" % y_link)
+    if loss == "logistic":
+        check_logistic(x_link, y_link, x_entry_weights, y_entry_weights, als_cg_steps, x_background_weight, y_background_weight, x_biases,
+                       y_biases, have_x=X is not None and (update_U or update_V), have_y=Y is not None and (update_Z or update_V))
 
     # ---- solver dispatch (cmf.py:433-453)
     common = dict(max_iter=max_iter, tol=tol, verbose=verbose, update_U=update_U, update_V=update_V,
@@ -168,10 +180,11 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
         solver_object = HipHALSSolver(**common)
     elif solver == "als":
         check_als(l1_reg, l2_reg, n_gpus, loss, n_components)
-        if x_link != "linear" or y_link != "linear":
+        if loss != "logistic" and (x_link != "linear" or y_link != "linear"):
             warnings.warn("als solver does not accept link functions other than linear, "
                           "link arguments will be ignored")
-        solver_object = HipALSSolver(U_non_negative=U_non_negative, V_non_negative=V_non_negative, Z_non_negative=Z_non_negative,
+        solver_object = HipALSSolver(loss=loss, x_link=x_link, y_link=y_link,
+                                     U_non_negative=U_non_negative, V_non_negative=V_non_negative, Z_non_negative=Z_non_negative,
                                      x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, nn_sweeps=als_nn_sweeps, cg_steps=als_cg_steps,
                                      x_background_weight=x_background_weight, y_background_weight=y_background_weight,
                                      x_biases=x_biases, y_biases=y_biases, bias_l2=bias_l2, x_bias_init=_x_bias_init,
@@ -381,6 +394,8 @@ class CMF(BaseEstimator, TransformerMixin):
         ``x_background_weight`` / ``y_background_weight`` (``solver='als'``, sparse entry weights): the weight of the cells outside
         the weights' pattern, for implicit feedback; ``reconstruction_err_`` is then sqrt(E_x) + sqrt(E_y) with
         E = sum_O w (t - a.b)^2 + c0 sum_{not O} (a.b)^2.
+        Under ``loss='logistic'`` a relation with a logit link contributes its weighted cross-entropy sum to ``reconstruction_err_``
+        (a Frobenius relation what it contributes otherwise), and ``logistic_loss_`` holds ``(L_x, L_y)``.
         ``x_biases`` / ``y_biases`` / ``bias_l2`` (``solver='als'``, sparse entry weights, no background weight): fit the relation as
         mu + r_i + c_j + a_i.b_j (``collective_matrix_factorization``).  The model then carries ``x_bias_`` / ``y_bias_`` (None, or an
         object with ``.offset``, ``.rows``, ``.cols``), which ``predict``, ``score_entries``, ``top_n``, ``ranks`` and ``transform``
@@ -399,6 +414,7 @@ class CMF(BaseEstimator, TransformerMixin):
         # unweighted sum of the two residual norms, evaluated on the device where the
         # data and the final factors still live (cmf.py:697-698)
         self.reconstruction_err_ = solver_object.reconstruction_error()
+        self.logistic_loss_ = getattr(solver_object, "logistic_loss", None)   # (L_x, L_y) under loss='logistic', else None
         self.x_bias_ = _fitted_bias(getattr(solver_object, "x_bias", None))
         self.y_bias_ = _fitted_bias(getattr(solver_object, "y_bias", None))
         self.bias_l2_ = bias_l2

@@ -27,20 +27,27 @@ import numpy as np
 from . import _lib
 
 
-LOSSES = ("frobenius", "kullback-leibler", "beta-divergence")
+LOSSES = ("frobenius", "kullback-leibler", "beta-divergence")   # of the multiplicative-update solver
+ALS_LOSSES = ("frobenius", "logistic")                           # of the ALS solver
+ALL_LOSSES = LOSSES + tuple(v for v in ALS_LOSSES if v not in LOSSES)
 BETA_NAMES = {"frobenius": 2.0, "kullback-leibler": 1.0, "itakura-saito": 0.0}
 
 
 def check_loss(loss, solver="mu", n_gpus=1):
-    """Validate the ``loss`` keyword (no device is touched): 'frobenius' | 'kullback-leibler' | 'beta-divergence'; the latter two
-    need the MU solver and one GPU."""
-    if not isinstance(loss, str) or loss not in LOSSES:
-        raise ValueError("Invalid loss parameter: got %r instead of one of %r" % (loss, list(LOSSES)))
+    """Validate the ``loss`` keyword (no device is touched): 'frobenius' | 'kullback-leibler' | 'beta-divergence' | 'logistic'; the
+    middle two need the MU solver and one GPU, 'logistic' the ALS solver and one GPU."""
+    if not isinstance(loss, str) or loss not in ALL_LOSSES:
+        raise ValueError("Invalid loss parameter: got %r instead of one of %r" % (loss, list(ALL_LOSSES)))
     if loss == "beta-divergence":
         if solver != "mu":
             raise ValueError("loss='beta-divergence' is implemented by the multiplicative-update solver only: solver='mu', got %r" % (solver,))
         if n_gpus != 1:
             raise ValueError("loss='beta-divergence' runs on one GPU: n_gpus must be 1, got %r (the sharded form is not built)" % (n_gpus,))
+    if loss == "logistic":
+        if solver != "als":
+            raise ValueError("loss='logistic' is implemented by the alternating-least-squares solver only: solver='als', got %r" % (solver,))
+        if n_gpus != 1:
+            raise ValueError("loss='logistic' runs on one GPU: n_gpus must be 1, got %r (the sharded form is not built)" % (n_gpus,))
     if loss == "kullback-leibler":
         if solver != "mu":
             raise ValueError("loss='kullback-leibler' is implemented by the multiplicative-update solver only: solver='mu', got %r" % (solver,))
@@ -56,6 +63,43 @@ def check_kl_data(X, Y):
         vals = M.data if hasattr(M, "tocsr") else np.asarray(M)
         if vals.size and vals.min() < 0:
             raise ValueError("loss='kullback-leibler' needs non-negative data: %s has negative entries" % name)
+
+
+def check_logistic(x_link="linear", y_link="linear", x_entry_weights="observed", y_entry_weights="observed", als_cg_steps=0,
+                   x_background_weight=0.0, y_background_weight=0.0, x_biases=False, y_biases=False, have_x=True, have_y=True):
+    """What ``loss='logistic'`` (solver='als') cannot do, refused before any device is touched.  The relations whose link is 'logit'
+    are the logistic ones: at least one must be; each needs entry weights that resolve to a CSR pattern (a SciPy sparse W or
+    'observed' -- ``have_x`` / ``have_y``: the relation is part of the call), and takes no conjugate-gradient rows, no background
+    weight and no biases.  Returns (x is logistic, y is logistic)."""
+    import scipy.sparse as sp
+    logit = (x_link == "logit", y_link == "logit")
+    if not any(logit):
+        raise ValueError("loss='logistic' fits the relations whose link is 'logit': x_link or y_link must be 'logit', got x_link=%r, "
+                         "y_link=%r" % (x_link, y_link))
+    if als_cg_steps:
+        raise ValueError("als_cg_steps=%r with loss='logistic' is not built (the conjugate-gradient rows have no reweighting pass): "
+                         "als_cg_steps must be 0; use the exact rows or als_nn_sweeps" % (als_cg_steps,))
+    for name, on, have, W, c0, biases in (("x", logit[0], have_x, x_entry_weights, x_background_weight, x_biases),
+                                          ("y", logit[1], have_y, y_entry_weights, y_background_weight, y_biases)):
+        if not on or not have:
+            continue
+        if W is None or not (isinstance(W, str) or sp.issparse(W)):
+            raise ValueError("loss='logistic' with %s_link='logit' needs %s_entry_weights that name the observed entries: pass a SciPy sparse "
+                             "W or 'observed', got %s; the logistic loss over every cell is not built"
+                             % (name, name, "None" if W is None else "a dense array"))
+        if c0:
+            raise ValueError("%s_background_weight=%r on a logistic relation (%s_link='logit') is not built: it must be 0" % (name, c0, name))
+        if biases:
+            raise ValueError("%s_biases=True on a logistic relation (%s_link='logit') is not built: it must be False" % (name, name))
+    return logit
+
+
+def check_logistic_data(values, name):
+    """The targets of a logistic relation (``name`` 'X' | 'Y': the values on its observed entries) must lie in [0, 1]; soft labels
+    are allowed."""
+    v = np.asarray(values, dtype=np.float64)
+    if v.size and not (np.isfinite(v).all() and v.min() >= 0.0 and v.max() <= 1.0):
+        raise ValueError("loss='logistic' needs targets in [0, 1]: the observed entries of %s range over [%g, %g]" % (name, np.nanmin(v), np.nanmax(v)))
 
 
 def check_beta(beta_loss):
@@ -171,7 +215,7 @@ def check_entry_weights(x_entry_weights, y_entry_weights, solver="mu", loss="fro
         return
     if solver not in ("mu", "als"):
         raise ValueError("x_entry_weights / y_entry_weights are implemented by the multiplicative-update solver only: solver='mu', got %r" % (solver,))
-    if loss != "frobenius":
+    if loss not in ("frobenius", "logistic"):
         raise ValueError("x_entry_weights / y_entry_weights are implemented for loss='frobenius' only, got %r" % (loss,))
     if n_gpus != 1:
         raise ValueError("x_entry_weights / y_entry_weights run on one GPU: n_gpus must be 1, got %r (the sharded form is not built)" % (n_gpus,))
@@ -652,8 +696,9 @@ class HipHALSSolver(_HipIterativeSolver):
 
 def check_als(l1_reg=0, l2_reg=1.0, n_gpus=1, loss="frobenius", n_components=None):
     """What the ALS solver cannot do, refused before any device is touched."""
-    if loss != "frobenius":
-        raise ValueError("solver='als' minimises the (weighted) Frobenius objective only: loss must be 'frobenius', got %r" % (loss,))
+    if loss not in ALS_LOSSES:
+        raise ValueError("solver='als' minimises the (weighted) Frobenius objective, or with loss='logistic' the cross-entropy of its "
+                         "logit relations: loss must be 'frobenius' or 'logistic', got %r" % (loss,))
     if not l2_reg > 0:
         raise ValueError("solver='als' needs l2_reg > 0 (a row with fewer observed entries than components has a singular system "
                          "otherwise), got %r" % (l2_reg,))
@@ -739,13 +784,26 @@ class HipALSSolver(HipMUSolver):
     zeros).  The bias blocks follow the update flag of the factor on their axis (r_x: U; c_x, r_y: V; c_y: Z), so a fold-in of new
     rows against a fixed V fits their own biases too.  The error of such a relation is the weighted residual of the biased model.
 
-    Like MU it ignores alpha and the links.  The error metric is the one of a weighted MU fit, sqrt(sum wx e^2) +
-    sqrt(sum wy e^2); the loop stays on the host (``cmf_run`` knows the MU and Newton steps only)."""
+    ``loss='logistic'``: the relations whose link is 'logit' (at least one) are fitted as sigmoid(a.b) under the weighted
+    cross-entropy over their observed entries,  sum_O w [softplus(a.b) - t a.b],  t in [0, 1]; a relation with a linear link keeps
+    its Frobenius term (observed or full), so one V sweep may mix both.  A logistic relation needs a SciPy sparse W or ``'observed'``
+    and takes no ``cg_steps``, background weight or biases (``check_logistic``).  Every row is the exact minimiser of the
+    Jaakkola-Jordan quadratic bound of its loss at the row it has (``cmf_set_relation_loss``): the objective descends monotonically
+    with signed factors, and with non-negative ones under ``nn_sweeps > 0``.  The error metric -- the stopping test and
+    ``reconstruction_error`` -- then takes from a logistic relation its cross-entropy SUM (not a root) and from a Frobenius
+    relation what it takes without this keyword; ``logistic_loss`` holds ``(L_x, L_y)`` of the last evaluation (0 for a Frobenius
+    relation).
+
+    Under ``loss='frobenius'`` it ignores alpha and the links, like MU.  The error metric is the one of a weighted MU fit,
+    sqrt(sum wx e^2) + sqrt(sum wy e^2); the loop stays on the host (``cmf_run`` knows the MU and Newton steps only)."""
 
     _densify_unweighted = False
 
     def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, cg_steps=0, x_background_weight=0.0,
-                 y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None, x_bias_init=None, y_bias_init=None, **kwargs):
+                 y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None, x_bias_init=None, y_bias_init=None,
+                 loss="frobenius", **kwargs):
+        check_loss(loss, "als")
+        check_als(loss=loss)
         check_als_nn_sweeps(nn_sweeps)
         check_als_cg_steps(cg_steps)
         self.x_background_weight = check_background_weight(x_background_weight, "x", "als", x_entry_weights)
@@ -760,11 +818,18 @@ class HipALSSolver(HipMUSolver):
         self.x_bias = self.y_bias = None     # (offset, rows, cols) as float64 after a fit or a step
         super().__init__(*args, loss="frobenius", x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, **kwargs)
         check_als(self.l1_reg, self.l2_reg)
+        # which relations are logistic (loss='logistic': those with a logit link); the device path of the weights is the Frobenius one
+        self.als_loss = loss
+        self._logit = (False, False)
+        if loss == "logistic":
+            self._logit = check_logistic(self.x_link, self.y_link, x_entry_weights, y_entry_weights, cg_steps, self.x_background_weight,
+                                         self.y_background_weight, self.x_biases, self.y_biases, have_x=False, have_y=False)
+        self.logistic_loss = None            # (L_x, L_y) of the last error evaluation under loss='logistic'
         self.nn_sweeps = int(nn_sweeps)
         self.cg_steps = int(cg_steps)
 
     def _weights_key(self):
-        return super()._weights_key() + (self.x_background_weight, self.y_background_weight, self.x_biases, self.y_biases)
+        return super()._weights_key() + (self.x_background_weight, self.y_background_weight, self.x_biases, self.y_biases) + tuple(self._logit)
 
     def _bias_l2(self):
         return self.bias_l2 if self.bias_l2 is not None else float(self.l2_reg)
@@ -784,7 +849,14 @@ class HipALSSolver(HipMUSolver):
     def _resolve_weights(self, X, Y):
         key = (id(X), id(Y))
         if getattr(self, "_als_resolved_for", None) != key:
-            self._als_resolved = tuple(_weights_as_pattern(ew) for ew in super()._resolve_weights(X, Y))
+            raw = super()._resolve_weights(X, Y)
+            if any(self._logit):   # a logistic relation that is part of the call: sparse weights, targets in [0, 1]
+                check_logistic(self.x_link, self.y_link, self.x_entry_weights, self.y_entry_weights, self.cg_steps, self.x_background_weight,
+                               self.y_background_weight, self.x_biases, self.y_biases, have_x=X is not None, have_y=Y is not None)
+                for on, ew, nm in ((self._logit[0], raw[0], "X"), (self._logit[1], raw[1], "Y")):
+                    if on and ew is not None:
+                        check_logistic_data(ew.t, nm)
+            self._als_resolved = tuple(_weights_as_pattern(ew) for ew in raw)
             check_background_floor(self._als_resolved[0], self.x_background_weight, "x")
             check_background_floor(self._als_resolved[1], self.y_background_weight, "y")
             shapes = ((None if X is None else X.shape), (None if Y is None else Y.shape))
@@ -812,6 +884,9 @@ class HipALSSolver(HipMUSolver):
             for which, c0 in ((0, self.x_background_weight), (1, self.y_background_weight)):
                 if c0:
                     ctx.set_background_weight(which, c0)
+            for which, M in ((0, X), (1, Y)):
+                if self._logit[which] and M is not None:
+                    ctx.set_relation_loss(which, "logistic")
             for which, start in enumerate(self._bias_start):
                 if start is not None:
                     ctx.set_biases(which, True, start[0], self._bias_l2())
@@ -840,12 +915,21 @@ class HipALSSolver(HipMUSolver):
             # E = sum_O w (t - s)^2 + c0 (<A^T A, B^T B> - sum_O s^2): the error over every cell; a side without a background
             # gets the bits of the weighted residual from the same call
             ex2, ey2 = self._ctx.als_residual_sq(wx and X is not None, wy and Y is not None)
+        elif any(self._logit):   # (no background, no biases: refused) the squared residual of a logistic relation is never read
+            qx, qy = wx and X is not None and not self._logit[0], wy and Y is not None and not self._logit[1]
+            if qx or qy:
+                ex2, ey2 = self._ctx.weighted_residual_sq(qx, qy)
         elif wx or wy:
             ex2, ey2 = self._ctx.weighted_residual_sq(wx and X is not None, wy and Y is not None)
         if not (wx and wy):   # a relation without weights: every cell with weight 1 -- the plain residual, whatever its layout
             fx2, fy2 = self._ctx.residual_sq("linear", "linear")
             ex2, ey2 = (ex2 if wx else fx2), (ey2 if wy else fy2)
-        return (np.sqrt(max(ex2, 0.0)) if X is not None else 0.0), (np.sqrt(max(ey2, 0.0)) if Y is not None else 0.0)
+        ex, ey = (np.sqrt(max(ex2, 0.0)) if X is not None else 0.0), (np.sqrt(max(ey2, 0.0)) if Y is not None else 0.0)
+        if any(self._logit):   # a logistic relation contributes its cross-entropy sum in place of the root of its squared residuals
+            lx, ly = self._ctx.als_logistic_loss(self._logit[0] and X is not None, self._logit[1] and Y is not None)
+            self.logistic_loss = (lx, ly)
+            ex, ey = (lx if self._logit[0] and X is not None else ex), (ly if self._logit[1] and Y is not None else ey)
+        return ex, ey
 
     def _device_step_error(self, l1_reg, l2_reg, alpha):
         return None
