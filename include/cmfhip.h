@@ -507,7 +507,7 @@ int cmf_predict_pairs(cmf_ctx *ctx, int which, int link, int64_t n, const int64_
  *   cmf_als_logistic_loss(ctx, lx, ly): *lx / *ly = sum_O w [max(s, 0) + log1p(exp(-|s|)) - t s] of X / Y with the factors on the
  *   device, 0 for a Frobenius relation; a null pointer skips that side.  CMF_EUNSUPPORTED as above for a logistic relation that is
  *   not observed; k_pad > 256.
- * The kernels (csrc/cmf_als_logit.hip.h): als_logit_normal_kernel is the normal-equation kernel with the current row in registers
+ * The kernels: the LG = true instance of als_normal_kernel (csrc/cmf_als.hip.h) is the normal-equation kernel with the current row in registers
  * beside every gathered row -- per gathered row one k-long dot product, a fixed-order lane reduction and one tanh; a Frobenius
  * side's pieces of a mixed V sweep run in the same launch.  The loss cuts every row into pieces of at most 2048 stored entries,
  * float64 partial sums added in piece order behind a kernel boundary.  No atomics: a repeated call from the same state is

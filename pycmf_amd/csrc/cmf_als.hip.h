@@ -23,7 +23,7 @@
 //                                                                      longer than "als_cg_piece" entries is cut into pieces
 //                                                                      (als_cg_piece_kernel / als_cg_combine_kernel)
 //
-// The finished systems (als_chunks).  als_normal_kernel<KP>: one 512-thread workgroup per PIECE of a row (at most `als_piece` stored
+// The finished systems (als_chunks).  als_normal_kernel<KP, LG>: one 512-thread workgroup per PIECE of a row (at most `als_piece` stored
 // entries, a multiple of 32) of a CSR image (indptr, idx, pv = w t, wv = w).  The gathered rows b_e are staged 32 at a time through
 // registers into a double-buffered LDS tile, scaled by sqrt(w_e); while they are in registers the owning lanes add p_e b_e to the
 // gradient part g.  H is a rank-32 update per step on v_mfma_f32_32x32x2_f32, both operands read from the ONE staged image:
@@ -35,7 +35,19 @@
 //     waves 4, 6 (base b):  (b, b) (b, b+1) (b, b+2) (b, b+3) (b+3, b+3)                  4 fragments
 //     waves 5, 7 (base b):  (b+1, b+1) (b+1, b+2) (b+1, b+3) (b+2, b+2) (b+2, b+3)        3 fragments
 // Below k_pad = 256 every block is formed (wave (wm, wn) owns block row wm, TN block columns).  Unlike row_hess_kernel there is no
-// dot product with the current row and no targets image: the system does not depend on f_i.
+// targets image, and under LG = false (no relation of the sweep is logistic) no dot product with the current row: the system does
+// not depend on f_i.
+// LG = true: the sweep reads a logistic relation (cmf_als_logit.hip.h), whose system is the one above under w kappa in place of w and
+// w (t - 1/2) in place of w t, kappa taken at the score under the CURRENT row.  The LPR lanes that hold one gathered row in rr[] hold
+// the same columns of the piece's row (AlsPiece::row) of F in fr[] (CPT more f32x4 per lane, loaded once per workgroup).  When a
+// staged tile leaves the registers, a logistic side forms the partial dot sum rr . fr per lane, reduces it over the LPR lanes in the
+// fixed order of group_sum (every lane of the group ends with the same bits of s), and sets
+//     kappa = |s| < 1e-4 ? 0.25f : tanhf(0.5f s) / (2 s),   sq = sqrtf(w kappa),   pe = p - 0.5f w;
+// a Frobenius side's piece of the same launch keeps sq = sqrtf(w), pe = p (logit0 / logit1: uniform over the workgroup).  The
+// reweighting sits in `stage`, not in `gather`: the loads of gather(tl + 2) stay in flight across the MFMAs of step tl, and the dot
+// waits for them only where the registers are consumed anyway.  Everything else is the one body: LG = false compiles to the kernel
+// without any of this, so a fit without a logistic relation pays nothing for it.  It takes sqrtf(w) in `gather`: taken in `stage`,
+// as the logistic instance must, the Frobenius pass measured 0.4 % (C5, k = 256) to 1.1 % (k = 64) slower.
 // A piece writes its partial H (the blocks it formed) and g to its own scratch slot; als_finish_kernel adds the pieces of a row in
 // piece order, mirrors the upper triangle (so H_i is symmetric to the bit), adds S, l2 on the first k diagonal entries and 1 on the
 // padding diagonal, and N_i to g.  No atomics anywhere: a repeated call from the same state is bit-identical.  Padding columns of
@@ -57,12 +69,15 @@ struct AlsPiece {
     int64_t beg;            // first stored entry
     int32_t len;            // entries (1 .. piece length)
     int32_t side;           // 0 | 1: which of the two CSR images of the sweep
+    int64_t row;            // of the swept factor
 };
 struct AlsArgs {
     AlsSide s0, s1;
     const AlsPiece *pieces; // one per workgroup
     float *Hp;              // [piece][KP][KP] partial Hessians (blocks on or above the block diagonal at KP = 256, all blocks below)
     float *gp;              // [piece][KP]
+    const float *F;         // LG: the swept factor, pitch KP: the current rows
+    int logit0, logit1;     // LG: the side is logistic (1) or Frobenius (0)
 };
 
 template <int KP>
@@ -87,7 +102,10 @@ struct AlsIntC {
     static constexpr int value = V;
 };
 
-template <int KP>
+// kappa(s) = tanh(s / 2) / (2 s), 1/4 at 0 (the guard: tanh(s / 2) / (2 s) = 1/4 - s^2 / 48 + ..., below 2^-24 off 1/4 for |s| < 1e-4)
+__device__ __forceinline__ float als_logit_kappa(float s) { return fabsf(s) < 1e-4f ? 0.25f : tanhf(0.5f * s) / (2.0f * s); }
+
+template <int KP, bool LG>
 __global__ __launch_bounds__(512) void als_normal_kernel(AlsArgs g) {
     using C = AlsCfg<KP>;
     __shared__ __attribute__((aligned(16))) float sm[2 * C::TILE];
@@ -95,6 +113,7 @@ __global__ __launch_bounds__(512) void als_normal_kernel(AlsArgs g) {
     const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
     const AlsPiece pc = g.pieces[blockIdx.x];
     const bool second = pc.side != 0;
+    const bool logit = LG && (second ? g.logit1 : g.logit0) != 0;   // uniform over the workgroup
     const int32_t *idx = (second ? g.s1.idx : g.s0.idx) + pc.beg;
     const float *pv = (second ? g.s1.pv : g.s0.pv) + pc.beg;
     const float *wv = (second ? g.s1.wv : g.s0.wv) + pc.beg;
@@ -104,9 +123,19 @@ __global__ __launch_bounds__(512) void als_normal_kernel(AlsArgs g) {
     const bool loader = t < 32 * C::LPR;    // k_pad = 32: half of the threads cover the tile
 
     f32x4 rr[C::CPT], gacc[C::CPT];
-    float sq = 0.f, pe = 0.f;
+    [[maybe_unused]] f32x4 fr[C::CPT];      // LG: the columns this lane holds of every gathered row, of the current row
+    float wq = 0.f, pq = 0.f;               // of the gathered row: p as stored, and w (LG) or its root (the root needs the row under LG)
 #pragma unroll
     for (int q = 0; q < C::CPT; ++q) rr[q] = gacc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (LG) {
+#pragma unroll
+        for (int q = 0; q < C::CPT; ++q) fr[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (logit && loader) {
+            const float *src = g.F + pc.row * KP + 4 * tl16;
+#pragma unroll
+            for (int c = 0; c < C::CPT; ++c) fr[c] = *reinterpret_cast<const f32x4 *>(src + 4 * c * C::LPR);
+        }
+    }
     f32x16 hs[5];
 #pragma unroll
     for (int n = 0; n < 5; ++n)
@@ -136,16 +165,30 @@ __global__ __launch_bounds__(512) void als_normal_kernel(AlsArgs g) {
             const float *src = B + (int64_t)idx[q] * KP + 4 * tl16;
 #pragma unroll
             for (int c = 0; c < C::CPT; ++c) rr[c] = *reinterpret_cast<const f32x4 *>(src + 4 * c * C::LPR);
-            sq = sqrtf(wv[q]);
-            pe = pv[q];
+            if constexpr (LG) wq = wv[q];
+            else wq = sqrtf(wv[q]);
+            pq = pv[q];
         } else {
 #pragma unroll
             for (int c = 0; c < C::CPT; ++c) rr[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-            sq = 0.f;
-            pe = 0.f;
+            wq = 0.f;
+            pq = 0.f;
         }
     };
-    auto stage = [&](int nb) { // registers -> gradient part and the sqrt(w)-scaled LDS image
+    auto stage = [&](int nb) { // registers -> gradient part and the sqrt(w)-scaled (logistic: sqrt(w kappa)-scaled) LDS image
+        float sq = wq, pe = pq;   // LG = false: gather took the root
+        if constexpr (LG) {
+            if (!logit) {
+                sq = sqrtf(wq);
+            } else {       // (all lanes: a row past the end of the piece is zeros with w = 0; the lanes of a row's group stay together)
+                float d = 0.f;
+#pragma unroll
+                for (int c = 0; c < C::CPT; ++c) d += rr[c][0] * fr[c][0] + rr[c][1] * fr[c][1] + rr[c][2] * fr[c][2] + rr[c][3] * fr[c][3];
+                const float s = group_sum<C::LPR>(d);
+                sq = sqrtf(wq * als_logit_kappa(s));
+                pe = pq - 0.5f * wq;
+            }
+        }
         if (!loader) return;
         float *dst = sm + nb * C::TILE + trow * KP + 4 * tl16;
 #pragma unroll
@@ -285,8 +328,6 @@ __global__ void als_apply_kernel(float *F, const float *sol, int64_t rows, int k
 
 } // namespace cmfk
 
-#include "cmf_als_logit.hip.h"   // a logistic loss on an observed relation: the reweighted twin of als_normal_kernel, and the loss
-
 // ------------------------------------------------------------------ host side (included by cmf_api.hip behind cmf_ctx)
 #ifdef CMF_ALS_HOST
 
@@ -335,16 +376,44 @@ static AlsRoute als_route(bool observed, bool nn, int sweeps, int cg_steps) {
     return !nn && cg_steps ? ALS_ROWS_CG : ALS_ROWS_EXACT;
 }
 
-// The launch ladder of the row kernels, templates on k_pad: LAUNCH is a statement that names the instance of cmfk::KERNEL as `kern`.
-#define ALS_LAUNCH_KP(c, KERNEL, WHAT, LAUNCH)                                                                           \
+// The launch ladder of the row kernels, templates on k_pad: LAUNCH is a statement that names the instance of cmfk::KERNEL as `kern`;
+// what follows LAUNCH are the kernel's template arguments behind k_pad.
+#define ALS_LAUNCH_KP(c, KERNEL, WHAT, LAUNCH, ...)                                                                      \
     switch ((c)->kp) {                                                                                                   \
-    case 32: { auto kern = cmfk::KERNEL<32>; LAUNCH; break; }                                                            \
-    case 64: { auto kern = cmfk::KERNEL<64>; LAUNCH; break; }                                                            \
-    case 128: { auto kern = cmfk::KERNEL<128>; LAUNCH; break; }                                                          \
-    case 256: { auto kern = cmfk::KERNEL<256>; LAUNCH; break; }                                                          \
+    case 32: { auto kern = cmfk::KERNEL<32, ##__VA_ARGS__>; LAUNCH; break; }                                             \
+    case 64: { auto kern = cmfk::KERNEL<64, ##__VA_ARGS__>; LAUNCH; break; }                                             \
+    case 128: { auto kern = cmfk::KERNEL<128, ##__VA_ARGS__>; LAUNCH; break; }                                           \
+    case 256: { auto kern = cmfk::KERNEL<256, ##__VA_ARGS__>; LAUNCH; break; }                                           \
     default: return fail(CMF_EUNSUPPORTED, WHAT " built for n_components <= 256 (k_pad = %d)", (c)->kp);                 \
     }                                                                                                                    \
     HIPCHK(hipGetLastError())
+
+// The ladder of the lane-group kernels, templates on GL = k_pad / 4 lanes per factor row (k_pad <= 256: the entry points' check);
+// what follows KERNEL are hipLaunchKernelGGL's arguments behind the kernel.
+#define ALS_LAUNCH_GL(c, KERNEL, ...)                                                                                    \
+    switch ((c)->kp) {                                                                                                   \
+    case 32: hipLaunchKernelGGL((cmfk::KERNEL<8>), __VA_ARGS__); break;                                                  \
+    case 64: hipLaunchKernelGGL((cmfk::KERNEL<16>), __VA_ARGS__); break;                                                 \
+    case 128: hipLaunchKernelGGL((cmfk::KERNEL<32>), __VA_ARGS__); break;                                                \
+    default: hipLaunchKernelGGL((cmfk::KERNEL<64>), __VA_ARGS__); break;                                                 \
+    }
+
+// Rows 0 .. nrows of `nip` CSR images (ip[s]: the rows' indptr) cut into pieces of at most L stored entries: row by row, within a row
+// image by image, piece(r, s, beg, len) per piece in that order.  Returns first[r], the pieces before row r ([nrows + 1]).
+template <class Piece>
+static std::vector<int64_t> als_cut_rows(const std::vector<int64_t> *ip, int nip, int64_t nrows, int64_t L, Piece piece) {
+    std::vector<int64_t> first((size_t)nrows + 1, 0);
+    int64_t n = 0;
+    for (int64_t r = 0; r < nrows; ++r) {
+        first[(size_t)r] = n;
+        for (int s = 0; s < nip; ++s) {
+            const int64_t e = ip[s][(size_t)r + 1];
+            for (int64_t q = ip[s][(size_t)r]; q < e; q += L, ++n) piece(r, s, q, (int32_t)std::min(L, e - q));
+        }
+    }
+    first[(size_t)nrows] = n;
+    return first;
+}
 
 static int als_relation_ok(cmf_ctx *c, const char *what, int which) {
     if (c->wm_kind[which] == WM_DENSE)
@@ -375,26 +444,24 @@ static int als_plan(cmf_ctx *c, const AlsSweep &sw, int64_t r0, int64_t r1, AlsP
     std::vector<int64_t> ip[2];
     CHK(als_fetch_indptr(c, sw, r0, r1, ip));
     pl.pieces.clear();
-    pl.first.assign((size_t)(r1 - r0 + 1), 0);
-    for (int64_t r = 0; r < r1 - r0; ++r) {
-        pl.first[(size_t)r] = (int64_t)pl.pieces.size();
-        for (int s = 0; s < sw.nobs; ++s) {
-            const int64_t b = ip[s][(size_t)r], e = ip[s][(size_t)r + 1];
-            for (int64_t q = b; q < e; q += L) pl.pieces.push_back(cmfk::AlsPiece{q, (int32_t)std::min(L, e - q), s});
-        }
-    }
-    pl.first[(size_t)(r1 - r0)] = (int64_t)pl.pieces.size();
+    pl.first = als_cut_rows(ip, sw.nobs, r1 - r0, L, [&](int64_t r, int s, int64_t beg, int32_t len) {
+        pl.pieces.push_back(cmfk::AlsPiece{beg, len, s, r0 + r});
+    });
     return CMF_OK;
 }
 
-#define CMF_ALS_LOGIT_HOST
-#include "cmf_als_logit.hip.h"   // relation losses: als_logit_sweep, als_logit_pieces, als_logit_launch_normal and the entry points of its own
+#include "cmf_als_logit.hip.h"   // relation losses: als_logit_rel, als_logit_sweep, als_logit_check, the loss kernel and the entry points of its own
 
-static int als_launch_normal(cmf_ctx *c, const cmfk::AlsArgs &a, int64_t npieces, int64_t nnz) {
+// lg: the sweep reads a logistic relation (a.F, a.logit0 / logit1 are set): the instance with the reweighting, and its dot products
+static int als_launch_normal(cmf_ctx *c, const cmfk::AlsArgs &a, int64_t npieces, int64_t nnz, bool lg) {
     if (npieces <= 0) return CMF_OK;
-    Timed tm(c, CMF_K_ROWHESS, 2.0 * (double)nnz * c->k * c->k);
+    Timed tm(c, CMF_K_ROWHESS, 2.0 * (double)nnz * c->k * c->k + (lg ? 2.0 * (double)nnz * c->k : 0.0));
     const dim3 grid((unsigned)npieces), block(512);
-    ALS_LAUNCH_KP(c, als_normal_kernel, "ALS normal equations are", hipLaunchKernelGGL(kern, grid, block, 0, c->stream, a));
+    if (lg) {
+        ALS_LAUNCH_KP(c, als_normal_kernel, "ALS normal equations are", hipLaunchKernelGGL(kern, grid, block, 0, c->stream, a), true);
+    } else {
+        ALS_LAUNCH_KP(c, als_normal_kernel, "ALS normal equations are", hipLaunchKernelGGL(kern, grid, block, 0, c->stream, a), false);
+    }
     return CMF_OK;
 }
 
@@ -424,10 +491,7 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin
     CHK(als_shared_terms(c, sw, &S, &N));
     AlsPlan pl;
     CHK(als_plan(c, sw, r_begin, r_end, pl));
-    // a sweep that reads a logistic relation: the same pieces with their rows, to als_logit_normal_kernel (cmf_als_logit.hip.h)
-    const bool lg = als_logit_sweep(c, sw);
-    std::vector<AlsLogitPiece> lpieces;
-    if (lg) als_logit_pieces(pl, r_begin, lpieces);
+    const bool lg = als_logit_sweep(c, sw);   // a sweep that reads a logistic relation: the LG = true instance of als_normal_kernel
     const int64_t nrows = r_end - r_begin;
     int64_t max_rows = 0, max_pieces = 0;
     std::vector<int64_t> cuts{0};
@@ -442,13 +506,11 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin
     CHK(ensure_scratch(c, c->als_h, (size_t)std::max<int64_t>(1, max_rows) * kk * sizeof(float)));
     CHK(ensure_scratch(c, c->als_part, (size_t)std::max<int64_t>(1, max_pieces) * (kk + kp) * sizeof(float)));
     CHK(ensure_scratch(c, c->als_g, (size_t)rows_pad * kp * sizeof(float)));
-    const size_t pbytes = std::max<size_t>(16, pl.pieces.size() * (lg ? sizeof(AlsLogitPiece) : sizeof(AlsPiece))), fbytes = pl.first.size() * sizeof(int64_t);
+    const size_t pbytes = std::max<size_t>(16, pl.pieces.size() * sizeof(AlsPiece)), fbytes = pl.first.size() * sizeof(int64_t);
     CHK(ensure_scratch(c, c->als_desc, pbytes + fbytes));
     AlsPiece *dpieces = (AlsPiece *)c->als_desc.p;
-    AlsLogitPiece *dlpieces = (AlsLogitPiece *)c->als_desc.p;   // (one list or the other)
     int64_t *dfirst = (int64_t *)((char *)c->als_desc.p + pbytes);
-    if (lg && !lpieces.empty()) HIPCHK(hipMemcpyAsync(dlpieces, lpieces.data(), lpieces.size() * sizeof(AlsLogitPiece), hipMemcpyHostToDevice, c->stream));
-    if (!lg && !pl.pieces.empty()) HIPCHK(hipMemcpyAsync(dpieces, pl.pieces.data(), pl.pieces.size() * sizeof(AlsPiece), hipMemcpyHostToDevice, c->stream));
+    if (!pl.pieces.empty()) HIPCHK(hipMemcpyAsync(dpieces, pl.pieces.data(), pl.pieces.size() * sizeof(AlsPiece), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(dfirst, pl.first.data(), fbytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream)); // the host vectors may go
 
@@ -461,24 +523,18 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin
     float *Hc = (float *)c->als_h.p, *Hp = (float *)c->als_part.p, *grad = (float *)c->als_g.p;
     a.Hp = Hp;
     a.gp = Hp + std::max<int64_t>(1, max_pieces) * kk;
-    AlsLogitArgs la;
-    memset(&la, 0, sizeof la);
     if (lg) {
-        la.s0 = a.s0; la.s1 = a.s1;
-        la.Hp = a.Hp; la.gp = a.gp;
-        la.F = c->F[sw.f];
+        a.F = c->F[sw.f];
         for (int s = 0, o = 0; s < sw.nrel; ++s)
-            if (sw.observed[s]) (o++ == 0 ? la.logit0 : la.logit1) = als_logit_rel(c, sw.rel[s].which) ? 1 : 0;
+            if (sw.observed[s]) (o++ == 0 ? a.logit0 : a.logit1) = als_logit_rel(c, sw.rel[s].which) ? 1 : 0;
     }
     for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
         const int64_t c0 = cuts[ci], c1 = cuts[ci + 1], nr = c1 - c0, row0 = r_begin + c0;
         const int64_t pbase = pl.first[(size_t)c0], np = pl.first[(size_t)c1] - pbase;
         a.pieces = dpieces + pbase;
-        la.pieces = dlpieces + pbase;
         int64_t nnz = 0;
         for (int64_t p = pbase; p < pbase + np; ++p) nnz += pl.pieces[(size_t)p].len;
-        if (lg) CHK(als_logit_launch_normal(c, la, np, nnz));
-        else CHK(als_launch_normal(c, a, np, nnz));
+        CHK(als_launch_normal(c, a, np, nnz, lg));
         {
             Timed tm(c, CMF_K_ELEMWISE);
             hipLaunchKernelGGL(als_finish_kernel, dim3((unsigned)nr), dim3(256), 0, c->stream, (const float *)Hp, (const float *)a.gp, (const int64_t *)(dfirst + c0),

@@ -163,16 +163,13 @@ static int als_bias_plan(cmf_ctx *c, int which) {
     const int64_t L = als_bias_piece_len(c);
     for (int t = 0; t < 2; ++t) {
         const WCsrDev &M = c->wm_sp[which][t];
-        std::vector<int64_t> ip((size_t)M.rows + 1, 0), first((size_t)M.rows + 1, 0);
+        std::vector<int64_t> ip((size_t)M.rows + 1, 0);
         HIPCHK(hipMemcpyAsync(ip.data(), M.indptr, ip.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         std::vector<cmfk::AlsBiasPiece> pieces;
-        for (int64_t r = 0; r < M.rows; ++r) {
-            first[(size_t)r] = (int64_t)pieces.size();
-            for (int64_t q = ip[(size_t)r]; q < ip[(size_t)r + 1]; q += L)
-                pieces.push_back(cmfk::AlsBiasPiece{q, (int32_t)std::min<int64_t>(L, ip[(size_t)r + 1] - q), (int32_t)r});
-        }
-        first[(size_t)M.rows] = (int64_t)pieces.size();
+        const std::vector<int64_t> first = als_cut_rows(&ip, 1, M.rows, L, [&](int64_t r, int, int64_t beg, int32_t len) {
+            pieces.push_back(cmfk::AlsBiasPiece{beg, len, (int32_t)r});
+        });
         if ((int64_t)pieces.size() > INT32_MAX) return fail(CMF_EUNSUPPORTED, "cmf_set_biases: more than 2^31 - 1 pieces (als_bias_piece too small)");
         dev_free(c, b.pieces[t]); dev_free(c, b.first[t]);
         b.pieces[t] = nullptr; b.first[t] = nullptr;
@@ -228,12 +225,7 @@ static int als_bias_sweep(cmf_ctx *c, int which, int axis, float *out) {
     Timed tm(c, CMF_K_KLMU, 2.0 * (double)M.nnz * (double)c->kp);
     if (np > 0) {
         const dim3 grid((unsigned)np), block(256);
-        switch (c->kp) {
-        case 32: hipLaunchKernelGGL((cmfk::als_bias_piece_kernel<8>), grid, block, 0, c->stream, a); break;
-        case 64: hipLaunchKernelGGL((cmfk::als_bias_piece_kernel<16>), grid, block, 0, c->stream, a); break;
-        case 128: hipLaunchKernelGGL((cmfk::als_bias_piece_kernel<32>), grid, block, 0, c->stream, a); break;
-        default: hipLaunchKernelGGL((cmfk::als_bias_piece_kernel<64>), grid, block, 0, c->stream, a); break;
-        }
+        ALS_LAUNCH_GL(c, als_bias_piece_kernel, grid, block, 0, c->stream, a);
     }
     if (M.rows > 0)
         hipLaunchKernelGGL(cmfk::als_bias_combine_kernel, dim3((unsigned)((M.rows + 255) / 256)), dim3(256), 0, c->stream, (const double *)a.part,
@@ -448,12 +440,7 @@ extern "C" int cmf_predict_pairs(cmf_ctx *c, int which, int link, int64_t n, con
         const int gl = c->kp / 4, ng = 256 / gl;
         const dim3 grid((unsigned)((n + ng - 1) / ng)), block(256);
         const float *A = c->F[fa], *B = c->F[fb];
-        switch (c->kp) {
-        case 32: hipLaunchKernelGGL((cmfk::predict_pairs_kernel<8>), grid, block, 0, c->stream, dr, dc, n, A, B, c->kp, rb, cb, off, link, dout); break;
-        case 64: hipLaunchKernelGGL((cmfk::predict_pairs_kernel<16>), grid, block, 0, c->stream, dr, dc, n, A, B, c->kp, rb, cb, off, link, dout); break;
-        case 128: hipLaunchKernelGGL((cmfk::predict_pairs_kernel<32>), grid, block, 0, c->stream, dr, dc, n, A, B, c->kp, rb, cb, off, link, dout); break;
-        default: hipLaunchKernelGGL((cmfk::predict_pairs_kernel<64>), grid, block, 0, c->stream, dr, dc, n, A, B, c->kp, rb, cb, off, link, dout); break;
-        }
+        ALS_LAUNCH_GL(c, predict_pairs_kernel, grid, block, 0, c->stream, dr, dc, n, A, B, c->kp, rb, cb, off, link, dout);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));

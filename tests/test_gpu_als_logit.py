@@ -165,6 +165,42 @@ def test_frobenius_relations_keep_their_kernel(lib):
     ctx.close()
 
 
+@pytest.mark.parametrize("ykind", ["observed", "long rows"])
+@pytest.mark.parametrize("k", [40, 200])                    # k_pad 64 / 256: both wave maps
+def test_frobenius_side_of_a_mixed_launch_is_the_frobenius_kernel(lib, k, ykind):
+    """The V sweep reads X and a Frobenius-observed Y in one launch.  With every stored weight of X zero, a logistic X contributes
+    sqrt(0 kappa) = 0 and p - 0.5 * 0 = 0 and a Frobenius X sqrt(0) = 0 and p = 0: X's pieces add exact zeros in the same piece order
+    either way, and the two systems are the same object (held in float64 first).  Y's pieces went through the instance with the
+    reweighting compiled in (its per-side flag off) in one call and through the instance without it in the other: the same bits.
+    "observed": the file's Y, whose rows hold at most 14 entries (one piece each); "long rows": an 80 x 80 Y with the rows of the
+    file's pattern, twice -- 0, 1, 32, 33 and 70 entries, the tile edge and a ragged third piece under als_piece = 32."""
+    T, W = _pattern()
+    W0 = sp.csr_matrix((np.zeros_like(W.data), W.indices, W.indptr), shape=W.shape)
+    F = _factors(k)
+    if ykind == "observed":
+        Y, Wy = _y("observed")
+    else:
+        rng = np.random.RandomState(6)
+        Y, Wy = _f32(rng.randn(D_, D_)), sp.vstack([W, W]).tocsr()
+        F[2] = _f32(k ** -0.25 * rng.randn(D_, k))
+    Rx, Ry = L.Relation(T, W0), L.Relation(Y, Wy)
+    assert Rx.w.size == W.nnz                               # the pattern is kept: stored entries of weight 0
+    Hl, gl = L.systems(Rx, Ry, *F, "V", L2)
+    Hf, gf = A.systems(Rx, Ry, *F, "V", L2)
+    assert (Hl == Hf).all() and (gl == gf).all()
+    ctx = _context(lib, T, W0, Y, Wy, F, logit=(False, False))
+    lengths = np.concatenate((Rx.row_lengths(True), Ry.row_lengths(False)))
+    assert ctx.als_layout()[2] == sum(-(-int(n) // 32) for n in lengths)      # the pieces of both sides, X's included
+    H0, g0 = ctx.als_normal(V_, 0, D_, L2)
+    ctx.set_relation_loss(0, "logistic")
+    H1, g1 = ctx.als_normal(V_, 0, D_, L2)
+    ctx.close()
+    H32, g32 = A.systems(Rx, Ry, *F, "V", L2, dtype=np.float32)
+    _close("H of the V sweep, X without weight", H0[:, :k, :k], H32, Hf, k)
+    _close("g of the V sweep, X without weight", g0[:, :k], g32, gf, k)
+    assert (H1 == H0).all() and (g1 == g0).all()
+
+
 # ------------------------------------------------------------------ step level
 @pytest.mark.parametrize("nn", [False, True])
 @pytest.mark.parametrize("k", [3, 40])

@@ -1,5 +1,5 @@
-"""Time of the logistic normal-equation pass (als_logit_normal_kernel) beside the Frobenius pass (als_normal_kernel) over the same
-pattern, in the same process.
+"""Time of the logistic normal-equation pass (als_normal_kernel<KP, true>) beside the Frobenius pass (als_normal_kernel<KP, false>) over
+the same pattern, in the same process.
 
     python tools/als_logit_timing.py [--out profiles/als_logit_timing.json] [--reps 5] [--cases case1 c5] [--csr-rows N]
                                      [--csr-k 256 64] [--case1-rows M]
@@ -103,13 +103,14 @@ def main():
     from pycmf_amd import _lib
     if _lib.device_count() < 1:
         raise SystemExit("als_logit_timing: no GPU visible (needs an MI355X)")
-    out = {"what": "logistic normal-equation pass (als_logit_normal_kernel) against the Frobenius pass (als_normal_kernel) over the same "
+    out = {"what": "logistic normal-equation pass (als_normal_kernel<KP, true>) against the Frobenius pass (als_normal_kernel<KP, false>) over the same "
                    "pattern, U sweep, class rowhess; medians of device-timed repetitions", "cases": []}
     if os.path.exists(a.out):                                # cases measured by an earlier call stay (one case per call fits a time limit)
         with open(a.out) as f:
             old = json.load(f)
         redo = {c if c == "case1" or a.csr_rows == 1000000 else "%s_%drows" % (c, a.csr_rows) for c in a.cases}
         out["cases"] = [r for r in old.get("cases", []) if r.get("case") not in redo]
+        out.update({key: v for key, v in old.items() if key not in out})      # (records other runs left beside the cases stay too)
     for case in a.cases:
         if case == "case1":
             m, d, per_row = a.case1_rows, 65536, 1024
