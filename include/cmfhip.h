@@ -395,6 +395,44 @@ int cmf_als_cg_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask, int c
 int cmf_als_cg_rows(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, double l2, int cg_steps, float *host_f);
 int cmf_als_cg_last(cmf_ctx *ctx, int64_t *out2);
 
+/* ---- ALS: matrix-free NON-NEGATIVE rows by projected conjugate gradients -------------------------------------------------------
+ * cmf_als_nncg_step: cmf_als_cg_step's step, except that a swept factor in nn_mask that has an OBSERVED relation never forms H_i
+ * either.  Each of its rows runs nn_cg_steps (1 .. 1024) steps on  min_{f >= 0} 1/2 f^T H_i f - g_i^T f  from the row it has, with
+ * the product H_i x of cmf_als_cg_step (one pass over the row's gathered factor rows; the excess weights and S under a background
+ * weight, exactly as the CG route reads them):
+ *   f <- max(f, 0);  r = g - H f;  p = none
+ *   per step:  free_j = f_j > 0 or r_j > 0;  z = r on free, 0 elsewhere;  rho = z.z;  stop unless rho is positive and finite
+ *              p = z + (rho / rho_old) p  if the step before was a free step and left the same free set,  else p = z
+ *              q = H p;  pq = p.q;  stop unless positive and finite;  alpha = (p.r) / pq;  t = f + alpha p
+ *              no t_j < 0:  FREE step       f = t,  r -= alpha q,  rho_old = rho,  free_old = free
+ *              otherwise    PROJECTED step  f+ = max(t, 0),  d = f+ - f,  hd = H d (a second pass),  dr = d.r,  dhd = d.hd;  stop
+ *                           unless both are positive and finite;  theta = dr / dhd;  theta >= 1: f = f+, r -= hd;  else
+ *                           f = max(f + theta d, 0), r -= theta hd;  p = none
+ * Every step is an exact line search along a descent direction that ends at or before the line's minimiser and leaves f >= 0, so
+ * the objective descends monotonically WITH non-negative factors; one or two passes of O(nnz k) per step, a row is read at most
+ * 2 nn_cg_steps + 1 times, no k x k scratch (csrc/cmf_als_nncg.hip.h: one workgroup per row, all steps in one launch, no atomics;
+ * options "als_cg_lds" and "als_cg_piece" act as on the CG route, long rows take the piece form with 2 + 4 nn_cg_steps launches).
+ * A stopped row keeps what it has, a row without information becomes exact zeros; the result of a row depends on that row (and the
+ * piece length) alone and is deterministic to the bit.
+ * The other factors keep their routes: a signed factor with an observed relation runs cg_steps CG steps (0: the exact rows), a
+ * factor in nn_mask whose relations are all full the route nn_sweeps names.  With no factor on the new route the call IS
+ * cmf_als_cg_step (cg_steps > 0), cmf_als_nnls_step (nn_sweeps > 0) or cmf_als_step, validation and bits.
+ * Validation as cmf_als_step; CMF_EINVAL for cg_steps or nn_sweeps outside 0 .. 1024 or nn_cg_steps outside 1 .. 1024;
+ * CMF_EUNSUPPORTED when a sweep on the new route reads a logistic relation or a relation with biases bound (cmf_als_bias_step
+ * keeps its signature and its routes), and for k_pad > 256.  Kernel time: class CMF_K_ROWHESS, 4 len k flops per pass a row of len
+ * stored entries actually ran (+ 2 k^2 per pass with a full side or a background); the passes stay on the device and
+ * come back only with kernel timing on (behind the timed stretch) or for cmf_als_nncg_passes: a sweep waits for neither.
+ *   cmf_als_nncg_rows (tests): host_f[nrows x k_pad] = the rows that route would write for rows [row0, row0 + nrows) of the sweep
+ *   of factor `which` (in nn_mask or not), from the current factors, which are left unchanged.  CMF_EINVAL for a sweep without an
+ *   observed relation.
+ *   cmf_als_nncg_last (tests, read-only): out2[0] = the long rows, out2[1] = their pieces in the last sweep of that route;
+ *   cmf_als_nncg_passes (measurement, read-only): out2[0] = the passes its rows ran, summed over the rows, out2[1] = the stored
+ *   entries those passes read (sum of len x passes).  Zeros before the first sweep; CMF_EINVAL for a null pointer.              */
+int cmf_als_nncg_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask, int cg_steps, int nn_cg_steps, int nn_sweeps);
+int cmf_als_nncg_rows(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, double l2, int nn_cg_steps, float *host_f);
+int cmf_als_nncg_last(cmf_ctx *ctx, int64_t *out2);
+int cmf_als_nncg_passes(cmf_ctx *ctx, int64_t *out2);
+
 /* ---- ALS for implicit feedback: a background weight on the cells outside the pattern ----------------------------------------
  * Clicks, plays, purchases: every stored target is 1, so a fit over the pattern alone is degenerate, and a fit with every cell at
  * weight 1 lets a click count no more than a non-click.  The standard model (Hu, Koren, Volinsky: "Collaborative Filtering for

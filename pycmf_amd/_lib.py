@@ -87,6 +87,10 @@ PROTOTYPES = {
     "cmf_als_cg_step": [_vp, _dbl, _i32, _i32, _i32, _i32],
     "cmf_als_cg_rows": [_vp, _i32, _i64, _i64, _dbl, _i32, _pf],
     "cmf_als_cg_last": [_vp, _pi64],
+    "cmf_als_nncg_step": [_vp, _dbl, _i32, _i32, _i32, _i32, _i32],
+    "cmf_als_nncg_rows": [_vp, _i32, _i64, _i64, _dbl, _i32, _pf],
+    "cmf_als_nncg_last": [_vp, _pi64],
+    "cmf_als_nncg_passes": [_vp, _pi64],
     "cmf_set_background_weight": [_vp, _i32, _dbl],
     "cmf_get_background_weight": [_vp, _i32, _pd],
     "cmf_als_residual_sq": [_vp, _pd, _pd],
@@ -636,6 +640,34 @@ class Context:
         ``"als_cg_piece"`` entries, which were cut into that many pieces.  Read-only; for the tests."""
         out = np.zeros(2, dtype=np.int64)
         check(self._lib.cmf_als_cg_last(self._h, out.ctypes.data_as(_pi64)))
+        return int(out[0]), int(out[1])
+
+    # ---- matrix-free non-negative rows (csrc/cmf_als_nncg.hip.h)
+    def als_nncg_step(self, l2, nn_mask, mask, cg_steps, nn_cg_steps, nn_sweeps=0):
+        """``als_cg_step`` (``cg_steps=0``: the exact rows) with every swept factor in ``nn_mask`` that has an observed relation
+        fitted by ``nn_cg_steps`` matrix-free projected conjugate-gradient steps per row, from the rows it has clamped at zero; a
+        non-negative factor whose relations are all full keeps the route ``nn_sweeps`` names."""
+        check(self._lib.cmf_als_nncg_step(self._h, l2, nn_mask, mask, cg_steps, nn_cg_steps, nn_sweeps))
+
+    def als_nncg_rows(self, which, row0, nrows, l2, nn_cg_steps):
+        """float32[nrows, k_pad]: the rows ``als_nncg_step`` would write for rows [row0, row0 + nrows) of factor ``which``; the
+        factors are left unchanged."""
+        kp = self.geometry()[3]
+        out = np.zeros((max(nrows, 0), kp), dtype=np.float32)
+        check(self._lib.cmf_als_nncg_rows(self._h, which, row0, nrows, l2, nn_cg_steps, out.ctypes.data_as(_pf)))
+        return out
+
+    def als_nncg_last(self):
+        """(long rows, pieces) of the last sweep of the non-negative CG route (``als_nncg_step`` or ``als_nncg_rows``), as
+        ``als_cg_last``.  Read-only; for the tests."""
+        out = np.zeros(2, dtype=np.int64)
+        check(self._lib.cmf_als_nncg_last(self._h, out.ctypes.data_as(_pi64)))
+        return int(out[0]), int(out[1])
+
+    def als_nncg_passes(self):
+        """(passes, entry passes) of that sweep: the passes its rows ran, summed, and the stored entries those passes read."""
+        out = np.zeros(2, dtype=np.int64)
+        check(self._lib.cmf_als_nncg_passes(self._h, out.ctypes.data_as(_pi64)))
         return int(out[0]), int(out[1])
 
     # ---- ALS for implicit feedback (csrc/cmf_als_bg.hip.h)

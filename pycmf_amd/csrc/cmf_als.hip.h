@@ -22,6 +22,9 @@
 //                                                                      sorts the rows into LDS capacity classes by length; a row
 //                                                                      longer than "als_cg_piece" entries is cut into pieces
 //                                                                      (als_cg_piece_kernel / als_cg_combine_kernel)
+//   rows NNCG     observed; non-negative, nn_cg_steps > 0 (before      no systems: als_nncg_kernel (cmf_als_nncg.hip.h) runs matrix-free
+//                 `sweeps` is looked at; cmf_als_nncg_step only)       projected CG steps per row from the current rows clamped at
+//                                                                      zero, in place; the classes and the pieces of rows CG
 //
 // The finished systems (als_chunks).  als_normal_kernel<KP, LG>: one 512-thread workgroup per PIECE of a row (at most `als_piece` stored
 // entries, a multiple of 32) of a CSR image (indptr, idx, pv = w t, wv = w).  The gathered rows b_e are staged 32 at a time through
@@ -56,6 +59,7 @@
 #include "cmf_kernels.hip.h"
 #include "cmf_als_nnls.hip.h"
 #include "cmf_als_cg.hip.h"
+#include "cmf_als_nncg.hip.h"
 #include "cmf_als_bg.hip.h"
 
 namespace cmfk {
@@ -669,13 +673,101 @@ static int als_cg_long_rows(cmf_ctx *c, cmfk::AlsCgPieceArgs &a, int64_t nlong, 
     return CMF_OK;
 }
 
+// The launches of the non-negative rows (cmf_als_nncg.hip.h) behind the plan of als_cg_rows: one launch per capacity class, then the
+// long rows -- 2 launches for r = g - H f and 4 per step (piece, combine A, piece, combine B).  The passes every row ran stay on the
+// device; they come back (4 bytes a row) only for cmf_als_nncg_passes, or with kernel timing on, behind the timed stretch, to charge
+// 4 len k flops per pass (+ 2 k^2 with a full side): a sweep without either waits for nothing.
+static int als_nncg_count(cmf_ctx *c) {
+    if (c->als_nncg_counted) return CMF_OK;
+    const size_t n = c->als_nncg_lens.size();
+    std::vector<int32_t> passes(n, 0);
+    if (n) {
+        HIPCHK(hipMemcpyAsync(passes.data(), c->als_nncg_passes.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    int64_t total = 0, entry_passes = 0;
+    for (size_t r = 0; r < n; ++r) {
+        total += passes[r];
+        entry_passes += (int64_t)c->als_nncg_lens[r] * passes[r];
+    }
+    c->als_nncg_last[2] = total;
+    c->als_nncg_last[3] = entry_passes;
+    c->als_nncg_counted = true;
+    return CMF_OK;
+}
+
+static int als_nncg_launches(cmf_ctx *c, const cmfk::AlsCgArgs &a, const std::vector<int64_t> *ip, int nobs, const std::vector<int64_t> *list,
+                             const int64_t *caps, const int64_t *drows, const cmfk::AlsCgLongRow *dlongs, const cmfk::AlsCgPiece *dpieces,
+                             const std::vector<cmfk::AlsCgLongRow> &longs, int64_t npieces, int64_t nrows) {
+    using namespace cmfk;
+    const int kp = c->kp, steps = a.steps;
+    const size_t nl = longs.size();
+    CHK(ensure_scratch(c, c->als_nncg_passes, (size_t)nrows * sizeof(int32_t)));
+    HIPCHK(hipMemsetAsync(c->als_nncg_passes.p, 0, (size_t)nrows * sizeof(int32_t), c->stream));
+    AlsNncgArgs na;
+    na.a = a;
+    na.passes = (int32_t *)c->als_nncg_passes.p;
+    AlsNncgLongArgs pa;
+    memset(&pa, 0, sizeof pa);
+    if (nl) {   // scratch of the long rows: state [5][k_pad] per row | partials [k_pad] per piece | a record per row
+        const size_t sfloats = (5 * nl + (size_t)npieces) * (size_t)kp;
+        CHK(ensure_scratch(c, c->als_cg_long, sfloats * sizeof(float) + nl * sizeof(AlsNncgRow)));
+        pa.s0 = a.s0; pa.s1 = a.s1;
+        pa.pieces = dpieces; pa.rows = dlongs;
+        pa.S = a.S; pa.N = a.N; pa.Fin = a.Fin; pa.Fout = a.Fout; pa.out_row0 = a.out_row0;
+        pa.state = (float *)c->als_cg_long.p;
+        pa.partial = pa.state + 5 * nl * (size_t)kp;
+        pa.info = (AlsNncgRow *)(pa.state + sfloats);
+        pa.passes = na.passes;
+        pa.l2 = a.l2; pa.k = a.k;
+    }
+    c->als_nncg_lens.assign((size_t)nrows, 0);
+    for (int64_t r = 0; r < nrows; ++r)
+        for (int s = 0; s < nobs; ++s) c->als_nncg_lens[(size_t)r] += (int32_t)(ip[s][(size_t)r + 1] - ip[s][(size_t)r]);
+    c->als_nncg_counted = false;
+    bool timed = false;
+    {
+        Timed tm(c, CMF_K_ROWHESS, 0.0);
+        timed = tm.on;
+        int64_t done = 0;
+        for (int q = 0; q <= ALS_CG_CLASSES; ++q) {
+            const int64_t n = (int64_t)list[q].size();
+            na.a.rows = drows + done;
+            na.a.cap = (int)caps[q];
+            done += n;
+            if (n <= 0) continue;
+            const size_t lds = 4 * (size_t)als_cg_fixed_floats(kp) + (size_t)na.a.cap * als_cg_entry_bytes(kp);
+            const dim3 grid((unsigned)n), block(256);
+            ALS_LAUNCH_KP(c, als_nncg_kernel, "the non-negative conjugate-gradient row solve is",
+                          CHK(allow_big_lds(c, (const void *)kern, ALS_CG_LDS_TOTAL)); hipLaunchKernelGGL(kern, grid, block, lds, c->stream, na));
+        }
+        if (nl) {
+            const dim3 pgrid((unsigned)npieces), cgrid((unsigned)nl), block(256);
+            for (int s = 0; s <= 2 * steps; ++s) {
+                pa.stage = s == 0 ? 0 : 2 - (s & 1);
+                pa.last = s == 2 * steps ? 1 : 0;
+                ALS_LAUNCH_KP(c, als_nncg_piece_kernel, "the non-negative conjugate-gradient row solve is", hipLaunchKernelGGL(kern, pgrid, block, 0, c->stream, pa));
+                ALS_LAUNCH_KP(c, als_nncg_combine_kernel, "the non-negative conjugate-gradient row solve is", hipLaunchKernelGGL(kern, cgrid, block, 0, c->stream, pa));
+            }
+        }
+    }
+    if (timed) {   // (the scope has recorded its events: the read-back is not in the timed stretch)
+        CHK(als_nncg_count(c));
+        c->pending.back().flops = 4.0 * (double)c->als_nncg_last[3] * c->k + (a.S ? 2.0 * (double)c->als_nncg_last[2] * c->k * c->k : 0.0);
+    }
+    return CMF_OK;
+}
+
 // rows CG: rows [r_begin, r_end) of the sweep (which has an observed relation) by `steps` CG steps from the rows of c->F[f];
 // row r goes to Fout + (r - out_row0) * k_pad (in place: Fout = c->F[f], out_row0 = 0 -- the gathered factors are the other ones).
 // The rows are sorted into capacity classes by their stored entries: capacity / 8, / 4, / 2 and the whole capacity keep the
 // gathered rows in LDS (shorter rows: more workgroups per CU), longer rows stream; one launch per class.  A row with more than
 // als_cg_piece_len entries goes to none of them: it is cut into pieces (cmf_als_cg.hip.h), all such rows of the sweep together.
-static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin, int64_t r_end, int steps, float *Fout, int64_t out_row0) {
+// nn: the non-negative rows of cmf_als_nncg.hip.h instead (the same classes, the same pieces; the passes every row ran come back to
+// the host, which charges the passes actually run).
+static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin, int64_t r_end, int steps, float *Fout, int64_t out_row0, bool nn = false) {
     using namespace cmfk;
+    const char *what = nn ? "cmf_als_nncg_step" : "cmf_als_cg_step";
     const int kp = c->kp;
     const int64_t nrows = r_end - r_begin;
     AlsCgArgs a;
@@ -699,11 +791,11 @@ static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begi
     for (int64_t r = 0; r < nrows; ++r) {
         int64_t len = 0;
         for (int s = 0; s < sw.nobs; ++s) len += ip[s][(size_t)r + 1] - ip[s][(size_t)r];
-        if (len > INT32_MAX) return fail(CMF_EUNSUPPORTED, "cmf_als_cg_step: a row with more than 2^31 - 1 stored entries");
+        if (len > INT32_MAX) return fail(CMF_EUNSUPPORTED, "%s: a row with more than 2^31 - 1 stored entries", what);
         nnz += len;
         if (len > L) {
             const int64_t np = (len + L - 1) / L;
-            if ((int64_t)pieces.size() + np > INT32_MAX) return fail(CMF_EUNSUPPORTED, "cmf_als_cg_step: more than 2^31 - 1 pieces of long rows (als_cg_piece too small)");
+            if ((int64_t)pieces.size() + np > INT32_MAX) return fail(CMF_EUNSUPPORTED, "%s: more than 2^31 - 1 pieces of long rows (als_cg_piece too small)", what);
             const int32_t slot = (int32_t)longs.size();
             longs.push_back(AlsCgLongRow{r_begin + r, (int32_t)pieces.size(), (int32_t)np});
             for (int64_t q = 0; q < len; q += L) pieces.push_back(AlsCgPiece{slot, (int32_t)q, (int32_t)std::min(L, len - q), 0});
@@ -713,8 +805,9 @@ static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begi
         while (q < ALS_CG_CLASSES && len > caps[q]) ++q;
         list[q].push_back(r_begin + r);
     }
-    c->als_cg_last[0] = (int64_t)longs.size();
-    c->als_cg_last[1] = (int64_t)pieces.size();
+    int64_t *last = nn ? c->als_nncg_last : c->als_cg_last;
+    last[0] = (int64_t)longs.size();
+    last[1] = (int64_t)pieces.size();
     std::vector<int64_t> all;
     all.reserve((size_t)nrows);
     for (int q = 0; q <= ALS_CG_CLASSES; ++q) all.insert(all.end(), list[q].begin(), list[q].end());
@@ -736,6 +829,7 @@ static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begi
     a.l2 = (float)l2;
     a.k = c->k;
     a.steps = steps;
+    if (nn) return als_nncg_launches(c, a, ip, sw.nobs, list, caps, drows, dlongs, dpieces, longs, (int64_t)pieces.size(), nrows);
     AlsCgPieceArgs pa;
     memset(&pa, 0, sizeof pa);
     if (!longs.empty()) {   // scratch of the long rows: state [3][k_pad] per row | partials [k_pad] per piece | r.r | alive flags
@@ -762,8 +856,9 @@ static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begi
 }
 
 // sweeps == 0: the solved rows of the factors in nn_mask are projected; sweeps > 0: those factors are swept by coordinate descent;
-// cg_steps > 0: a signed factor with an observed relation runs that many CG steps per row instead of the exact solves
-static int als_step(cmf_ctx *c, double l2, int nn_mask, int mask, int sweeps, int cg_steps = 0) {
+// cg_steps > 0: a signed factor with an observed relation runs that many CG steps per row instead of the exact solves;
+// nn_cg_steps > 0: a non-negative factor with an observed relation runs that many projected CG steps per row (cmf_als_nncg.hip.h)
+static int als_step(cmf_ctx *c, double l2, int nn_mask, int mask, int sweeps, int cg_steps = 0, int nn_cg_steps = 0) {
     DeviceGuard dg(c->device);
     const int bits[3] = {CMF_UPD_V, CMF_UPD_U, CMF_UPD_Z}, fs[3] = {CMF_V, CMF_U, CMF_Z}; // sweep order V, U, Z (cmf_solvers.py:248-263)
     const int nnb[3] = {CMF_NN_V, CMF_NN_U, CMF_NN_Z};
@@ -772,6 +867,10 @@ static int als_step(cmf_ctx *c, double l2, int nn_mask, int mask, int sweeps, in
         if (!(mask & bits[s]) || c->frows[f] <= 0) continue;
         const bool nn = (nn_mask & nnb[s]) != 0;
         const AlsSweep sw = als_sweep(c, f);
+        if (nn && nn_cg_steps && als_observed(sw)) {
+            CHK(als_cg_rows(c, sw, l2, 0, c->frows[f], nn_cg_steps, c->F[f], 0, true));
+            continue;
+        }
         switch (als_route(als_observed(sw), nn, sweeps, cg_steps)) {
         case ALS_SHARED_EXACT: CHK(als_sweep_shared(c, sw, l2, nn)); break;
         case ALS_SHARED_HALS: CHK(als_nnls_sweep_shared(c, f, l2, sweeps)); break;
@@ -841,6 +940,81 @@ extern "C" int cmf_als_cg_last(cmf_ctx *c, int64_t *out2) {
     if (!c || !out2) return fail(CMF_EINVAL, "cmf_als_cg_last: null context or output");
     out2[0] = c->als_cg_last[0];
     out2[1] = c->als_cg_last[1];
+    return CMF_OK;
+}
+
+// What the non-negative CG rows cannot sweep: a logistic relation (no reweighting pass) and a relation with biases bound
+static int als_nncg_sweep_ok(cmf_ctx *c, const char *what, const AlsSweep &sw) {
+    for (int s = 0; s < sw.nrel; ++s) {
+        const int w = sw.rel[s].which;
+        const char *nm = w == 0 ? "X" : "Y";
+        if (als_logit_rel(c, w))
+            return fail(CMF_EUNSUPPORTED, "%s: %s has a logistic loss; the non-negative conjugate-gradient rows have no reweighting pass: use cmf_als_nnls_step", what, nm);
+        if (c->als_bias[w].on)
+            return fail(CMF_EUNSUPPORTED, "%s: %s has biases bound; the non-negative conjugate-gradient rows under biases are not built: use cmf_als_bias_step", what, nm);
+    }
+    return CMF_OK;
+}
+
+extern "C" int cmf_als_nncg_step(cmf_ctx *c, double l2, int nn_mask, int mask, int cg_steps, int nn_cg_steps, int nn_sweeps) {
+    NEED_PROBLEM(c);
+    CHK(als_check(c, "cmf_als_nncg_step", l2, mask));
+    CHK(als_count_ok("cmf_als_nncg_step", "cg_steps", cg_steps, 0));
+    CHK(als_count_ok("cmf_als_nncg_step", "nn_cg_steps", nn_cg_steps));
+    CHK(als_count_ok("cmf_als_nncg_step", "nn_sweeps", nn_sweeps, 0));
+    const int bits[3] = {CMF_UPD_U, CMF_UPD_V, CMF_UPD_Z}, nnb[3] = {CMF_NN_U, CMF_NN_V, CMF_NN_Z}, fs[3] = {CMF_U, CMF_V, CMF_Z};
+    bool any = false;
+    for (int s = 0; s < 3; ++s) {
+        if (!(mask & bits[s]) || !(nn_mask & nnb[s]) || c->frows[fs[s]] <= 0) continue;
+        const AlsSweep sw = als_sweep(c, fs[s]);
+        if (!als_observed(sw)) continue;
+        CHK(als_nncg_sweep_ok(c, "cmf_als_nncg_step", sw));
+        any = true;
+    }
+    if (!any) {   // no factor on the new route: the entry point that names the routes left
+        if (cg_steps) return cmf_als_cg_step(c, l2, nn_mask, mask, cg_steps, nn_sweeps);
+        return nn_sweeps ? cmf_als_nnls_step(c, l2, nn_mask, mask, nn_sweeps) : cmf_als_step(c, l2, nn_mask, mask);
+    }
+    if (cg_steps) CHK(als_logit_check(c, "cmf_als_nncg_step", mask, true));
+    return als_step(c, l2, nn_mask, mask, nn_sweeps, cg_steps, nn_cg_steps);
+}
+
+// test entry: the rows the non-negative CG route would write for rows [row0, row0 + nrows) of sweep `which`; the factors are left alone
+extern "C" int cmf_als_nncg_rows(cmf_ctx *c, int which, int64_t row0, int64_t nrows, double l2, int nn_cg_steps, float *host_f) {
+    NEED_PROBLEM(c);
+    if (which < 0 || which > 2) return fail(CMF_EINVAL, "cmf_als_nncg_rows: bad factor selector");
+    CHK(als_check(c, "cmf_als_nncg_rows", l2, 1 << which));
+    CHK(als_count_ok("cmf_als_nncg_rows", "nn_cg_steps", nn_cg_steps));
+    if (row0 < 0 || nrows < 0 || row0 + nrows > c->frows[which]) return fail(CMF_EINVAL, "cmf_als_nncg_rows: rows out of range");
+    const AlsSweep sw = als_sweep(c, which);
+    if (!als_observed(sw)) return fail(CMF_EINVAL, "cmf_als_nncg_rows: this sweep has no observed relation: one shared matrix, no per-row systems");
+    CHK(als_nncg_sweep_ok(c, "cmf_als_nncg_rows", sw));
+    if (nrows == 0) return CMF_OK;
+    if (!host_f) return fail(CMF_EINVAL, "cmf_als_nncg_rows: null output");
+    DeviceGuard dg(c->device);
+    const size_t bytes = (size_t)nrows * c->kp * sizeof(float);
+    CHK(ensure_scratch(c, c->als_cg_ws, bytes));
+    HIPCHK(hipMemsetAsync(c->als_cg_ws.p, 0, bytes, c->stream));
+    CHK(als_cg_rows(c, sw, l2, row0, row0 + nrows, nn_cg_steps, (float *)c->als_cg_ws.p, row0, true));
+    HIPCHK(hipMemcpyAsync(host_f, c->als_cg_ws.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CMF_OK;
+}
+
+// test entries: the long rows and the pieces of the last non-negative CG sweep (or cmf_als_nncg_rows call); the passes its rows ran
+// and the stored entries those passes read
+extern "C" int cmf_als_nncg_last(cmf_ctx *c, int64_t *out2) {
+    if (!c || !out2) return fail(CMF_EINVAL, "cmf_als_nncg_last: null context or output");
+    out2[0] = c->als_nncg_last[0];
+    out2[1] = c->als_nncg_last[1];
+    return CMF_OK;
+}
+extern "C" int cmf_als_nncg_passes(cmf_ctx *c, int64_t *out2) {
+    if (!c || !out2) return fail(CMF_EINVAL, "cmf_als_nncg_passes: null context or output");
+    DeviceGuard dg(c->device);
+    CHK(als_nncg_count(c));
+    out2[0] = c->als_nncg_last[2];
+    out2[1] = c->als_nncg_last[3];
     return CMF_OK;
 }
 

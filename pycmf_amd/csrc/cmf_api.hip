@@ -173,6 +173,10 @@ struct cmf_ctx {
     int opt_als_cg_piece = 0;             // ... stored entries per piece of a long row (rows with more are cut; 0: the default, 2048; > 0 rounded up to 16; < 0: no row is cut)
     DevBuf als_cg_long;                   // ... the long rows' state (f, r, p, r.r, alive) and the partial sums of their pieces
     int64_t als_cg_last[2] = {0, 0};      // long rows and pieces of the last CG sweep (cmf_als_cg_last, tests)
+    int64_t als_nncg_last[4] = {0, 0, 0, 0}; // non-negative CG rows (cmf_als_nncg.hip.h): long rows, pieces, passes and entry passes (sum of stored entries x passes) of the last sweep
+    DevBuf als_nncg_passes;               // ... the passes every row of the sweep ran
+    std::vector<int32_t> als_nncg_lens;   // ... the stored entries of those rows; als_nncg_counted: als_nncg_last[2 .. 3] hold that sweep's sums
+    bool als_nncg_counted = true;
     double wm_bg[2] = {0.0, 0.0};         // background weight c0 of X / Y on the cells outside a CSR pattern (cmf_als_bg.hip.h; 0: none)
     DevBuf als_bg_s, als_bg64;            // ... the shared matrix sum coef Gram of a sweep; float64 Grams of the error's trace term
     int rel_loss[2] = {0, 0};             // loss of X / Y under the ALS steps (cmf_als_logit.hip.h): CMF_LOSS_FROBENIUS | CMF_LOSS_LOGISTIC
@@ -860,6 +864,8 @@ static void release_problem(cmf_ctx *c) {
     c->hals_ws = DevBuf();
     c->als_h = DevBuf(); c->als_part = DevBuf(); c->als_g = DevBuf(); c->als_sol = DevBuf(); c->als_desc = DevBuf(); c->als_nnls_ws = DevBuf(); c->als_cg_ws = DevBuf();
     c->als_cg_long = DevBuf(); c->als_cg_last[0] = c->als_cg_last[1] = 0;
+    c->als_nncg_passes = DevBuf(); for (int q = 0; q < 4; ++q) c->als_nncg_last[q] = 0;
+    c->als_nncg_lens.clear(); c->als_nncg_counted = true;
     c->als_bg_s = DevBuf(); c->als_bg64 = DevBuf();
     c->als_bias_part = DevBuf(); c->als_bias_ws = DevBuf();
     for (int w = 0; w < 2; ++w) {

@@ -13,7 +13,7 @@ from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
 from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_beta, check_beta_extras, check_beta_data, check_entry_weights, check_hals,
-                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_background_weight, check_biases, check_bias_l2, check_logistic)
+                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_als_nn_cg_steps, check_background_weight, check_biases, check_bias_l2, check_logistic)
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -43,7 +43,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                     device=0, sg_sampler="numpy", n_gpus=1, _return_solver=False, loss="frobenius",
                                     x_entry_weights=None, y_entry_weights=None, als_nn_sweeps=0, als_cg_steps=0,
                                     x_background_weight=0.0, y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None,
-                                    _x_bias_init=None, _y_bias_init=None):
+                                    _x_bias_init=None, _y_bias_init=None, als_nn_cg_steps=0):
     """Factorise X ~ f(U V^T) and Y ~ f(V Z^T) with a shared V on an MI355X.
 
     Same contract as the reference function (pycmf/cmf.py:215-456): returns
@@ -101,6 +101,12 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     factorising their k x k systems -- still a monotone descent, far cheaper per iteration; 6 is the documented choice
     (``HipALSSolver``).  Non-negative factors keep the route ``als_nn_sweeps`` names, unweighted sweeps the shared inverse.
 
+    ``als_nn_cg_steps``: 0 | n in 1 .. 1024 (``solver='als'`` and ``n_gpus=1`` only; ``ValueError`` otherwise, when every factor
+    the call updates is signed, and together with ``loss='logistic'`` or biases, before any device is touched).  n >= 1: the rows of
+    a NON-NEGATIVE factor with entry weights on one of its relations run n matrix-free projected conjugate-gradient steps from the
+    rows they have instead of forming their k x k systems -- a monotone descent with non-negative factors at O(nnz k) per pass
+    (``HipALSSolver``).  Signed factors keep ``als_cg_steps``, unweighted sweeps ``als_nn_sweeps``; a background weight is honoured.
+
     ``x_background_weight`` / ``y_background_weight``: 0 | c0 > 0 (``solver='als'`` only) -- implicit feedback.  The relation's
     entry weights must be a SciPy sparse W or ``'observed'`` with every stored weight >= c0; the cells outside that pattern then
     count with weight c0 and target 0 instead of not at all: 1/2 sum_O w (t - a.b)^2 + 1/2 c0 sum_{not O} (a.b)^2, at the cost of
@@ -126,6 +132,9 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     check_als_nn_sweeps(als_nn_sweeps, solver)
     check_als_cg_steps(als_cg_steps, solver, [nn for nn, upd in ((U_non_negative, update_U), (V_non_negative, update_V),
                                                                  (Z_non_negative, update_Z)) if upd])
+    check_als_nn_cg_steps(als_nn_cg_steps, solver, [nn for nn, upd in ((U_non_negative, update_U), (V_non_negative, update_V),
+                                                                       (Z_non_negative, update_Z)) if upd],
+                          n_gpus, loss, bool(x_biases) or bool(y_biases))
     x_background_weight = check_background_weight(x_background_weight, "x", solver, x_entry_weights)
     y_background_weight = check_background_weight(y_background_weight, "y", solver, y_entry_weights)
     x_biases = check_biases(x_biases, "x", solver, x_entry_weights, x_background_weight)
@@ -188,7 +197,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                      x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, nn_sweeps=als_nn_sweeps, cg_steps=als_cg_steps,
                                      x_background_weight=x_background_weight, y_background_weight=y_background_weight,
                                      x_biases=x_biases, y_biases=y_biases, bias_l2=bias_l2, x_bias_init=_x_bias_init,
-                                     y_bias_init=_y_bias_init, **common)
+                                     y_bias_init=_y_bias_init, nn_cg_steps=als_nn_cg_steps, **common)
         solver_object.check_weights(X, Y)
     else:
         raise ValueError("No such solver: %s" % solver)
@@ -343,14 +352,26 @@ class CMF(BaseEstimator, TransformerMixin):
     matrix-free conjugate-gradient steps instead of exact k x k solves (``collective_matrix_factorization``);
     ``CMF(solver="als", l2_reg=0.05, als_cg_steps=6, U_non_negative=False, V_non_negative=False, Z_non_negative=False)`` is the
     documented choice.
+
+    ``als_nn_cg_steps`` (``solver='als'`` only, default 0): n >= 1 fits the rows of a non-negative factor that has entry weights by
+    n matrix-free projected conjugate-gradient steps, never forming the k x k systems (``collective_matrix_factorization``);
+    ``CMF(solver="als", l2_reg=0.05, als_nn_cg_steps=4)``.  ``transform`` honours it.  It is a keyword-only OPTION, not one of the
+    estimator's scikit-learn parameters: ``get_params`` lists what it listed before (grid searches and pipelines that enumerate the
+    parameters see no new name), ``set_params(als_nn_cg_steps=n)``, ``clone`` and ``repr`` carry it all the same.  Needs
+    scikit-learn >= 1.3 (``__sklearn_clone__``); with an older one passing the keyword is a ``NotImplementedError``.
     """
+
+    _OPTIONS = {"als_nn_cg_steps": 0}     # keyword-only options outside get_params(): name -> default
 
     def __init__(self, n_components=None, x_init=None, y_init=None, solver='mu', alpha='auto',
                  beta_loss='frobenius', tol=1e-4, max_iter=600,
                  random_state=None, l1_reg=0., l2_reg=0., verbose=0,
                  U_non_negative=True, V_non_negative=True, Z_non_negative=True,
                  x_link="linear", y_link="linear", hessian_pertubation=0.2, sg_sample_ratio=1.,
-                 device=0, sg_sampler="numpy", n_gpus=1, loss="frobenius", als_nn_sweeps=0, als_cg_steps=0):
+                 device=0, sg_sampler="numpy", n_gpus=1, loss="frobenius", als_nn_sweeps=0, als_cg_steps=0, **options):
+        unknown = sorted(set(options) - set(self._OPTIONS))
+        if unknown:
+            raise TypeError("CMF.__init__() got an unexpected keyword argument %r" % (unknown[0],))
         self.n_components = n_components
         self.x_init = x_init
         self.y_init = y_init
@@ -376,6 +397,27 @@ class CMF(BaseEstimator, TransformerMixin):
         self.loss = loss
         self.als_nn_sweeps = als_nn_sweeps
         self.als_cg_steps = als_cg_steps
+        if options and not hasattr(BaseEstimator, "__sklearn_clone__"):   # (scikit-learn < 1.3: clone() would drop the option in silence)
+            raise NotImplementedError("CMF(%s=...) needs scikit-learn >= 1.3" % (sorted(options)[0],))
+        for name, default in self._OPTIONS.items():
+            setattr(self, name, options.get(name, default))
+
+    def __repr__(self, N_CHAR_MAX=700):
+        text = super().__repr__(N_CHAR_MAX=N_CHAR_MAX)
+        extra = ", ".join("%s=%r" % (name, getattr(self, name)) for name, default in self._OPTIONS.items() if getattr(self, name) != default)
+        if not extra or not text.endswith(")"):
+            return text
+        return text[:-1] + ("" if text.endswith("()") else ", ") + extra + ")"
+
+    def set_params(self, **params):
+        for name in [n for n in params if n in self._OPTIONS]:
+            setattr(self, name, params.pop(name))
+        return super().set_params(**params)
+
+    def __sklearn_clone__(self):
+        from sklearn.base import clone
+        params = {name: clone(value, safe=False) for name, value in self.get_params(deep=False).items()}
+        return type(self)(**params, **{name: getattr(self, name) for name in self._OPTIONS})
 
     def _kwargs(self):
         return dict(solver=self.solver, beta_loss=self.beta_loss, tol=self.tol, max_iter=self.max_iter,
@@ -385,7 +427,8 @@ class CMF(BaseEstimator, TransformerMixin):
                     x_link=self.x_link, y_link=self.y_link,
                     hessian_pertubation=self.hessian_pertubation,
                     sg_sample_ratio=self.sg_sample_ratio, device=self.device, sg_sampler=self.sg_sampler,
-                    loss=self.loss, als_nn_sweeps=self.als_nn_sweeps, als_cg_steps=self.als_cg_steps)
+                    loss=self.loss, als_nn_sweeps=self.als_nn_sweeps, als_cg_steps=self.als_cg_steps,
+                    als_nn_cg_steps=self.als_nn_cg_steps)
 
     def fit_transform(self, X, Y, U=None, V=None, Z=None, x_entry_weights=None, y_entry_weights=None, x_background_weight=0.0,
                       y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None):

@@ -735,6 +735,31 @@ def check_als_cg_steps(als_cg_steps, solver="als", updated_non_negative=None):
                          "(U/V/Z_non_negative=True is the default): pass *_non_negative=False, or use als_nn_sweeps" % (als_cg_steps,))
 
 
+def check_als_nn_cg_steps(als_nn_cg_steps, solver="als", updated_non_negative=None, n_gpus=1, loss="frobenius", biases=False):
+    """``als_nn_cg_steps``: an integer 0 .. 1024; non-zero with solver='als' on one GPU only, only when some updated factor is
+    non-negative (``updated_non_negative`` as in ``check_als_cg_steps``), and not with ``loss='logistic'`` or biases.  No device is
+    touched."""
+    if isinstance(als_nn_cg_steps, (bool, np.bool_)) or not isinstance(als_nn_cg_steps, (numbers.Integral, np.integer)):
+        raise ValueError("als_nn_cg_steps must be an integer 0 .. 1024, got %r" % (als_nn_cg_steps,))
+    if als_nn_cg_steps < 0 or als_nn_cg_steps > 1024:
+        raise ValueError("als_nn_cg_steps must be an integer 0 .. 1024, got %r" % (als_nn_cg_steps,))
+    if not als_nn_cg_steps:
+        return
+    if solver != "als":
+        raise ValueError("als_nn_cg_steps is the non-negative conjugate-gradient row solve of solver='als': it must be 0 with solver=%r, "
+                         "got %r" % (solver, als_nn_cg_steps))
+    if n_gpus != 1:
+        raise ValueError("als_nn_cg_steps=%r runs on one GPU: n_gpus must be 1, got %r" % (als_nn_cg_steps, n_gpus))
+    if updated_non_negative is not None and not any(updated_non_negative):
+        raise ValueError("als_nn_cg_steps=%r acts on non-negative factors only, and every factor this call updates is signed: "
+                         "pass *_non_negative=True, or use als_cg_steps" % (als_nn_cg_steps,))
+    if loss == "logistic":
+        raise ValueError("als_nn_cg_steps=%r with loss='logistic' is not built (the conjugate-gradient rows have no reweighting pass): "
+                         "als_nn_cg_steps must be 0; use als_nn_sweeps" % (als_nn_cg_steps,))
+    if biases:
+        raise ValueError("als_nn_cg_steps=%r with x_biases / y_biases is not built: als_nn_cg_steps must be 0; use als_nn_sweeps" % (als_nn_cg_steps,))
+
+
 class HipALSSolver(HipMUSolver):
     """Alternating least squares in MU's sweep order V -> U -> Z (``cmf_als_step`` / ``cmf_als_nnls_step``) on
 
@@ -763,6 +788,13 @@ class HipALSSolver(HipMUSolver):
     descent stays monotone; the rows are no longer exact minimisers (planted rank 12, 50 % observed, 20 iterations: objective
     50.05 with 6 steps against 50.46 exact, 51.45 with 4, 55.3 with 3, 60.8 with 2, 144.7 with 1).  A non-negative factor keeps the route ``nn_sweeps`` names,
     a factor whose relations are all unweighted the one shared inverse; refused when every updated factor is non-negative.
+
+    ``nn_cg_steps=n`` (1 .. 1024; default 0): a NON-NEGATIVE factor with an OBSERVED relation never forms its k x k systems either
+    -- each row runs n matrix-free projected conjugate-gradient steps from the row it has (``cmf_als_nncg_step``): a CG step on the
+    free coordinates while it stays feasible, otherwise an exactly searched step towards the projection.  One or two passes of
+    O(nnz k) per step; every step lowers the row's quadratic and keeps the row >= 0, so the descent stays monotone WITH
+    non-negative factors.  Takes precedence over ``nn_sweeps`` on such a factor; signed factors keep ``cg_steps`` (0: exact rows),
+    a non-negative factor whose relations are all unweighted keeps ``nn_sweeps``.  Not with ``loss='logistic'`` or biases.
 
     ``x_background_weight=c0`` / ``y_background_weight`` (default 0): the implicit-feedback model (Hu, Koren, Volinsky).  The
     relation must have sparse entry weights W (or ``'observed'``) with every stored weight >= c0; the cells outside W's pattern
@@ -801,11 +833,12 @@ class HipALSSolver(HipMUSolver):
 
     def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, cg_steps=0, x_background_weight=0.0,
                  y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None, x_bias_init=None, y_bias_init=None,
-                 loss="frobenius", **kwargs):
+                 loss="frobenius", nn_cg_steps=0, **kwargs):
         check_loss(loss, "als")
         check_als(loss=loss)
         check_als_nn_sweeps(nn_sweeps)
         check_als_cg_steps(cg_steps)
+        check_als_nn_cg_steps(nn_cg_steps, loss=loss, biases=bool(x_biases) or bool(y_biases))
         self.x_background_weight = check_background_weight(x_background_weight, "x", "als", x_entry_weights)
         self.y_background_weight = check_background_weight(y_background_weight, "y", "als", y_entry_weights)
         self.x_biases = check_biases(x_biases, "x", "als", x_entry_weights, self.x_background_weight)
@@ -827,6 +860,7 @@ class HipALSSolver(HipMUSolver):
         self.logistic_loss = None            # (L_x, L_y) of the last error evaluation under loss='logistic'
         self.nn_sweeps = int(nn_sweeps)
         self.cg_steps = int(cg_steps)
+        self.nn_cg_steps = int(nn_cg_steps)
 
     def _weights_key(self):
         return super()._weights_key() + (self.x_background_weight, self.y_background_weight, self.x_biases, self.y_biases) + tuple(self._logit)
@@ -897,7 +931,9 @@ class HipALSSolver(HipMUSolver):
 
     def _device_step(self, l1_reg, l2_reg, alpha):
         check_als(l1_reg, l2_reg)
-        if self.x_biases or self.y_biases:
+        if self.nn_cg_steps:   # (never with biases or a logistic relation: check_als_nn_cg_steps)
+            self._ctx.als_nncg_step(l2_reg, self._nn_mask(), self._update_mask(), self.cg_steps, self.nn_cg_steps, self.nn_sweeps)
+        elif self.x_biases or self.y_biases:
             self._ctx.als_bias_step(l2_reg, self._nn_mask(), self._update_mask(), self.cg_steps, self.nn_sweeps)
         elif self.cg_steps:
             self._ctx.als_cg_step(l2_reg, self._nn_mask(), self._update_mask(), self.cg_steps, self.nn_sweeps)
