@@ -433,6 +433,32 @@ int cmf_als_nncg_rows(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, doub
 int cmf_als_nncg_last(cmf_ctx *ctx, int64_t *out2);
 int cmf_als_nncg_passes(cmf_ctx *ctx, int64_t *out2);
 
+/* ---- ALS: exact rows of few stored entries in DUAL form ---------------------------------------------------------------------
+ * cmf_als_dual_step: cmf_als_step's step with a permission dual_max (0 = off, 1 .. 128).  A sweep is ELIGIBLE when it would take
+ * the exact row route (observed; signed, or in nn_mask with nn_sweeps = 0 and nn_cg_steps = 0: the solved row is then projected),
+ * has no shared term (every relation it reads is observed and has no background weight) and reads no logistic relation.  With
+ *   a_e = sqrt(w_e) b_e  (A: n x k),   y_e = p_e / sqrt(w_e)  (0 where w_e = 0)
+ * over the row's n stored entries (side 0 then side 1, stored order; p = w t with the bias terms taken off) the exact row solves
+ * (A^T A + l2 I_k) f = A^T y, and the same f is  K = A A^T + l2 I_n,  K z = y,  f = A^T z.  Inside an eligible sweep a row goes
+ * dual when 1 <= n <= dual_max and its class width NP(n) (the smallest of 32, 64, 128 that is >= n) is below k_pad; a row
+ * without a stored entry becomes zeros; every other row takes the formed route on compact slots and ends with the bits
+ * cmf_als_step gives it.  A sweep that is not eligible, and every sweep under dual_max = 0, runs what it runs without this entry
+ * point: same launches, same bits.  Non-negative factors take nn_sweeps / nn_cg_steps as cmf_als_nncg_step gives them; there is
+ * no cg_steps (CG would take every sweep the dual route could); with biases bound the bias blocks follow as in cmf_als_bias_step.
+ * csrc/cmf_als_dual.hip.h: the symmetric Gram on the matrix pipe, the solve through the Cholesky path of the exact route on
+ * NP x NP matrices (threshold l2 / 16), one accumulator chain per coordinate in stored order for f; no atomics, deterministic to
+ * the bit, a row's result depends on that row alone.  Kernel time: the Gram under CMF_K_ROWHESS at 2 NP^2 k flops per row.
+ * Validation as cmf_als_step; CMF_EINVAL for dual_max outside 0 .. 128 or a count outside 0 .. 1024; CMF_EUNSUPPORTED for
+ * k_pad > 256 and for nn_cg_steps > 0 with biases bound.
+ *   cmf_als_dual_rows (tests): host_f[nrows x k_pad] = the rows an eligible sweep of factor `which` would write for rows
+ *   [row0, row0 + nrows) under dual_max (unprojected), from the current factors, which are left unchanged.  CMF_EINVAL, naming
+ *   why, for a sweep that is not eligible: no observed relation, a shared term, or a logistic relation.
+ *   cmf_als_dual_last (tests, read-only): out5 = rows in class 32, 64 and 128, rows left to the formed route and rows written as
+ *   zeros in the last dual sweep (or cmf_als_dual_rows call).  Zeros before the first; CMF_EINVAL for a null pointer.            */
+int cmf_als_dual_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask, int dual_max, int nn_sweeps, int nn_cg_steps);
+int cmf_als_dual_rows(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, double l2, int dual_max, float *host_f);
+int cmf_als_dual_last(cmf_ctx *ctx, int64_t *out5);
+
 /* ---- ALS for implicit feedback: a background weight on the cells outside the pattern ----------------------------------------
  * Clicks, plays, purchases: every stored target is 1, so a fit over the pattern alone is degenerate, and a fit with every cell at
  * weight 1 lets a click count no more than a non-click.  The standard model (Hu, Koren, Volinsky: "Collaborative Filtering for

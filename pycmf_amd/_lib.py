@@ -91,6 +91,9 @@ PROTOTYPES = {
     "cmf_als_nncg_rows": [_vp, _i32, _i64, _i64, _dbl, _i32, _pf],
     "cmf_als_nncg_last": [_vp, _pi64],
     "cmf_als_nncg_passes": [_vp, _pi64],
+    "cmf_als_dual_step": [_vp, _dbl, _i32, _i32, _i32, _i32, _i32],
+    "cmf_als_dual_rows": [_vp, _i32, _i64, _i64, _dbl, _i32, _pf],
+    "cmf_als_dual_last": [_vp, _pi64],
     "cmf_set_background_weight": [_vp, _i32, _dbl],
     "cmf_get_background_weight": [_vp, _i32, _pd],
     "cmf_als_residual_sq": [_vp, _pd, _pd],
@@ -669,6 +672,29 @@ class Context:
         out = np.zeros(2, dtype=np.int64)
         check(self._lib.cmf_als_nncg_passes(self._h, out.ctypes.data_as(_pi64)))
         return int(out[0]), int(out[1])
+
+    # ---- exact rows of few stored entries in dual form (csrc/cmf_als_dual.hip.h)
+    def als_dual_step(self, l2, nn_mask, mask, dual_max, nn_sweeps=0, nn_cg_steps=0):
+        """``als_step`` with the permission ``dual_max`` (0 .. 128): in a sweep on the exact row route that has no shared term and
+        reads no logistic relation, a row of 1 .. dual_max stored entries whose class width (32, 64, 128) is below k_pad is solved
+        from its n x n dual system -- the same exact row; every other sweep runs what it runs without the permission.  Non-negative
+        factors take ``nn_sweeps`` / ``nn_cg_steps`` as ``als_nncg_step`` gives them."""
+        check(self._lib.cmf_als_dual_step(self._h, l2, nn_mask, mask, dual_max, nn_sweeps, nn_cg_steps))
+
+    def als_dual_rows(self, which, row0, nrows, l2, dual_max):
+        """float32[nrows, k_pad]: the rows an eligible sweep of factor ``which`` would write for rows [row0, row0 + nrows) under
+        ``dual_max`` (unprojected); the factors are left unchanged."""
+        kp = self.geometry()[3]
+        out = np.zeros((max(nrows, 0), kp), dtype=np.float32)
+        check(self._lib.cmf_als_dual_rows(self._h, which, row0, nrows, l2, dual_max, out.ctypes.data_as(_pf)))
+        return out
+
+    def als_dual_last(self):
+        """(rows in class 32, in class 64, in class 128, rows left to the formed route, rows written as zeros) of the last dual
+        sweep (``als_dual_step`` or ``als_dual_rows``).  Read-only; for the tests."""
+        out = np.zeros(5, dtype=np.int64)
+        check(self._lib.cmf_als_dual_last(self._h, out.ctypes.data_as(_pi64)))
+        return tuple(int(v) for v in out)
 
     # ---- ALS for implicit feedback (csrc/cmf_als_bg.hip.h)
     def set_background_weight(self, which, c0):

@@ -25,6 +25,10 @@
 //   rows NNCG     observed; non-negative, nn_cg_steps > 0 (before      no systems: als_nncg_kernel (cmf_als_nncg.hip.h) runs matrix-free
 //                 `sweeps` is looked at; cmf_als_nncg_step only)       projected CG steps per row from the current rows clamped at
 //                                                                      zero, in place; the classes and the pieces of rows CG
+//   rows dual     a sweep on rows exact with S = N = null and no        the rows of 1 .. dual_max stored entries whose class width
+//                 logistic relation, under cmf_als_dual_step's          NP(n) < k_pad: K = A A^T + l2 I_n (als_dual_gram_kernel,
+//                 permission dual_max >= 1                              cmf_als_dual.hip.h), K z = y through safe_solve_rows, f = A^T z;
+//                                                                      the same exact row from an n x n system; other rows: rows exact
 //
 // The finished systems (als_chunks).  als_normal_kernel<KP, LG>: one 512-thread workgroup per PIECE of a row (at most `als_piece` stored
 // entries, a multiple of 32) of a CSR image (indptr, idx, pv = w t, wv = w).  The gathered rows b_e are staged 32 at a time through
@@ -855,6 +859,10 @@ static int als_cg_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begi
     return als_cg_long_rows(c, pa, (int64_t)longs.size(), (int64_t)pieces.size(), steps);
 }
 
+// cmf_als_dual.hip.h: under the permission of cmf_als_dual_step an ELIGIBLE sweep on the exact row route (no shared term, no logistic
+// relation) solves its rows of few stored entries in dual form and sets *taken; otherwise nothing is launched and *taken is false
+static int als_dual_sweep(cmf_ctx *c, const AlsSweep &sw, double l2, bool nn, bool *taken);
+
 // sweeps == 0: the solved rows of the factors in nn_mask are projected; sweeps > 0: those factors are swept by coordinate descent;
 // cg_steps > 0: a signed factor with an observed relation runs that many CG steps per row instead of the exact solves;
 // nn_cg_steps > 0: a non-negative factor with an observed relation runs that many projected CG steps per row (cmf_als_nncg.hip.h)
@@ -876,10 +884,14 @@ static int als_step(cmf_ctx *c, double l2, int nn_mask, int mask, int sweeps, in
         case ALS_SHARED_HALS: CHK(als_nnls_sweep_shared(c, f, l2, sweeps)); break;
         case ALS_ROWS_NNLS: CHK(als_rows_nnls(c, sw, l2, sweeps)); break;
         case ALS_ROWS_CG: CHK(als_cg_rows(c, sw, l2, 0, c->frows[f], cg_steps, c->F[f], 0)); break;
-        case ALS_ROWS_EXACT:
+        case ALS_ROWS_EXACT: {
+            bool dual = false;   // under cmf_als_dual_step's permission an eligible sweep solves its short rows in dual form
+            CHK(als_dual_sweep(c, sw, l2, nn, &dual));
+            if (dual) break;
             CHK(als_rows_solve(c, sw, l2));
             CHK(als_apply(c, f, (const float *)c->als_sol.p, nn));
             break;
+        }
         }
     }
     return CMF_OK;

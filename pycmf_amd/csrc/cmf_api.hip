@@ -177,6 +177,9 @@ struct cmf_ctx {
     DevBuf als_nncg_passes;               // ... the passes every row of the sweep ran
     std::vector<int32_t> als_nncg_lens;   // ... the stored entries of those rows; als_nncg_counted: als_nncg_last[2 .. 3] hold that sweep's sums
     bool als_nncg_counted = true;
+    int als_dual_perm = 0;                // dual ALS rows (cmf_als_dual.hip.h): the permission dual_max while cmf_als_dual_step runs (0: none)
+    int64_t als_dual_last[5] = {0, 0, 0, 0, 0}; // ... rows in class 32, 64, 128, rows left to the formed route, rows written as zeros in the last dual sweep
+    DevBuf als_dual_ws;                   // ... K, y and z of a chunk of dual rows
     double wm_bg[2] = {0.0, 0.0};         // background weight c0 of X / Y on the cells outside a CSR pattern (cmf_als_bg.hip.h; 0: none)
     DevBuf als_bg_s, als_bg64;            // ... the shared matrix sum coef Gram of a sweep; float64 Grams of the error's trace term
     int rel_loss[2] = {0, 0};             // loss of X / Y under the ALS steps (cmf_als_logit.hip.h): CMF_LOSS_FROBENIUS | CMF_LOSS_LOGISTIC
@@ -866,6 +869,7 @@ static void release_problem(cmf_ctx *c) {
     c->als_cg_long = DevBuf(); c->als_cg_last[0] = c->als_cg_last[1] = 0;
     c->als_nncg_passes = DevBuf(); for (int q = 0; q < 4; ++q) c->als_nncg_last[q] = 0;
     c->als_nncg_lens.clear(); c->als_nncg_counted = true;
+    c->als_dual_ws = DevBuf(); c->als_dual_perm = 0; for (int q = 0; q < 5; ++q) c->als_dual_last[q] = 0;
     c->als_bg_s = DevBuf(); c->als_bg64 = DevBuf();
     c->als_bias_part = DevBuf(); c->als_bias_ws = DevBuf();
     for (int w = 0; w < 2; ++w) {
@@ -1996,3 +2000,5 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_als.hip.h"
 #define CMF_ALS_BIAS_HOST
 #include "cmf_als_bias.hip.h"
+#define CMF_ALS_DUAL_HOST
+#include "cmf_als_dual.hip.h"

@@ -760,6 +760,25 @@ def check_als_nn_cg_steps(als_nn_cg_steps, solver="als", updated_non_negative=No
         raise ValueError("als_nn_cg_steps=%r with x_biases / y_biases is not built: als_nn_cg_steps must be 0; use als_nn_sweeps" % (als_nn_cg_steps,))
 
 
+def check_als_dual_max(als_dual_max, solver="als", n_gpus=1, als_cg_steps=0):
+    """``als_dual_max``: an integer 0 .. 128 (a bool is refused); non-zero with solver='als' on one GPU only, and not together with
+    ``als_cg_steps`` (conjugate gradients already take every sweep the dual rows could).  ``loss='logistic'``, biases and background
+    weights are all accepted: the option then acts on the eligible sweeps only.  No device is touched."""
+    if isinstance(als_dual_max, (bool, np.bool_)) or not isinstance(als_dual_max, (numbers.Integral, np.integer)):
+        raise ValueError("als_dual_max must be an integer 0 .. 128, got %r" % (als_dual_max,))
+    if als_dual_max < 0 or als_dual_max > 128:
+        raise ValueError("als_dual_max must be an integer 0 .. 128, got %r" % (als_dual_max,))
+    if not als_dual_max:
+        return
+    if solver != "als":
+        raise ValueError("als_dual_max is the dual row solve of solver='als': it must be 0 with solver=%r, got %r" % (solver, als_dual_max))
+    if n_gpus != 1:
+        raise ValueError("als_dual_max=%r runs on one GPU: n_gpus must be 1, got %r" % (als_dual_max, n_gpus))
+    if als_cg_steps:
+        raise ValueError("als_dual_max=%r together with als_cg_steps=%r: conjugate gradients already take every sweep the dual rows "
+                         "could (signed factors with entry weights): one of the two must be 0" % (als_dual_max, als_cg_steps))
+
+
 class HipALSSolver(HipMUSolver):
     """Alternating least squares in MU's sweep order V -> U -> Z (``cmf_als_step`` / ``cmf_als_nnls_step``) on
 
@@ -795,6 +814,13 @@ class HipALSSolver(HipMUSolver):
     O(nnz k) per step; every step lowers the row's quadratic and keeps the row >= 0, so the descent stays monotone WITH
     non-negative factors.  Takes precedence over ``nn_sweeps`` on such a factor; signed factors keep ``cg_steps`` (0: exact rows),
     a non-negative factor whose relations are all unweighted keeps ``nn_sweeps``.  Not with ``loss='logistic'`` or biases.
+
+    ``dual_max=n`` (1 .. 128; default 0): permission for the DUAL form of the exact rows (``cmf_als_dual_step``).  In a sweep
+    whose rows are solved exactly (signed, or non-negative under ``nn_sweeps=0``: projected) and whose relations are all observed,
+    without a background weight or a logistic loss, a row with 1 .. n stored entries is solved from the system of its entries,
+    K = A A^T + l2 I (A: the gathered rows scaled by sqrt(w)), K z = y, f = A^T z -- the same exact minimiser from an n x n matrix
+    instead of a k x k one, when the padded n (32, 64, 128) is below k_pad.  Other rows of such a sweep keep their bits, other
+    sweeps their routes; biases are honoured.  Not together with ``cg_steps``.
 
     ``x_background_weight=c0`` / ``y_background_weight`` (default 0): the implicit-feedback model (Hu, Koren, Volinsky).  The
     relation must have sparse entry weights W (or ``'observed'``) with every stored weight >= c0; the cells outside W's pattern
@@ -833,12 +859,13 @@ class HipALSSolver(HipMUSolver):
 
     def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, cg_steps=0, x_background_weight=0.0,
                  y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None, x_bias_init=None, y_bias_init=None,
-                 loss="frobenius", nn_cg_steps=0, **kwargs):
+                 loss="frobenius", nn_cg_steps=0, dual_max=0, **kwargs):
         check_loss(loss, "als")
         check_als(loss=loss)
         check_als_nn_sweeps(nn_sweeps)
         check_als_cg_steps(cg_steps)
         check_als_nn_cg_steps(nn_cg_steps, loss=loss, biases=bool(x_biases) or bool(y_biases))
+        check_als_dual_max(dual_max, als_cg_steps=cg_steps)
         self.x_background_weight = check_background_weight(x_background_weight, "x", "als", x_entry_weights)
         self.y_background_weight = check_background_weight(y_background_weight, "y", "als", y_entry_weights)
         self.x_biases = check_biases(x_biases, "x", "als", x_entry_weights, self.x_background_weight)
@@ -861,6 +888,7 @@ class HipALSSolver(HipMUSolver):
         self.nn_sweeps = int(nn_sweeps)
         self.cg_steps = int(cg_steps)
         self.nn_cg_steps = int(nn_cg_steps)
+        self.dual_max = int(dual_max)
 
     def _weights_key(self):
         return super()._weights_key() + (self.x_background_weight, self.y_background_weight, self.x_biases, self.y_biases) + tuple(self._logit)
@@ -931,7 +959,9 @@ class HipALSSolver(HipMUSolver):
 
     def _device_step(self, l1_reg, l2_reg, alpha):
         check_als(l1_reg, l2_reg)
-        if self.nn_cg_steps:   # (never with biases or a logistic relation: check_als_nn_cg_steps)
+        if self.dual_max:      # (never with cg_steps: check_als_dual_max; the bias blocks follow inside the call)
+            self._ctx.als_dual_step(l2_reg, self._nn_mask(), self._update_mask(), self.dual_max, self.nn_sweeps, self.nn_cg_steps)
+        elif self.nn_cg_steps:   # (never with biases or a logistic relation: check_als_nn_cg_steps)
             self._ctx.als_nncg_step(l2_reg, self._nn_mask(), self._update_mask(), self.cg_steps, self.nn_cg_steps, self.nn_sweeps)
         elif self.x_biases or self.y_biases:
             self._ctx.als_bias_step(l2_reg, self._nn_mask(), self._update_mask(), self.cg_steps, self.nn_sweeps)
