@@ -19,8 +19,7 @@
 // The error of such a relation:  E = sum_O w (t - s)^2 + c0 (<A^T A, B^T B>_F - sum_O s^2),  clamped at 0.
 // No atomics; nothing here writes through a scalar path.  c0 = 0 frees the excess arrays: every route is then the code without
 // this file, byte for byte.
-#ifndef CMF_ALS_BG_KERNELS
-#define CMF_ALS_BG_KERNELS
+#pragma once
 #include "cmf_kernels.hip.h"
 #include "cmf_wmu.hip.h"
 
@@ -89,16 +88,21 @@ __global__ __launch_bounds__(256) void als_bg_dot64_kernel(const double *a, cons
 }
 
 } // namespace cmfk
-#endif // CMF_ALS_BG_KERNELS
 
-// ------------------------------------------------------------------ host side (included by cmf_als.hip.h behind AlsSweep)
-#if defined(CMF_ALS_BG_HOST) && !defined(CMF_ALS_BG_HOST_DONE)
-#define CMF_ALS_BG_HOST_DONE
+// ------------------------------------------------------------------ host side (included by cmf_api.hip behind cmf_als_bias.hip.h)
+#ifdef CMF_ALS_HOST
 
 // the weights the row kernels read for an observed side: the excess w - c0 under a background, w itself otherwise
 static const float *als_side_weights(const WCsrDev &M) { return M.ev ? M.ev : M.wv; }
 // the products w t they read: w times the adjusted targets under biases (cmf_als_bias.hip.h), p = w t otherwise
 static const float *als_side_targets(const WCsrDev &M) { return M.bp ? M.bp : M.pv; }
+
+// does the sweep have a shared term (als_shared_terms sets S): a full relation, or an observed one under a background weight
+static bool als_shared_present(const cmf_ctx *c, const AlsSweep &sw) {
+    for (int s = 0; s < sw.nrel; ++s)
+        if (!sw.observed[s] || c->wm_bg[sw.rel[s].which] > 0.0) return true;
+    return false;
+}
 
 // The part of a sweep's systems that all its rows share: *S = sum_sides coef Gram(B_side) (coef: c0 of a side with a background,
 // 1 of a full side; null when no side has either) and *N = T B of the full side (or null).  Without a background S is the Gram of
@@ -248,4 +252,4 @@ extern "C" int cmf_als_residual_sq(cmf_ctx *c, double *ex, double *ey) {
     return CMF_OK;
 }
 
-#endif // CMF_ALS_BG_HOST
+#endif // CMF_ALS_HOST

@@ -18,8 +18,7 @@
 //                          pair, f linear or sigmoid; the k-sum in the fixed order of group_sum
 // Every cross-workgroup sum is a kernel boundary; no atomics, no grid-wide barrier, vector stores only: a repeated call from the
 // same state is bit-identical, and a row's bias depends on the row and on L alone.
-#ifndef CMF_ALS_BIAS_KERNELS
-#define CMF_ALS_BIAS_KERNELS
+#pragma once
 #include "cmf_kernels.hip.h"
 
 namespace cmfk {
@@ -142,11 +141,10 @@ __global__ __launch_bounds__(256) void predict_pairs_kernel(const int64_t *rows,
 }
 
 } // namespace cmfk
-#endif // CMF_ALS_BIAS_KERNELS
 
-// ------------------------------------------------------------------ host side (included by cmf_api.hip behind cmf_als.hip.h)
-#if defined(CMF_ALS_BIAS_HOST) && !defined(CMF_ALS_BIAS_HOST_DONE)
-#define CMF_ALS_BIAS_HOST_DONE
+// ------------------------------------------------------------------ host side (included by cmf_api.hip behind cmf_als.hip.h; the step
+// that sweeps the biases is als_step, cmf_als_steps.hip.h)
+#ifdef CMF_ALS_HOST
 
 enum { ALS_BIAS_PIECE_DEFAULT = 2048 };
 // entries per piece ("als_bias_piece": > 0 rounded up to 16; 0 the default; < 0 every row is one piece)
@@ -385,33 +383,6 @@ extern "C" int cmf_als_bias_targets(cmf_ctx *c, int which, int image, int64_t nn
     return CMF_OK;
 }
 
-extern "C" int cmf_als_bias_step(cmf_ctx *c, double l2, int nn_mask, int mask, int cg_steps, int nn_sweeps) {
-    NEED_PROBLEM(c);
-    CHK(als_check(c, "cmf_als_bias_step", l2, mask));
-    CHK(als_count_ok("cmf_als_bias_step", "cg_steps", cg_steps, 0));
-    CHK(als_count_ok("cmf_als_bias_step", "nn_sweeps", nn_sweeps, 0));
-    if (als_logit_swept(c, mask))
-        return fail(CMF_EUNSUPPORTED, "cmf_als_bias_step: a swept relation has a logistic loss (cmf_set_relation_loss); biases under a logit link are not built: "
-                                      "use cmf_als_step or cmf_als_nnls_step");
-    if (!als_bias_any(c)) return als_step(c, l2, nn_mask, mask, nn_sweeps, cg_steps);
-    DeviceGuard dg(c->device);
-    for (int w = 0; w < 2; ++w) CHK(als_bias_refresh(c, w));   // (written when the biases last changed: nothing to do)
-    CHK(als_step(c, l2, nn_mask, mask, nn_sweeps, cg_steps));
-    // r_x follows U, c_x and r_y follow V, c_y follows Z; r first, then c from the new r
-    const int bit[2][2] = {{CMF_UPD_U, CMF_UPD_V}, {CMF_UPD_V, CMF_UPD_Z}};
-    for (int w = 0; w < 2; ++w) {
-        AlsBias &b = c->als_bias[w];
-        if (!b.on) continue;
-        for (int axis = 0; axis < 2; ++axis) {
-            if (!(mask & bit[w][axis])) continue;
-            CHK(als_bias_sweep(c, w, axis, axis == 0 ? b.r : b.c));
-            b.dirty = true;
-        }
-        CHK(als_bias_refresh(c, w));   // the adjusted targets of the next step, and of cmf_als_residual_sq
-    }
-    return CMF_OK;
-}
-
 extern "C" int cmf_predict_pairs(cmf_ctx *c, int which, int link, int64_t n, const int64_t *rows, const int64_t *cols, float *out) {
     NEED_PROBLEM(c);
     CHK(als_bias_which_ok("cmf_predict_pairs", which));
@@ -448,4 +419,4 @@ extern "C" int cmf_predict_pairs(cmf_ctx *c, int which, int link, int64_t n, con
     return CMF_OK;
 }
 
-#endif // CMF_ALS_BIAS_HOST
+#endif // CMF_ALS_HOST

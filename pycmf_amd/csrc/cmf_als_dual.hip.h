@@ -8,7 +8,8 @@
 // an n x n system instead of a k x k one.  lambda_min(K) >= l2, and cond(K) is bounded by that of the primal matrix.  With NP(n) the
 // smallest of 32, 64, 128 that is >= n, a row goes dual when 1 <= n <= dual_max and NP(n) < k_pad (the dual system is strictly the
 // smaller one); a row without a stored entry is zeros; every other row of the sweep takes the formed route of cmf_als.hip.h,
-// restricted to those rows (als_list_rows below: the unchanged kernels on compact slots, then a scatter).
+// restricted to those rows (a plan of listed rows through the one chunk loop: the unchanged kernels on compact slots, then a scatter).
+// The planner is als_dual_rows (cmf_als_steps.hip.h); this file holds the kernels.
 //
 // als_dual_gram_kernel<KP, NP>: one 256-thread workgroup per row (NP = 32: four rows, one wave each).  The sqrt(w_e)-scaled gathered
 //   rows are staged 64 columns of k at a time into ONE LDS image [NP][64 + 4] (16 lanes x f32x4 per gathered row, all loads of a
@@ -21,7 +22,7 @@
 //   The k-chunks are added in ascending order.  K goes to scratch [row][NP][NP], both triangles (a block below the diagonal also
 //   leaves transposed, f32x4 at a time), l2 on the WHOLE diagonal: a padding coordinate is l2 z = 0.  y goes to [row][NP], exact
 //   zeros on padding entries and where w_e = 0.  Vector stores only, no atomics, no scratch memory.
-// The solve is safe_solve_rows (cmf_newton.hip.h) on NP x NP matrices, as als_rows_solve calls it.
+// The solve is the exact solve of the formed route (als_solve_rows: safe_solve_rows, cmf_newton.hip.h) on NP x NP matrices.
 // als_dual_back_kernel<KP>: one wave per row: f = sum_e (sqrt(w_e) z_e) b_e over the entries in stored order, one accumulator chain
 //   per coordinate (KP / 64 floats per lane, ALS_CG_U loads in flight): the sum order is the stored order whatever the launch shape.
 //   Coordinates j < k only, max(., 0) for a projected non-negative factor; the padding is never written.
@@ -235,290 +236,3 @@ __global__ void als_dual_scatter_kernel(float *Fout, int64_t out_row0, const int
 
 } // namespace cmfk
 
-// ------------------------------------------------------------------ host side (included by cmf_api.hip behind cmf_als_bias.hip.h)
-#ifdef CMF_ALS_DUAL_HOST
-
-enum { ALS_DUAL_CLASSES = 3, ALS_DUAL_MAX = 128 };
-static int als_dual_np(int64_t n) { return n <= 32 ? 32 : (n <= 64 ? 64 : 128); }
-
-// why the sweep is not eligible for the dual route (null: it is): it must take ALS_ROWS_EXACT (the caller's test), every relation it
-// reads must be observed without a background weight (als_shared_terms then gives S = N = null) and none may be logistic
-static const char *als_dual_why_not(const cmf_ctx *c, const AlsSweep &sw) {
-    if (!als_observed(sw)) return "no observed relation: one shared matrix, no per-row systems";
-    for (int s = 0; s < sw.nrel; ++s)
-        if (!sw.observed[s] || c->wm_bg[sw.rel[s].which] > 0.0) return "a shared term (a full relation or a background weight): the Woodbury form with a shared matrix is not built";
-    if (als_logit_sweep(c, sw)) return "a logistic relation: reweighted dual rows are not built";
-    return nullptr;
-}
-
-// The formed route over a row list: the systems of rows[0 .. n) (global rows of the sweep, which has S = N = null) by the unchanged
-// als_normal_kernel / als_finish_kernel on compact slots, chunk by chunk, the unchanged safe_solve_rows, then the scatter.  pieces
-// / first: the plan of the listed rows on the device (AlsPiece::row is the global row), hp / hfirst its host copy.  The pieces of a
-// row, their order and the per-matrix solve are those of als_chunks: a listed row ends with the bits cmf_als_step gives it.
-static int als_list_rows(cmf_ctx *c, const AlsSweep &sw, double l2, const int64_t *drows, int64_t n, const cmfk::AlsPiece *dpieces, const int64_t *dfirst,
-                         const std::vector<cmfk::AlsPiece> &hp, const std::vector<int64_t> &hfirst, int64_t cap, bool nn, float *Fout, int64_t out_row0) {
-    using namespace cmfk;
-    if (n <= 0) return CMF_OK;
-    const int kp = c->kp;
-    const int64_t kk = (int64_t)kp * kp;
-    int64_t max_rows = 0, max_pieces = 0;
-    std::vector<int64_t> cuts{0};
-    for (int64_t r = 0; r < n;) {                        // the chunk rule of als_chunks
-        int64_t e = r;
-        while (e < n && e - r < cap && (e == r || hfirst[(size_t)e + 1] - hfirst[(size_t)r] <= cap)) ++e;
-        max_rows = std::max(max_rows, e - r);
-        max_pieces = std::max(max_pieces, hfirst[(size_t)e] - hfirst[(size_t)r]);
-        cuts.push_back(e);
-        r = e;
-    }
-    CHK(ensure_scratch(c, c->als_h, (size_t)max_rows * kk * sizeof(float)));
-    CHK(ensure_scratch(c, c->als_part, (size_t)std::max<int64_t>(1, max_pieces) * (kk + kp) * sizeof(float)));
-    CHK(ensure_scratch(c, c->als_g, (size_t)max_rows * kp * sizeof(float)));
-    CHK(ensure_scratch(c, c->als_sol, (size_t)max_rows * kp * sizeof(float)));
-    AlsArgs a;
-    memset(&a, 0, sizeof a);
-    for (int s = 0; s < sw.nobs; ++s) {
-        const WCsrDev &M = *sw.obs[s].M;
-        (s == 0 ? a.s0 : a.s1) = AlsSide{M.idx, als_side_targets(M), als_side_weights(M), sw.obs[s].B};
-    }
-    float *Hc = (float *)c->als_h.p, *Hp = (float *)c->als_part.p, *grad = (float *)c->als_g.p, *sol = (float *)c->als_sol.p;
-    a.Hp = Hp;
-    a.gp = Hp + std::max<int64_t>(1, max_pieces) * kk;
-    const double pert = l2 / 16.0;                       // als_rows_solve's threshold
-    for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
-        const int64_t c0 = cuts[ci], c1 = cuts[ci + 1], nr = c1 - c0;
-        const int64_t pbase = hfirst[(size_t)c0], np = hfirst[(size_t)c1] - pbase;
-        a.pieces = dpieces + pbase;
-        int64_t nnz = 0;
-        for (int64_t p = pbase; p < pbase + np; ++p) nnz += hp[(size_t)p].len;
-        CHK(als_launch_normal(c, a, np, nnz, false));
-        {
-            Timed tm(c, CMF_K_ELEMWISE);
-            hipLaunchKernelGGL(als_finish_kernel, dim3((unsigned)nr), dim3(256), 0, c->stream, (const float *)Hp, (const float *)a.gp, dfirst + c0, pbase,
-                               (const float *)nullptr, (const float *)nullptr, (float)l2, c->k, kp, Hc, grad);
-            HIPCHK(hipGetLastError());
-        }
-        {
-            AlsNewtonStateGuard keep(c);
-            c->hess_psd = true;
-            CHK(safe_solve_rows(c, Hc, grad, sol, nr, c->k, kp, pert));
-        }
-        CHK(launch_ew(c, als_dual_scatter_kernel, nr * kp, Fout, out_row0, drows + c0, (const float *)sol, nr, c->k, kp, nn ? 1 : 0));
-    }
-    return CMF_OK;
-}
-
-template <int KP>
-static int als_dual_launch_class(cmf_ctx *c, const cmfk::AlsDualArgs &a, int np) {
-    using namespace cmfk;
-    const dim3 block(256);
-    if constexpr (KP > 32) {
-        if (np == 32) hipLaunchKernelGGL((als_dual_gram_kernel<KP, 32>), dim3((unsigned)((a.nrows + 3) / 4)), block, 0, c->stream, a);
-    }
-    if constexpr (KP > 64) {
-        if (np == 64) hipLaunchKernelGGL((als_dual_gram_kernel<KP, 64>), dim3((unsigned)a.nrows), block, 0, c->stream, a);
-    }
-    if constexpr (KP > 128) {
-        if (np == 128) hipLaunchKernelGGL((als_dual_gram_kernel<KP, 128>), dim3((unsigned)a.nrows), block, 0, c->stream, a);
-    }
-    HIPCHK(hipGetLastError());
-    return CMF_OK;
-}
-
-// Rows [r_begin, r_end) of an ELIGIBLE sweep (als_dual_why_not is null) under the permission dual_max >= 1: the dual rows class by
-// class (Gram, solve, back-product, in chunks of rows whose K scratch stays within the byte budget hessian_chunk_rows gives the
-// exact route), zeros for the rows without a stored entry, the formed route for the rest.  Row r goes to Fout + (r - out_row0) k_pad.
-// none_dual (a whole sweep): when no row of the plan goes dual nothing is launched and *none_dual is set -- the caller runs the
-// exact sweep as it stands (the same bits: a formed row keeps them, a row without an entry solves l2 f = 0), without the row list.
-static int als_dual_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_begin, int64_t r_end, int dual_max, bool nn, float *Fout, int64_t out_row0,
-                         bool *none_dual = nullptr) {
-    using namespace cmfk;
-    const int kp = c->kp;
-    const int64_t nrows = r_end - r_begin;
-    std::vector<int64_t> ip[2];
-    CHK(als_fetch_indptr(c, sw, r_begin, r_end, ip));
-    const int64_t L = als_piece_len(c);
-    if (none_dual) {   // a first pass that only counts: a sweep without a dual row builds no list and no piece
-        int64_t n_dual = 0, n_zero = 0;
-        for (int64_t r = 0; r < nrows; ++r) {
-            int64_t len = 0;
-            for (int s = 0; s < sw.nobs; ++s) len += ip[s][(size_t)r + 1] - ip[s][(size_t)r];
-            n_zero += len == 0;
-            n_dual += len > 0 && len <= dual_max && als_dual_np(len) < kp;
-        }
-        *none_dual = n_dual == 0;
-        if (*none_dual) {
-            c->als_dual_last[0] = c->als_dual_last[1] = c->als_dual_last[2] = 0;
-            c->als_dual_last[3] = nrows - n_zero;
-            c->als_dual_last[4] = n_zero;
-            return CMF_OK;
-        }
-    }
-    std::vector<int64_t> list[ALS_DUAL_CLASSES], zeros, formed, first{0};
-    std::vector<AlsPiece> pieces;
-    for (int64_t r = 0; r < nrows; ++r) {
-        int64_t len = 0;
-        for (int s = 0; s < sw.nobs; ++s) len += ip[s][(size_t)r + 1] - ip[s][(size_t)r];
-        if (len == 0) { zeros.push_back(r_begin + r); continue; }
-        if (len <= dual_max && als_dual_np(len) < kp) {
-            list[als_dual_np(len) == 32 ? 0 : (als_dual_np(len) == 64 ? 1 : 2)].push_back(r_begin + r);
-            continue;
-        }
-        formed.push_back(r_begin + r);
-        for (int s = 0; s < sw.nobs; ++s) {              // the pieces of als_cut_rows: image by image
-            const int64_t e = ip[s][(size_t)r + 1];
-            for (int64_t q = ip[s][(size_t)r]; q < e; q += L) pieces.push_back(AlsPiece{q, (int32_t)std::min(L, e - q), s, r_begin + r});
-        }
-        first.push_back((int64_t)pieces.size());
-    }
-    for (int q = 0; q < ALS_DUAL_CLASSES; ++q) c->als_dual_last[q] = (int64_t)list[q].size();
-    c->als_dual_last[3] = (int64_t)formed.size();
-    c->als_dual_last[4] = (int64_t)zeros.size();
-
-    // descriptors, once per sweep: the rows of the three classes | the zero rows | the formed rows | their first[] | their pieces
-    std::vector<int64_t> all;
-    all.reserve((size_t)nrows + first.size());
-    for (int q = 0; q < ALS_DUAL_CLASSES; ++q) all.insert(all.end(), list[q].begin(), list[q].end());
-    all.insert(all.end(), zeros.begin(), zeros.end());
-    all.insert(all.end(), formed.begin(), formed.end());
-    const size_t nlisted = all.size();
-    all.insert(all.end(), first.begin(), first.end());
-    const size_t abytes = all.size() * sizeof(int64_t);
-    CHK(ensure_scratch(c, c->als_desc, abytes + std::max<size_t>(16, pieces.size() * sizeof(AlsPiece))));
-    int64_t *drows = (int64_t *)c->als_desc.p;
-    const int64_t *dfirst = drows + nlisted;
-    AlsPiece *dpieces = (AlsPiece *)((char *)c->als_desc.p + abytes);
-    HIPCHK(hipMemcpyAsync(drows, all.data(), abytes, hipMemcpyHostToDevice, c->stream));
-    if (!pieces.empty()) HIPCHK(hipMemcpyAsync(dpieces, pieces.data(), pieces.size() * sizeof(AlsPiece), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream)); // the host vectors may go
-
-    const int64_t cap_exact = hessian_chunk_rows(c, c->frows_pad[sw.f]);
-    const int64_t budget = cap_exact * kp * kp;          // floats of K scratch a chunk may take: the exact route's
-    AlsDualArgs a;
-    memset(&a, 0, sizeof a);
-    for (int s = 0; s < sw.nobs; ++s) {
-        const WCsrDev &M = *sw.obs[s].M;
-        (s == 0 ? a.s0 : a.s1) = AlsCgSide{M.indptr, M.idx, als_side_targets(M), als_side_weights(M), sw.obs[s].B};
-    }
-    a.Fout = Fout;
-    a.out_row0 = out_row0;
-    a.l2 = (float)l2;
-    a.k = c->k;
-    a.nn = nn ? 1 : 0;
-    const double pert = l2 / 16.0;
-    int64_t done = 0;
-    for (int q = 0; q < ALS_DUAL_CLASSES; ++q) {
-        const int np = 32 << q;
-        const int64_t n = (int64_t)list[q].size(), per = (int64_t)np * np;
-        const int64_t cap = std::max<int64_t>(4, budget / per / 4 * 4);
-        for (int64_t r0 = 0; r0 < n; r0 += cap) {
-            const int64_t nr = std::min(cap, n - r0);
-            CHK(ensure_scratch(c, c->als_dual_ws, (size_t)nr * (per + 2 * np) * sizeof(float)));
-            a.rows = drows + done + r0;
-            a.nrows = nr;
-            a.K = (float *)c->als_dual_ws.p;
-            a.y = a.K + nr * per;
-            float *z = a.y + nr * np;
-            a.z = z;
-            {
-                Timed tm(c, CMF_K_ROWHESS, 2.0 * (double)nr * np * np * c->k);
-                switch (kp) {
-                case 64: CHK(als_dual_launch_class<64>(c, a, np)); break;
-                case 128: CHK(als_dual_launch_class<128>(c, a, np)); break;
-                case 256: CHK(als_dual_launch_class<256>(c, a, np)); break;
-                default: return fail(CMF_EUNSUPPORTED, "the dual ALS rows are built for k_pad 64, 128 and 256 (k_pad = %d)", kp);
-                }
-            }
-            {
-                AlsNewtonStateGuard keep(c);
-                c->hess_psd = true;
-                CHK(safe_solve_rows(c, a.K, a.y, z, nr, np, np, pert));
-            }
-            {
-                Timed tm(c, CMF_K_ELEMWISE);
-                const dim3 grid((unsigned)((nr + 3) / 4)), block(256);
-                switch (kp) {
-                case 64: hipLaunchKernelGGL((als_dual_back_kernel<64>), grid, block, 0, c->stream, a, np); break;
-                case 128: hipLaunchKernelGGL((als_dual_back_kernel<128>), grid, block, 0, c->stream, a, np); break;
-                default: hipLaunchKernelGGL((als_dual_back_kernel<256>), grid, block, 0, c->stream, a, np); break;
-                }
-                HIPCHK(hipGetLastError());
-            }
-        }
-        done += n;
-    }
-    if (!zeros.empty())
-        CHK(launch_ew(c, als_dual_scatter_kernel, (int64_t)zeros.size() * kp, Fout, out_row0, (const int64_t *)(drows + done), (const float *)nullptr,
-                      (int64_t)zeros.size(), c->k, kp, 0));
-    done += (int64_t)zeros.size();
-    return als_list_rows(c, sw, l2, drows + done, (int64_t)formed.size(), dpieces, dfirst, pieces, first, cap_exact, nn, Fout, out_row0);
-}
-
-static int als_dual_max_ok(const char *what, int dual_max) {
-    if (dual_max < 0 || dual_max > ALS_DUAL_MAX) return fail(CMF_EINVAL, "%s: dual_max must be 0 .. %d, got %d", what, (int)ALS_DUAL_MAX, dual_max);
-    return CMF_OK;
-}
-
-// the permission of als_step's exact row sweeps for the length of one entry point
-struct AlsDualPermission {
-    cmf_ctx *const c;
-    const int before;
-    AlsDualPermission(cmf_ctx *ctx, int dual_max) : c(ctx), before(ctx->als_dual_perm) { c->als_dual_perm = dual_max; }
-    ~AlsDualPermission() { c->als_dual_perm = before; }
-};
-
-// als_step's hook (declared in cmf_als.hip.h): a sweep on ALS_ROWS_EXACT under a permission; *taken = false leaves it to the caller
-static int als_dual_sweep(cmf_ctx *c, const AlsSweep &sw, double l2, bool nn, bool *taken) {
-    *taken = c->als_dual_perm > 0 && c->kp > 32 && !als_dual_why_not(c, sw);   // (k_pad = 32: no class is below it)
-    if (!*taken) return CMF_OK;
-    bool none = false;
-    CHK(als_dual_rows(c, sw, l2, 0, c->frows[sw.f], c->als_dual_perm, nn, c->F[sw.f], 0, &none));
-    *taken = !none;
-    return CMF_OK;
-}
-
-extern "C" int cmf_als_dual_step(cmf_ctx *c, double l2, int nn_mask, int mask, int dual_max, int nn_sweeps, int nn_cg_steps) {
-    NEED_PROBLEM(c);
-    CHK(als_check(c, "cmf_als_dual_step", l2, mask));
-    CHK(als_dual_max_ok("cmf_als_dual_step", dual_max));
-    CHK(als_count_ok("cmf_als_dual_step", "nn_sweeps", nn_sweeps, 0));
-    CHK(als_count_ok("cmf_als_dual_step", "nn_cg_steps", nn_cg_steps, 0));
-    if (nn_cg_steps && als_bias_any(c))
-        return fail(CMF_EUNSUPPORTED, "cmf_als_dual_step: nn_cg_steps with biases bound is not built (cmf_als_nncg_step): pass nn_cg_steps = 0");
-    AlsDualPermission perm(c, dual_max);
-    if (nn_cg_steps) return cmf_als_nncg_step(c, l2, nn_mask, mask, 0, nn_cg_steps, nn_sweeps);
-    if (als_bias_any(c)) return cmf_als_bias_step(c, l2, nn_mask, mask, 0, nn_sweeps);
-    return nn_sweeps ? cmf_als_nnls_step(c, l2, nn_mask, mask, nn_sweeps) : cmf_als_step(c, l2, nn_mask, mask);
-}
-
-// test entry: the rows an eligible sweep `which` would write for rows [row0, row0 + nrows) under dual_max; the factors are left alone
-extern "C" int cmf_als_dual_rows(cmf_ctx *c, int which, int64_t row0, int64_t nrows, double l2, int dual_max, float *host_f) {
-    NEED_PROBLEM(c);
-    if (which < 0 || which > 2) return fail(CMF_EINVAL, "cmf_als_dual_rows: bad factor selector");
-    CHK(als_check(c, "cmf_als_dual_rows", l2, 1 << which));
-    CHK(als_dual_max_ok("cmf_als_dual_rows", dual_max));
-    if (row0 < 0 || nrows < 0 || row0 + nrows > c->frows[which]) return fail(CMF_EINVAL, "cmf_als_dual_rows: rows out of range");
-    const AlsSweep sw = als_sweep(c, which);
-    if (const char *why = als_dual_why_not(c, sw)) return fail(CMF_EINVAL, "cmf_als_dual_rows: this sweep is not eligible: %s", why);
-    if (nrows == 0) return CMF_OK;
-    if (!host_f) return fail(CMF_EINVAL, "cmf_als_dual_rows: null output");
-    DeviceGuard dg(c->device);
-    for (int s = 0; s < sw.nrel; ++s) CHK(als_bias_refresh(c, sw.rel[s].which));   // (written when the biases last changed: nothing to do)
-    const size_t bytes = (size_t)nrows * c->kp * sizeof(float);
-    CHK(ensure_scratch(c, c->als_cg_ws, bytes));
-    HIPCHK(hipMemsetAsync(c->als_cg_ws.p, 0, bytes, c->stream));
-    CHK(als_dual_rows(c, sw, l2, row0, row0 + nrows, dual_max, false, (float *)c->als_cg_ws.p, row0));
-    HIPCHK(hipMemcpyAsync(host_f, c->als_cg_ws.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return CMF_OK;
-}
-
-// test entry: rows in class 32, 64 and 128, rows left to the formed route and rows written as zeros in the last dual sweep (or
-// cmf_als_dual_rows call)
-extern "C" int cmf_als_dual_last(cmf_ctx *c, int64_t *out5) {
-    if (!c || !out5) return fail(CMF_EINVAL, "cmf_als_dual_last: null context or output");
-    for (int q = 0; q < 5; ++q) out5[q] = c->als_dual_last[q];
-    return CMF_OK;
-}
-
-#endif // CMF_ALS_DUAL_HOST

@@ -18,10 +18,8 @@
 //                          terms added in float64 per lane group, the groups in group order; the pieces are added in piece order
 //                          behind the kernel boundary (als_logit_sum_kernel, one thread).
 // No atomics anywhere, vector stores only: a repeated call from the same state is bit-identical.
-// Included once, by cmf_als.hip.h's host side behind AlsSweep, the launch ladders and als_cut_rows.
 #pragma once
-#include "cmf_kernels.hip.h"
-#include "cmf_als_bias.hip.h"
+#include "cmf_kernels.hip.h"   // (AlsBiasPiece: cmf_als_bias.hip.h, which cmf_api.hip includes before this file)
 
 namespace cmfk {
 
@@ -73,7 +71,8 @@ __global__ void als_logit_sum_kernel(const double *part, int64_t n, double *out)
 
 } // namespace cmfk
 
-// ------------------------------------------------------------------ host side
+// ------------------------------------------------------------------ host side (included by cmf_api.hip behind cmf_als_bg.hip.h)
+#ifdef CMF_ALS_HOST
 enum { ALS_LOGIT_LOSS_PIECE = 2048 };
 
 static bool als_logit_rel(const cmf_ctx *c, int which) { return c->rel_loss[which] == CMF_LOSS_LOGISTIC; }
@@ -177,3 +176,5 @@ extern "C" int cmf_als_logistic_loss(cmf_ctx *c, double *lx, double *ly) {
     }
     return CMF_OK;
 }
+
+#endif // CMF_ALS_HOST

@@ -177,8 +177,7 @@ struct cmf_ctx {
     DevBuf als_nncg_passes;               // ... the passes every row of the sweep ran
     std::vector<int32_t> als_nncg_lens;   // ... the stored entries of those rows; als_nncg_counted: als_nncg_last[2 .. 3] hold that sweep's sums
     bool als_nncg_counted = true;
-    int als_dual_perm = 0;                // dual ALS rows (cmf_als_dual.hip.h): the permission dual_max while cmf_als_dual_step runs (0: none)
-    int64_t als_dual_last[5] = {0, 0, 0, 0, 0}; // ... rows in class 32, 64, 128, rows left to the formed route, rows written as zeros in the last dual sweep
+    int64_t als_dual_last[5] = {0, 0, 0, 0, 0}; // dual ALS rows (cmf_als_dual.hip.h): rows in class 32, 64, 128, rows left to the formed route, rows written as zeros in the last dual sweep
     DevBuf als_dual_ws;                   // ... K, y and z of a chunk of dual rows
     double wm_bg[2] = {0.0, 0.0};         // background weight c0 of X / Y on the cells outside a CSR pattern (cmf_als_bg.hip.h; 0: none)
     DevBuf als_bg_s, als_bg64;            // ... the shared matrix sum coef Gram of a sweep; float64 Grams of the error's trace term
@@ -395,7 +394,6 @@ static void als_bias_free(cmf_ctx *c, int which) {
     c->wm_sp[which][1].tv = nullptr;
     b = AlsBias();
 }
-static int als_bias_refresh(cmf_ctx *c, int which);   // cmf_als_bias.hip.h: bt / bp of both images from the current biases
 static void drop_graph(StepGraph &g) {
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
     g = StepGraph();
@@ -869,7 +867,7 @@ static void release_problem(cmf_ctx *c) {
     c->als_cg_long = DevBuf(); c->als_cg_last[0] = c->als_cg_last[1] = 0;
     c->als_nncg_passes = DevBuf(); for (int q = 0; q < 4; ++q) c->als_nncg_last[q] = 0;
     c->als_nncg_lens.clear(); c->als_nncg_counted = true;
-    c->als_dual_ws = DevBuf(); c->als_dual_perm = 0; for (int q = 0; q < 5; ++q) c->als_dual_last[q] = 0;
+    c->als_dual_ws = DevBuf(); for (int q = 0; q < 5; ++q) c->als_dual_last[q] = 0;
     c->als_bg_s = DevBuf(); c->als_bg64 = DevBuf();
     c->als_bias_part = DevBuf(); c->als_bias_ws = DevBuf();
     for (int w = 0; w < 2; ++w) {
@@ -1996,9 +1994,9 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_rank.hip.h"
 #define CMF_HALS_HOST
 #include "cmf_hals.hip.h"
-#define CMF_ALS_HOST
-#include "cmf_als.hip.h"
-#define CMF_ALS_BIAS_HOST
-#include "cmf_als_bias.hip.h"
-#define CMF_ALS_DUAL_HOST
-#include "cmf_als_dual.hip.h"
+#define CMF_ALS_HOST   // the ALS headers, each once, in this order: a host part calls only what stands above it
+#include "cmf_als.hip.h"         // every row kernel; the sweep descriptor, the launch ladders, the piece plan
+#include "cmf_als_bias.hip.h"    // biases
+#include "cmf_als_bg.hip.h"      // background weights, the shared terms of a sweep
+#include "cmf_als_logit.hip.h"   // relation losses
+#include "cmf_als_steps.hip.h"   // the chunk loop, the routes, als_step and every step entry point

@@ -44,6 +44,7 @@ import scipy.sparse as sp
 
 U_BIT, V_BIT, Z_BIT = 1, 2, 4
 SHARED_EXACT, SHARED_HALS, ROWS_EXACT, ROWS_NNLS, ROWS_CG = "shared exact", "shared hals", "rows exact", "rows nnls", "rows cg"
+ROWS_NNCG, ROWS_DUAL = "rows nncg", "rows dual"
 
 
 class Relation:
@@ -216,13 +217,19 @@ def cg_row(Bs, ws, pvs, S, Nrow, l2, f, cg_steps, dtype=np.float64):
     return f
 
 
-def route(is_observed, non_negative, nn_sweeps, cg_steps):
-    """What the sweep of one factor does (the device's als_route): without an observed relation all rows share one matrix."""
+def route(is_observed, non_negative, nn_sweeps, cg_steps, nn_cg_steps=0, dual_max=0, shared_term=False, logistic=False, k_pad=64):
+    """What the sweep of one factor does (the device's als_route, the same precedence): without an observed relation all rows share
+    one matrix.  The facts behind the options: the sweep has a shared term (a full relation or a background weight), reads a
+    logistic relation, and k_pad -- the dual rows need an exact row sweep without either, and a class width below k_pad."""
+    if is_observed and non_negative and nn_cg_steps:
+        return ROWS_NNCG
     if non_negative and nn_sweeps:
         return ROWS_NNLS if is_observed else SHARED_HALS
     if not is_observed:
         return SHARED_EXACT
-    return ROWS_CG if cg_steps and not non_negative else ROWS_EXACT
+    if cg_steps and not non_negative:
+        return ROWS_CG
+    return ROWS_DUAL if dual_max > 0 and not shared_term and not logistic and k_pad > 32 else ROWS_EXACT
 
 
 def sweep(Rx, Ry, U, V, Z, which, l2, *, non_negative=False, nn_sweeps=0, cg_steps=0, cx=0.0, cy=0.0, rows=None, dtype=np.float64,

@@ -122,6 +122,42 @@ def test_float32_yardstick_prices_the_tolerance():
         assert A.tolerance(a, b, k) <= 4e-4 * np.abs(b).max()
 
 
+def test_route_truth_table():
+    """Every combination of the facts of a sweep and the options of a step: 2 observed x 2 non-negative x {0, > 0}^4 options x
+    shared term x logistic x k_pad in {32, 64}.  The precedence is the device's (als_route): the non-negative CG rows before
+    nn_sweeps on a non-negative observed factor; CG only on a signed observed factor; the dual rows only where the exact rows would
+    run, with no shared term, no logistic relation and k_pad > 32; a sweep without an observed relation never leaves the shared
+    routes; and with the new options at zero the answer is the one of the four old arguments.  This pins the Python mirror
+    (als_yardstick.route), which the float64 references are routed by, not the device's als_route: the device's table is held to it
+    by the GPU tests that compare each route with its reference and by test_gpu_als_dispatch.py."""
+    import itertools
+    seen = set()
+    for obs, nn, s, c, n, dm, shared, logit, kp in itertools.product((False, True), (False, True), (0, 2), (0, 3), (0, 4), (0, 128),
+                                                                        (False, True), (False, True), (32, 64)):
+        got = A.route(obs, nn, s, c, n, dm, shared, logit, kp)
+        seen.add(got)
+        if not obs:
+            want = A.SHARED_HALS if nn and s else A.SHARED_EXACT
+        elif nn and n:
+            want = A.ROWS_NNCG
+        elif nn and s:
+            want = A.ROWS_NNLS
+        elif not nn and c:
+            want = A.ROWS_CG
+        elif dm and not shared and not logit and kp > 32:
+            want = A.ROWS_DUAL
+        else:
+            want = A.ROWS_EXACT
+        assert got == want, (obs, nn, s, c, n, dm, shared, logit, kp)
+        assert (got == A.ROWS_NNCG) == (obs and nn and n > 0)
+        assert (got == A.ROWS_CG) == (obs and not nn and c > 0)
+        if got == A.ROWS_DUAL:                                # only where the exact rows would run otherwise
+            assert A.route(obs, nn, s, c, n, 0, shared, logit, kp) == A.ROWS_EXACT and not shared and not logit and kp > 32
+        if n == 0 and dm == 0:                                # the old callers, arguments unchanged
+            assert got == A.route(obs, nn, s, c)
+    assert seen == {A.SHARED_EXACT, A.SHARED_HALS, A.ROWS_EXACT, A.ROWS_NNLS, A.ROWS_CG, A.ROWS_NNCG, A.ROWS_DUAL}
+
+
 # ------------------------------------------------------------------ validation before any device is opened
 @pytest.mark.parametrize("kw, match", [(dict(l2_reg=0.0), "l2_reg > 0"), (dict(l2_reg=0.1, l1_reg=0.01), "l1_reg must be 0"),
                                        (dict(l2_reg=0.1, n_gpus=2), "n_gpus must be 1"),

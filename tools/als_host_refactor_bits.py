@@ -1,0 +1,187 @@
+"""Bits of every ALS entry point on a fixed list of small cases: one SHA-256 per case over the float32 bytes of U, V and Z (and of
+the bias vectors where biases are bound) after TWO steps from the same start, so that the second step reads the first's output, with
+the counters of cmf_als_cg_last / cmf_als_nncg_last / cmf_als_nncg_passes / cmf_als_dual_last behind it.  Written for the refactor
+of the ALS host code (one options record, one route table, one chunk loop): run on the commit before it and on the commit with it,
+on the same GPU, the two records must be equal entry for entry.
+
+    python tools/als_host_refactor_bits.py --label parent|branch [--out profiles/als_host_refactor_bits.json]
+
+The record goes under its label into the file --out names, beside the other label's if that is there already; with both there the
+tool compares them and fails on the first difference.
+
+The problem is tests/als_dual_cases.py::problem(k): 48 x 160 x 40, both relations observed, row lengths on both sides of 32 / 64 /
+128, empty rows and rows of one entry; k = 3, 40, 200 (k_pad 32, 64, 256); once with als_piece = 32 and als_cg_piece = 16 (rows of
+several pieces, long CG rows) and once with the defaults.  A background weight (0.25 on X) needs every stored weight at or above
+it: those cases bind max(w, 0.25) in place of the weights with stored zeros.  The logistic cases bind the labels Y > 0.
+Fails without a GPU."""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import als_dual_cases as C  # noqa: E402
+
+L2 = C.L2
+KS = (3, 40, 200)
+BG = 0.25
+ROWS = (3, 20)              # the row hooks: rows 3 .. 23
+
+
+def _bind(ctx, which, T, W):
+    if W is None:
+        ctx.set_data(which, T)
+        return
+    r = np.repeat(np.arange(W.shape[0]), np.diff(W.indptr))
+    ctx.set_weighted_csr(which, W.indptr, W.indices, np.asarray(T)[r, W.indices], W.data)
+
+
+def _context(lib, k, pieces, kind):
+    """kind: '' both relations observed | 'bias' x biases on | 'bg' a background weight on X | 'logit' Y logistic | 'full' X unweighted."""
+    X, Y, Wx, Wy, F = C.problem(k)
+    ctx = lib.Context(0)
+    if pieces:
+        ctx.set_option("als_piece", 32)
+        ctx.set_option("als_cg_piece", 16)
+    ctx.set_problem(C.M, C.D, C.P, k)
+    if kind == "bg":
+        Wx = Wx.copy()
+        Wx.data = np.maximum(Wx.data, BG)
+    _bind(ctx, 0, X, None if kind == "full" else Wx)
+    _bind(ctx, 1, (Y > 0).astype(np.float64) if kind == "logit" else Y, Wy)
+    if kind == "bg":
+        ctx.set_background_weight(0, BG)
+    if kind == "bias":
+        ctx.set_biases(0, True, 0.125, 0.5)
+    if kind == "logit":
+        ctx.set_relation_loss(1, "logistic")
+    return ctx, F
+
+
+def _reset(ctx, F, kind):
+    for w in range(3):
+        ctx.set_factor(w, F[w])
+    if kind == "bias":
+        for axis, n in ((0, C.M), (1, C.D)):
+            ctx.set_bias(0, axis, np.zeros(n))
+
+
+def _counters(ctx):
+    return {"cg_last": [int(v) for v in ctx.als_cg_last()], "nncg_last": [int(v) for v in ctx.als_nncg_last()],
+            "nncg_passes": [int(v) for v in ctx.als_nncg_passes()], "dual_last": [int(v) for v in ctx.als_dual_last()]}
+
+
+def _state(ctx, kind):
+    h = hashlib.sha256()
+    for w in range(3):
+        h.update(ctx.get_factor(w).astype(np.float32).tobytes())
+    if kind == "bias":
+        for axis in (0, 1):
+            h.update(ctx.get_bias(0, axis).astype(np.float32).tobytes())
+    return dict(_counters(ctx), sha256=h.hexdigest())
+
+
+DUAL = (("dual_max 128", (128, 0, 0)), ("dual_max 20", (20, 0, 0)), ("dual_max 0", (0, 0, 0)), ("nn_sweeps 2", (128, 2, 0)),
+        ("nn_cg_steps 3", (128, 0, 3)))
+
+
+def _steps(kind):
+    """(name, call(ctx)) of the step cases on a context of that kind."""
+    out = []
+    if kind == "":
+        out += [("als_step signed", lambda c: c.als_step(L2, 0, 7)), ("als_step nn 7", lambda c: c.als_step(L2, 7, 7)),
+                ("als_nnls_step 2 nn 7", lambda c: c.als_nnls_step(L2, 7, 7, 2)), ("als_nnls_step 2 nn 2", lambda c: c.als_nnls_step(L2, 2, 7, 2)),
+                ("als_cg_step 3 0 nn 5", lambda c: c.als_cg_step(L2, 5, 7, 3, 0)), ("als_cg_step 3 2 nn 5", lambda c: c.als_cg_step(L2, 5, 7, 3, 2)),
+                ("als_nncg_step 0 3 0 nn 7", lambda c: c.als_nncg_step(L2, 7, 7, 0, 3, 0)),
+                ("als_nncg_step 3 3 2 nn 5", lambda c: c.als_nncg_step(L2, 5, 7, 3, 3, 2)),
+                ("als_nncg_step 3 3 0 nn 0", lambda c: c.als_nncg_step(L2, 0, 7, 3, 3, 0)),
+                ("als_bias_step no biases cg 0", lambda c: c.als_bias_step(L2, 0, 7, 0, 0)),
+                ("als_bias_step no biases cg 3", lambda c: c.als_bias_step(L2, 5, 7, 3, 2))]
+    if kind == "bias":
+        out += [("als_bias_step cg 0", lambda c: c.als_bias_step(L2, 0, 7, 0, 0)), ("als_bias_step cg 3", lambda c: c.als_bias_step(L2, 0, 7, 3, 0))]
+    if kind in ("", "bias", "bg"):
+        for name, (dm, ns, ncg) in DUAL:
+            if kind == "bias" and ncg:
+                continue                                     # refused: nn_cg_steps with biases bound
+            nn = 5 if ns or ncg else 0
+            out.append(("als_dual_step " + name, lambda c, dm=dm, ns=ns, ncg=ncg, nn=nn: c.als_dual_step(L2, nn, 7, dm, ns, ncg)))
+    if kind == "logit":
+        out += [("als_step", lambda c: c.als_step(L2, 0, 7)), ("als_nnls_step 2 nn 7", lambda c: c.als_nnls_step(L2, 7, 7, 2))]
+    if kind == "full":
+        out += [("als_step", lambda c: c.als_step(L2, 0, 7))]
+    return out
+
+
+def _sha(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a, dtype=np.float32).tobytes())
+    return h.hexdigest()
+
+
+def record(lib):
+    rec = {}
+    for k in KS:
+        for pieces in (True, False):
+            tag = "k %d %s" % (k, "pieces 32/16" if pieces else "default pieces")
+            for kind in ("", "bias", "bg", "logit", "full"):
+                ctx, F = _context(lib, k, pieces, kind)
+                for name, call in _steps(kind):
+                    _reset(ctx, F, kind)
+                    call(ctx)
+                    call(ctx)
+                    rec["%s | %s | %s" % (tag, kind or "observed", name)] = _state(ctx, kind)
+                if kind == "":                               # the row hooks, rows 3 .. 23 of each factor, the factors at their start
+                    _reset(ctx, F, kind)
+                    for w in range(3):
+                        hooks = (("als_cg_rows", lambda: ctx.als_cg_rows(w, ROWS[0], ROWS[1], L2, 3)),
+                                 ("als_nncg_rows", lambda: ctx.als_nncg_rows(w, ROWS[0], ROWS[1], L2, 3)),
+                                 ("als_dual_rows", lambda: ctx.als_dual_rows(w, ROWS[0], ROWS[1], L2, 128)),
+                                 ("als_normal", lambda: ctx.als_normal(w, ROWS[0], ROWS[1], L2)))
+                        for name, hook in hooks:
+                            got = hook()
+                            rec["%s | observed | %s %s" % (tag, name, "UVZ"[w])] = dict(
+                                _counters(ctx), sha256=_sha(*got) if isinstance(got, tuple) else _sha(got))
+                ctx.close()
+            print("%s: done" % tag, flush=True)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--label", required=True, choices=("parent", "branch"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "als_host_refactor_bits.json"))
+    a = ap.parse_args()
+    from pycmf_amd import _lib
+    if _lib.device_count() < 1:
+        raise SystemExit("als_host_refactor_bits: no GPU visible (needs an MI355X)")
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out[a.label] = record(_lib)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:                              # one line per case
+        f.write("{\n" + ",\n".join(' "%s": {\n%s\n }' % (label, ",\n".join('  %s: %s' % (json.dumps(n), json.dumps(rec[n], sort_keys=True))
+                                                                       for n in sorted(rec))) for label, rec in sorted(out.items())) + "\n}\n")
+    print("%s: %d cases" % (a.label, len(out[a.label])))
+    if "parent" in out and "branch" in out:
+        if sorted(out["parent"]) != sorted(out["branch"]):
+            raise SystemExit("als_host_refactor_bits: the two records hold different cases")
+        bad = [n for n in sorted(out["parent"]) if out["parent"][n] != out["branch"][n]]
+        for n in bad:
+            print("DIFFERENT: %s\n  parent %s\n  branch %s" % (n, out["parent"][n], out["branch"][n]))
+        if bad:
+            raise SystemExit("als_host_refactor_bits: %d of %d cases differ" % (len(bad), len(out["parent"])))
+        print("parent and branch are equal on all %d cases" % len(out["parent"]))
+
+
+if __name__ == "__main__":
+    main()
