@@ -459,6 +459,33 @@ int cmf_als_dual_step(cmf_ctx *ctx, double l2, int nn_mask, int update_mask, int
 int cmf_als_dual_rows(cmf_ctx *ctx, int which, int64_t row0, int64_t nrows, double l2, int dual_max, float *host_f);
 int cmf_als_dual_last(cmf_ctx *ctx, int64_t *out5);
 
+/* ---- ALS: a per-row l2 (frequency-scaled regularisation) ---------------------------------------------------------------------
+ * One scalar l2 over-shrinks the rows with many stored entries or under-regularises those with few.  With a vector of positive
+ * multipliers m_F per factor F in {U, V, Z} the regulariser of the ALS objective becomes
+ *   l2 / 2 sum_F sum_i m_F[i] |f_i|^2,
+ * and row i of a sweep of F solves the system it solves above under lambda_i = l2 m_F[i] in place of l2.  m = n_i is the
+ * weighted-lambda form of Zhou, Wilkinson, Schreiber and Pan (ALS-WR); m = (n_i + alpha0 D)^nu the frequency-scaled form of
+ * Rendle, Krichene, Zhang and Koren (pycmf_amd.l2_multipliers computes both on the host).
+ *   cmf_set_l2_rows(ctx, which, mult): binds frows[which] multipliers for factor `which` (0 U | 1 V | 2 Z); mult = NULL clears them.
+ *   CMF_EINVAL for a bad `which` and for a value that is not finite and positive, as a double or rounded to float32; the state is
+ *   then unchanged.  cmf_set_problem clears all three factors' multipliers.
+ *   cmf_get_l2_rows(ctx, which, mult, set): *set = 1 | 0 (bound or not), mult[frows[which]] = the doubles as given (ones when none
+ *   are bound); either pointer may be NULL.
+ * The device holds the multipliers as float32, rounded once, and every row kernel forms lambda_i = (float)l2 * mult[row] as ONE
+ * float32 multiplication that is never fused with the addition behind it: a row under the multiplier v has, to the bit, the row the
+ * same call gives it under the scalar l2' with (float)l2' = fl((float)l2 v) and nothing bound.  With nothing bound the kernels take
+ * l2 itself: the launches and the bits of a context that never heard of this block.
+ * HONOURED BY all six cmf_als_*_step entry points on every row route (the finished systems of the exact, coordinate-descent and
+ * logistic rows; the l2 x term of the conjugate-gradient and projected conjugate-gradient rows, whole or cut into pieces; the whole
+ * diagonal of the dual systems), by cmf_als_cg_rows / cmf_als_nncg_rows / cmf_als_dual_rows and by cmf_als_normal.  The exact
+ * solve takes its threshold from the smallest lambda of the sweep: l2 min(m_F) / 16.  A factor WITHOUT an observed relation has one
+ * matrix for all rows: with multipliers that are all equal as float32 its sweep runs under l2 m_F[0]; otherwise the step returns
+ * CMF_EUNSUPPORTED and names the factor (nothing of that sweep has run; the context stays usable).
+ * The bias blocks of cmf_als_bias_step keep their own regulariser bias_l2 UNSCALED; the factor sweeps inside that call honour the
+ * multipliers.  NOT READ by the MU, HALS and Newton steps or by the error entry points: bind multipliers only for the ALS steps.    */
+int cmf_set_l2_rows(cmf_ctx *ctx, int which, const double *mult);
+int cmf_get_l2_rows(cmf_ctx *ctx, int which, double *mult, int *set);
+
 /* ---- ALS for implicit feedback: a background weight on the cells outside the pattern ----------------------------------------
  * Clicks, plays, purchases: every stored target is 1, so a fit over the pattern alone is degenerate, and a fit with every cell at
  * weight 1 lets a click count no more than a non-click.  The standard model (Hu, Koren, Volinsky: "Collaborative Filtering for

@@ -4,7 +4,7 @@ The public names are resolved on first use (PEP 562): ``from pycmf_amd import _l
 drivers need -- then imports NumPy only, not scikit-learn / SciPy / pandas behind the estimator."""
 
 __all__ = ["CMF", "collective_matrix_factorization", "HipMUSolver", "HipNewtonSolver", "HipHALSSolver", "HipALSSolver", "top_n_products", "rank_products",
-           "ranking_metrics", "implicit_confidence", "predict_products"]
+           "ranking_metrics", "implicit_confidence", "predict_products", "l2_multipliers"]
 
 
 def __getattr__(name):
@@ -14,9 +14,9 @@ def __getattr__(name):
     if name in ("HipMUSolver", "HipNewtonSolver", "HipHALSSolver", "HipALSSolver"):
         from . import solver_shell
         return getattr(solver_shell, name)
-    if name == "implicit_confidence":
+    if name in ("implicit_confidence", "l2_multipliers"):
         from . import solver_shell
-        return solver_shell.implicit_confidence
+        return getattr(solver_shell, name)
     if name == "top_n_products":
         from . import prediction
         return prediction.top_n_products

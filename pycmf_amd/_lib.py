@@ -94,6 +94,8 @@ PROTOTYPES = {
     "cmf_als_dual_step": [_vp, _dbl, _i32, _i32, _i32, _i32, _i32],
     "cmf_als_dual_rows": [_vp, _i32, _i64, _i64, _dbl, _i32, _pf],
     "cmf_als_dual_last": [_vp, _pi64],
+    "cmf_set_l2_rows": [_vp, _i32, _pd],
+    "cmf_get_l2_rows": [_vp, _i32, _pd, C.POINTER(C.c_int)],
     "cmf_set_background_weight": [_vp, _i32, _dbl],
     "cmf_get_background_weight": [_vp, _i32, _pd],
     "cmf_als_residual_sq": [_vp, _pd, _pd],
@@ -695,6 +697,28 @@ class Context:
         out = np.zeros(5, dtype=np.int64)
         check(self._lib.cmf_als_dual_last(self._h, out.ctypes.data_as(_pi64)))
         return tuple(int(v) for v in out)
+
+    # ---- a per-row l2 under the ALS steps (cmf_set_l2_rows, csrc/cmf_als_steps.hip.h)
+    def set_l2_rows(self, which, mult):
+        """Positive multipliers of ``l2``, one per row of factor ``which`` (0 U | 1 V | 2 Z): row i of an ALS sweep of that factor
+        is solved under ``l2 * mult[i]``.  ``None`` clears them.  ``ValueError`` (state unchanged) for a bad ``which``, a wrong
+        length or a value that is not finite and positive."""
+        if mult is None or which not in (0, 1, 2):   # (a bad selector: the library refuses it before it reads anything)
+            check(self._lib.cmf_set_l2_rows(self._h, which, None))
+            return
+        v = np.ascontiguousarray(mult, dtype=np.float64)
+        if v.shape != (self.shape[which],):
+            raise ValueError("set_l2_rows: expected %d multipliers, got an array of shape %s" % (self.shape[which], v.shape))
+        check(self._lib.cmf_set_l2_rows(self._h, which, v.ctypes.data_as(_pd)))
+
+    def get_l2_rows(self, which):
+        """float64[rows of factor ``which``]: the multipliers as they were set, or ``None`` when none are bound."""
+        if which not in (0, 1, 2):
+            check(self._lib.cmf_get_l2_rows(self._h, which, None, None))
+        out = np.ones(self.shape[which], dtype=np.float64)
+        on = C.c_int(0)
+        check(self._lib.cmf_get_l2_rows(self._h, which, out.ctypes.data_as(_pd), C.byref(on)))
+        return out if on.value else None
 
     # ---- ALS for implicit feedback (csrc/cmf_als_bg.hip.h)
     def set_background_weight(self, which, c0):

@@ -38,6 +38,11 @@
 //                                                                      spectral clamp never acts), no float64 refinement; projected
 //                                                                      if non-negative
 // Under `biases` als_step refreshes the adjusted targets before the sweeps and sweeps the bias blocks after them (cmf_als_bias.hip.h).
+// A PER-ROW l2 (cmf_set_l2_rows; cmf_als_steps.hip.h): with multipliers m_F bound for the swept factor, row i of every row route reads
+// lambda_i = l2 * m_F[i] where it reads l2 below -- one float32 product (als_row_l2, cmf_als_cg.hip.h) in the LR = true instance of
+// als_finish_kernel, als_cg_kernel / als_cg_combine_kernel, als_nncg_kernel / als_nncg_combine_kernel and als_dual_gram_kernel; the
+// exact solve takes its threshold from l2 min(m_F); the shared routes take equal multipliers only.  Nothing bound: the LR = false
+// instances, which are the kernels without any of this.
 //
 // The finished systems.  ONE chunk loop (als_chunks) is the only caller of als_normal_kernel / als_finish_kernel.  It takes a plan
 // (AlsPlan: the pieces, first[], where the finished g of a slot goes, the shared terms or null) -- of a range of rows for rows
@@ -295,10 +300,14 @@ __global__ __launch_bounds__(512) void als_normal_kernel(AlsArgs g) {
 // g_i = sum of the pieces + N_i.  first[row] .. first[row + 1] (minus pbase) are the row's slots.  One workgroup per row walks the
 // 32 x 32 blocks on or above the block diagonal: a block is read and written along its rows, and its mirror image leaves through a
 // 32 x 33 LDS tile, along rows too.
+// LR: l2m are the multipliers of cmf_set_l2_rows; slot `row` is row lrows[row] of them (a plan of listed rows) or, lrows null, row
+// `row` (a plan of a range: the host passes the pointer at its first row).  LR = false: neither is read.
+template <bool LR>
 __global__ __launch_bounds__(256) void als_finish_kernel(const float *Hp, const float *gp, const int64_t *first, int64_t pbase, const float *S,
-                                                         const float *N, float l2, int k, int kp, float *H, float *g) {
+                                                         const float *N, float l2, int k, int kp, float *H, float *g, const float *l2m, const int64_t *lrows) {
     __shared__ float tl[32][33];
     const int64_t row = blockIdx.x;
+    if constexpr (LR) l2 = als_row_l2<true>(l2, l2m, lrows ? lrows[row] : row);   // uniform over the workgroup
     const int64_t p0 = first[row] - pbase, p1 = first[row + 1] - pbase;
     const int64_t kk = (int64_t)kp * kp;
     float *Hr = H + row * kk;

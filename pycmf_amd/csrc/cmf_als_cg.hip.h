@@ -14,7 +14,8 @@
 //     and a butterfly over the 64 lanes (offsets 32 .. 1: every lane ends with the same bits); acc += (w_e d_e) b_e goes into
 //     the wave's own accumulator.  The four accumulators are added through LDS in wave order by thread j < KP,
 //     which then adds (S x)_j = sum_c S[c][j] x_c for c ascending (x broadcast from LDS, the row of S coalesced and served by L2)
-//     and l2 x_j on the first k coordinates.  Padding coordinates stay exact zeros and are never written to the factor.
+//     and l2 x_j on the first k coordinates (LR = true: lambda_i x_j with the row's own lambda_i = l2 * mult[row], als_row_l2).
+//     Padding coordinates stay exact zeros and are never written to the factor.
 //   * The first pass fuses the right-hand side: its coefficient is pv_e - w_e (b_e . f), so it yields r = g - H f directly.  A row
 //     is read steps + 1 times.
 //   * r.r and p.q: a butterfly inside each wave, the four wave sums added in wave order.
@@ -59,6 +60,7 @@ struct AlsCgArgs {
     float l2;
     int k, steps;
     int cap;                // entries a row may keep resident in this launch's dynamic LDS (0: every row streams)
+    const float *l2m;       // per-row multipliers of l2 (cmf_set_l2_rows), indexed by the row of the swept factor; null: the LR = false instance
 };
 
 enum { ALS_CG_U = 4 };      // entries in flight per wave
@@ -67,13 +69,29 @@ enum { ALS_CG_U = 4 };      // entries in flight per wave
 __host__ __device__ constexpr int als_cg_fixed_floats(int kp) { return 5 * kp + 16; }
 __host__ __device__ constexpr int als_cg_entry_bytes(int kp) { return 4 * kp + 4; }
 
+// lambda_i of a row.  LR = false (no multipliers bound): l2, and the instance is the kernel without any of this.  LR = true: the ONE
+// float32 product l2 * mult[row], never fused into the addition that takes it: a row under a multiplier v has the bits of the same
+// row under the scalar fl(l2 v).  The flag is a template argument of every kernel that reads a row's l2, as LG is of
+// als_normal_kernel: with a run-time test of the pointer the row kernels of this file and of cmf_als_nncg.hip.h took one VGPR more
+// and als_nncg_kernel<256> fell from 8 to 7 waves per SIMD.
+template <bool LR>
+__device__ __forceinline__ float als_row_l2(float l2, [[maybe_unused]] const float *mult, [[maybe_unused]] int64_t row) {
+    if constexpr (LR) {   // (every caller's row is wave-uniform: the product is handed on in a scalar register)
+#pragma clang fp contract(off)
+        const float lam = l2 * mult[row];
+        return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(lam)));
+    } else {
+        return l2;
+    }
+}
+
 __device__ __forceinline__ float als_cg_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
-template <int KP>
+template <int KP, bool LR>
 __global__ __launch_bounds__(256) void als_cg_kernel(AlsCgArgs g) {
     constexpr int VPL = KP >= 64 ? KP / 64 : 1;     // floats of a gathered row per lane
     extern __shared__ __attribute__((aligned(16))) float als_cg_lds[];
@@ -177,7 +195,7 @@ __global__ __launch_bounds__(256) void als_cg_kernel(AlsCgArgs g) {
             if (g.S) {
                 for (int c = 0; c < k; ++c) sx = fmaf(g.S[c * KP + t], xs[c], sx);
             }
-            if (t < k) sx += g.l2 * xs[t];
+            if (t < k) sx += als_row_l2<LR>(g.l2, g.l2m, row) * xs[t];   // (wave-uniform)
             o = first ? o - sx : o + sx;
         }
         return o;
@@ -243,6 +261,7 @@ struct AlsCgPieceArgs {
     float l2;
     int k;
     int phase;              // 0: the first pass / its combine; 1: a step; 2: the last step (f goes to Fout)
+    const float *l2m;       // as AlsCgArgs (the combine finds its row through AlsCgLongRow::row)
 };
 
 __device__ __forceinline__ bool als_cg_positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
@@ -314,7 +333,7 @@ __global__ __launch_bounds__(256) void als_cg_piece_kernel(AlsCgPieceArgs g) {
     if (t < KP) g.partial[(int64_t)blockIdx.x * KP + t] = ((part[t] + part[KP + t]) + part[2 * KP + t]) + part[3 * KP + t];
 }
 
-template <int KP>
+template <int KP, bool LR>
 __global__ __launch_bounds__(256) void als_cg_combine_kernel(AlsCgPieceArgs g) {
     __shared__ float xs[KP], wsum[8];
     const int t = threadIdx.x, lane = t & 63;
@@ -351,7 +370,7 @@ __global__ __launch_bounds__(256) void als_cg_combine_kernel(AlsCgPieceArgs g) {
         if (g.S) {
             for (int c = 0; c < k; ++c) sx = fmaf(g.S[c * KP + t], xs[c], sx);
         }
-        if (t < k) sx += g.l2 * xs[t];
+        if (t < k) sx += als_row_l2<LR>(g.l2, g.l2m, lr.row) * xs[t];
         o = first ? o - sx : o + sx;
     }
     if (first) {

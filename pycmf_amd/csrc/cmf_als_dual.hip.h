@@ -20,7 +20,7 @@
 //       NP = 64    wave 0: (0,0)   wave 1: (1,0)   wave 2: (1,1)
 //       NP = 32    wave w: block (0,0) of the workgroup's row w
 //   The k-chunks are added in ascending order.  K goes to scratch [row][NP][NP], both triangles (a block below the diagonal also
-//   leaves transposed, f32x4 at a time), l2 on the WHOLE diagonal: a padding coordinate is l2 z = 0.  y goes to [row][NP], exact
+//   leaves transposed, f32x4 at a time), l2 (lambda_i = l2 * mult[row] under cmf_set_l2_rows) on the WHOLE diagonal: a padding coordinate is l2 z = 0.  y goes to [row][NP], exact
 //   zeros on padding entries and where w_e = 0.  Vector stores only, no atomics, no scratch memory.
 // The solve is the exact solve of the formed route (als_solve_rows: safe_solve_rows, cmf_newton.hip.h) on NP x NP matrices.
 // als_dual_back_kernel<KP>: one wave per row: f = sum_e (sqrt(w_e) z_e) b_e over the entries in stored order, one accumulator chain
@@ -43,6 +43,7 @@ struct AlsDualArgs {
     int64_t out_row0;
     float l2;
     int k, nn;
+    const float *l2m;       // per-row multipliers of l2 (cmf_set_l2_rows), indexed by the row of the swept factor; null: the LR = false instance
 };
 
 enum { ALS_DUAL_KC = 64, ALS_DUAL_PITCH = ALS_DUAL_KC + 4 };
@@ -55,7 +56,7 @@ struct AlsDualCfg {
     static constexpr int MAXB = NP == 128 ? 3 : 1;      // blocks per wave
 };
 
-template <int KP, int NP>
+template <int KP, int NP, bool LR>
 __global__ __launch_bounds__(256) void als_dual_gram_kernel(AlsDualArgs g) {
     using C = AlsDualCfg<NP>;
     constexpr int P = ALS_DUAL_PITCH, KC = ALS_DUAL_KC;
@@ -149,6 +150,7 @@ __global__ __launch_bounds__(256) void als_dual_gram_kernel(AlsDualArgs g) {
     const int64_t slot = (int64_t)blockIdx.x * C::RPW + wrs;
     if (slot >= g.nrows) return;
     float *Kd = g.K + slot * NP * NP;
+    const float l2 = als_row_l2<LR>(g.l2, g.l2m, LR ? g.rows[slot] : 0);   // wave-uniform
 #pragma unroll
     for (int b = 0; b < C::MAXB; ++b) {
         if (b < nb) {
@@ -158,7 +160,7 @@ __global__ __launch_bounds__(256) void als_dual_gram_kernel(AlsDualArgs g) {
             for (int r = 0; r < 16; ++r) {
                 const int br = (r & 3) + 8 * (r >> 2);
                 float v = acc[b][r];
-                if (diag && br + 4 * lh == l31) v += g.l2;
+                if (diag && br + 4 * lh == l31) v += l2;
                 dst[br * NP] = v;
             }
             if (!diag) {

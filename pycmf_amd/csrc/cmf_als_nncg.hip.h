@@ -65,6 +65,7 @@ struct AlsNncgLongArgs {
     int k;
     int stage;              // 0: r = g - H f; 1: the pass with p / combine A; 2: the pass with d / combine B
     int last;               // stage 2 of the last step: f and the passes go out
+    const float *l2m;       // as AlsCgArgs
 };
 
 // acc += sum_e coef_e b_e over entries [e_begin, e_begin + n) of the row (side 0 then side 1 concatenated), wave uw taking every
@@ -139,7 +140,7 @@ __device__ __forceinline__ void als_nncg_accumulate(const AlsCgSide s0, const Al
     }
 }
 
-template <int KP>
+template <int KP, bool LR>
 __global__ __launch_bounds__(256) void als_nncg_kernel(AlsNncgArgs ga) {
     constexpr int VPL = KP >= 64 ? KP / 64 : 1;     // floats of a gathered row per lane
     const AlsCgArgs &g = ga.a;
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(256) void als_nncg_kernel(AlsNncgArgs ga) {
             if (g.S) {
                 for (int c = 0; c < k; ++c) sx = fmaf(g.S[c * KP + t], xs[c], sx);
             }
-            if (t < k) sx += g.l2 * xs[t];
+            if (t < k) sx += als_row_l2<LR>(g.l2, g.l2m, row) * xs[t];   // (wave-uniform)
             o = first ? o - sx : o + sx;
         }
         return o;
@@ -294,7 +295,7 @@ __global__ __launch_bounds__(256) void als_nncg_piece_kernel(AlsNncgLongArgs g) 
     if (t < KP) g.partial[(int64_t)blockIdx.x * KP + t] = ((part[t] + part[KP + t]) + part[2 * KP + t]) + part[3 * KP + t];
 }
 
-template <int KP>
+template <int KP, bool LR>
 __global__ __launch_bounds__(256) void als_nncg_combine_kernel(AlsNncgLongArgs g) {
     __shared__ float xs[KP], wsum[16];
     const int t = threadIdx.x, lane = t & 63;
@@ -354,7 +355,7 @@ __global__ __launch_bounds__(256) void als_nncg_combine_kernel(AlsNncgLongArgs g
         if (g.S) {
             for (int c = 0; c < k; ++c) sx = fmaf(g.S[c * KP + t], xs[c], sx);
         }
-        if (t < k) sx += g.l2 * xs[t];
+        if (t < k) sx += als_row_l2<LR>(g.l2, g.l2m, lr.row) * xs[t];
         o = stage == 0 ? o - sx : o + sx;
     }
     const int passes = in.passes + 1;

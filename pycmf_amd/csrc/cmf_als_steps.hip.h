@@ -4,6 +4,70 @@
 #pragma once
 #ifdef CMF_ALS_HOST
 
+// ------------------------------------------------------------------ per-row l2 (cmf_set_l2_rows)
+// The regulariser l2 / 2 sum_F sum_i m_F[i] |f_i|^2: row i of a sweep of F solves its system under lambda_i = l2 m_F[i].  The device
+// holds m_F as float32 and every row kernel forms lambda_i as ONE float32 product (float)l2 * mult[row] (cmfk::als_row_l2); with
+// nothing bound the pointer is null and lambda_i = l2.  What the host reads of the multipliers:
+//   als_l2_mult    the device image of factor f, or null
+//   als_l2_floor   the smallest lambda of the sweep: the l2 the exact solve derives its threshold from (l2 min(m_F) / 16)
+//   als_l2_shared  the one l2 of a shared route (a factor without an observed relation: ONE matrix for all rows), which takes equal
+//                  multipliers and refuses others
+static const float *als_l2_mult(const cmf_ctx *c, int f) { return c->als_l2rows[f].dev; }
+static double als_l2_floor(const cmf_ctx *c, int f, double l2) { return c->als_l2rows[f].dev ? l2 * (double)c->als_l2rows[f].min : l2; }
+static int als_l2_shared(const cmf_ctx *c, const char *what, int f, double *l2) {
+    const AlsL2Rows &m = c->als_l2rows[f];
+    if (!m.dev) return CMF_OK;
+    if (!m.equal)
+        return fail(CMF_EUNSUPPORTED, "%s: %s has per-row l2 multipliers that differ (cmf_set_l2_rows) but no observed relation: its sweep has one "
+                                      "matrix for all rows and cannot give them different penalties", what, f == CMF_U ? "U" : (f == CMF_V ? "V" : "Z"));
+    *l2 *= (double)m.head;
+    return CMF_OK;
+}
+
+extern "C" int cmf_set_l2_rows(cmf_ctx *c, int which, const double *mult) {
+    NEED_PROBLEM(c);
+    if (which < 0 || which > 2) return fail(CMF_EINVAL, "cmf_set_l2_rows: bad factor selector %d", which);
+    const int64_t n = c->frows[which], np = c->frows_pad[which];
+    std::vector<float> img((size_t)np, 1.0f);
+    if (mult)
+        for (int64_t i = 0; i < n; ++i) {
+            if (!std::isfinite(mult[i]) || !(mult[i] > 0.0) || !std::isfinite((float)mult[i]) || !((float)mult[i] > 0.f))
+                return fail(CMF_EINVAL, "cmf_set_l2_rows: multiplier %lld is %g; every multiplier must be finite and positive (in float32 too)", (long long)i, mult[i]);
+            img[(size_t)i] = (float)mult[i];
+        }
+    DeviceGuard dg(c->device);
+    AlsL2Rows &m = c->als_l2rows[which];
+    if (!mult) {
+        if (m.dev) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            dev_free(c, m.dev);
+        }
+        m = AlsL2Rows();
+        return CMF_OK;
+    }
+    if (!m.dev) CHK(dev_alloc(c, (void **)&m.dev, (size_t)np * sizeof(float), false));
+    HIPCHK(hipMemcpyAsync(m.dev, img.data(), (size_t)np * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream)); // the host vector may go
+    m.host.assign(mult, mult + n);
+    m.min = m.head = n > 0 ? img[0] : 1.0f;
+    m.equal = true;
+    for (int64_t i = 1; i < n; ++i) {
+        m.min = std::min(m.min, img[(size_t)i]);
+        m.equal = m.equal && img[(size_t)i] == m.head;
+    }
+    return CMF_OK;
+}
+
+extern "C" int cmf_get_l2_rows(cmf_ctx *c, int which, double *mult, int *set) {
+    NEED_PROBLEM(c);
+    if (which < 0 || which > 2) return fail(CMF_EINVAL, "cmf_get_l2_rows: bad factor selector %d", which);
+    const AlsL2Rows &m = c->als_l2rows[which];
+    if (set) *set = m.dev ? 1 : 0;
+    if (mult)
+        for (int64_t i = 0; i < c->frows[which]; ++i) mult[i] = m.dev ? m.host[(size_t)i] : 1.0;
+    return CMF_OK;
+}
+
 // lg: the sweep reads a logistic relation (a.F, a.logit0 / logit1 are set): the instance with the reweighting, and its dot products
 static int als_launch_normal(cmf_ctx *c, const cmfk::AlsArgs &a, int64_t npieces, int64_t nnz, bool lg) {
     if (npieces <= 0) return CMF_OK;
@@ -51,8 +115,9 @@ struct AlsChunk { int64_t slot0, row0, nr; float *H; const float *g; const int64
 // THE chunk loop: the only caller of als_normal_kernel / als_finish_kernel.  The slots of the plan in per-row form, chunk by chunk:
 // als_normal_kernel over the chunk's pieces, als_finish_kernel, then use(chunk).  A chunk holds at most `cap` slots and (but for a
 // single slot) as many pieces.  A plan that is not on the device yet is sent there.
+// lrows (a plan of listed rows): the device list of the rows of the slots, which the per-row l2 is looked up by.
 template <class Use>
-static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, AlsPlan &pl, int64_t cap, Use use) {
+static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, AlsPlan &pl, int64_t cap, Use use, const int64_t *lrows = nullptr) {
     using namespace cmfk;
     const int kp = c->kp;
     const int64_t kk = (int64_t)kp * kp, nslots = (int64_t)pl.first.size() - 1;
@@ -76,6 +141,7 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, AlsPlan &pl, in
     memset(&a, 0, sizeof a);
     als_bind_sides(sw, a.s0, a.s1);
     float *Hc = (float *)c->als_h.p, *Hp = (float *)c->als_part.p;
+    const float *l2m = als_l2_mult(c, sw.f);   // the finish kernel finds a slot's multiplier by its row: row0 + slot, or lrows[slot]
     a.Hp = Hp;
     a.gp = Hp + std::max<int64_t>(1, max_pieces) * kk;
     if (lg) {
@@ -93,8 +159,13 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, AlsPlan &pl, in
         CHK(als_launch_normal(c, a, np, nnz, lg));
         {
             Timed tm(c, CMF_K_ELEMWISE);
-            hipLaunchKernelGGL(als_finish_kernel, dim3((unsigned)nr), dim3(256), 0, c->stream, (const float *)Hp, (const float *)a.gp, pl.dfirst + c0, pbase, pl.S,
-                               pl.N ? pl.N + row0 * kp : nullptr, (float)l2, c->k, kp, Hc, grad);
+            if (l2m)
+                hipLaunchKernelGGL(als_finish_kernel<true>, dim3((unsigned)nr), dim3(256), 0, c->stream, (const float *)Hp, (const float *)a.gp, pl.dfirst + c0, pbase,
+                                   pl.S, pl.N ? pl.N + row0 * kp : nullptr, (float)l2, c->k, kp, Hc, grad, pl.listed ? l2m : l2m + row0,
+                                   pl.listed ? lrows + c0 : nullptr);
+            else
+                hipLaunchKernelGGL(als_finish_kernel<false>, dim3((unsigned)nr), dim3(256), 0, c->stream, (const float *)Hp, (const float *)a.gp, pl.dfirst + c0, pbase,
+                                   pl.S, pl.N ? pl.N + row0 * kp : nullptr, (float)l2, c->k, kp, Hc, grad, (const float *)nullptr, (const int64_t *)nullptr);
             HIPCHK(hipGetLastError());
         }
         CHK(use(AlsChunk{c0, row0, nr, Hc, grad, pl.S ? nullptr : pl.dfirst + c0}));
@@ -109,7 +180,7 @@ static int als_chunks_range(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r
     AlsPlan pl;
     CHK(als_shared_terms(c, sw, &pl.S, &pl.N));
     CHK(als_plan(c, sw, r_begin, r_end, pl));
-    return als_chunks(c, sw, l2, pl, cap, use);
+    return als_chunks(c, sw, l2, pl, cap, use);   // (a range: no list)
 }
 
 // What safe_solve_rows (cmf_newton.hip.h) reads and writes of the Newton step's state: put back when the scope ends.
@@ -126,6 +197,7 @@ struct AlsNewtonStateGuard {
 // matrices declared positive semi-definite.  Its threshold l2 / 16 lies well below l2: the test of that route (a Cholesky of
 // H_i - pert I whose pivots must exceed 4e-6 max H_jj) passes unless cond(H_i) is above ~2e5, where a float32 factorisation has
 // nothing left to give.  The exact rows, the dual systems and the formed rows of a dual sweep all come here.
+// Under per-row multipliers the caller passes the smallest lambda of the sweep (als_l2_floor): lambda_min >= that for every row.
 static int als_solve_rows(cmf_ctx *c, float *H, const float *g, float *out, int64_t nr, int n, int np, double l2) {
     AlsNewtonStateGuard keep(c);
     c->hess_psd = true;
@@ -136,7 +208,7 @@ static int als_solve_rows(cmf_ctx *c, float *H, const float *g, float *out, int6
 static int als_rows_solve(cmf_ctx *c, const AlsSweep &sw, double l2) {
     CHK(ensure_scratch(c, c->als_sol, (size_t)c->frows_pad[sw.f] * c->kp * sizeof(float)));
     return als_chunks_range(c, sw, l2, 0, c->frows[sw.f], hessian_chunk_rows(c, c->frows_pad[sw.f]), [&](const AlsChunk &ch) -> int {
-        return als_solve_rows(c, ch.H, ch.g, (float *)c->als_sol.p + ch.row0 * c->kp, ch.nr, c->k, c->kp, l2);
+        return als_solve_rows(c, ch.H, ch.g, (float *)c->als_sol.p + ch.row0 * c->kp, ch.nr, c->k, c->kp, als_l2_floor(c, sw.f, l2));
     });
 }
 
@@ -164,6 +236,7 @@ static int als_apply(cmf_ctx *c, int f, const float *sol, bool nn) {
 
 // shared exact: F <- clamp(N (G + l2 I)^-1), the inverse formed once in float64
 static int als_sweep_shared(cmf_ctx *c, const char *what, const AlsSweep &sw, double l2, bool nn) {
+    CHK(als_l2_shared(c, what, sw.f, &l2));
     CHK(ensure_shared64(c));
     for (int s = 0; s < sw.nrel; ++s) {
         const AlsRel &r = sw.rel[s];
@@ -179,7 +252,8 @@ static int als_sweep_shared(cmf_ctx *c, const char *what, const AlsSweep &sw, do
 }
 
 // shared HALS: N and G as cmf_hals_step forms them, `sweeps` passes of hals_sweep
-static int als_nnls_sweep_shared(cmf_ctx *c, int f, double l2, int sweeps) {
+static int als_nnls_sweep_shared(cmf_ctx *c, const char *what, int f, double l2, int sweeps) {
+    CHK(als_l2_shared(c, what, f, &l2));
     const float *N = c->num, *G = c->G2;
     if (f == CMF_V) {
         CHK(cmf_mu_v_partials(c, c->vbuf));
@@ -206,8 +280,13 @@ static int als_cg_launch(cmf_ctx *c, const cmfk::AlsCgArgs &a, int64_t nrows) {
     if (nrows <= 0) return CMF_OK;
     const size_t lds = 4 * (size_t)cmfk::als_cg_fixed_floats(c->kp) + (size_t)a.cap * cmfk::als_cg_entry_bytes(c->kp);
     const dim3 grid((unsigned)nrows), block(256);
-    ALS_LAUNCH_KP(c, als_cg_kernel, "the conjugate-gradient row solve is",
-                  CHK(allow_big_lds(c, (const void *)kern, ALS_CG_LDS_TOTAL)); hipLaunchKernelGGL(kern, grid, block, lds, c->stream, a));
+    if (a.l2m) {   // per-row l2: the LR = true instance
+        ALS_LAUNCH_KP(c, als_cg_kernel, "the conjugate-gradient row solve is",
+                      CHK(allow_big_lds(c, (const void *)kern, ALS_CG_LDS_TOTAL)); hipLaunchKernelGGL(kern, grid, block, lds, c->stream, a), true);
+    } else {
+        ALS_LAUNCH_KP(c, als_cg_kernel, "the conjugate-gradient row solve is",
+                      CHK(allow_big_lds(c, (const void *)kern, ALS_CG_LDS_TOTAL)); hipLaunchKernelGGL(kern, grid, block, lds, c->stream, a), false);
+    }
     return CMF_OK;
 }
 
@@ -225,7 +304,11 @@ static int als_cg_long_rows(cmf_ctx *c, cmfk::AlsCgPieceArgs &a, int64_t nlong, 
     for (int s = 0; s <= steps; ++s) {
         a.phase = s == 0 ? 0 : (s == steps ? 2 : 1);
         ALS_LAUNCH_KP(c, als_cg_piece_kernel, "the conjugate-gradient row solve is", hipLaunchKernelGGL(kern, pgrid, block, 0, c->stream, a));
-        ALS_LAUNCH_KP(c, als_cg_combine_kernel, "the conjugate-gradient row solve is", hipLaunchKernelGGL(kern, cgrid, block, 0, c->stream, a));
+        if (a.l2m) {
+            ALS_LAUNCH_KP(c, als_cg_combine_kernel, "the conjugate-gradient row solve is", hipLaunchKernelGGL(kern, cgrid, block, 0, c->stream, a), true);
+        } else {
+            ALS_LAUNCH_KP(c, als_cg_combine_kernel, "the conjugate-gradient row solve is", hipLaunchKernelGGL(kern, cgrid, block, 0, c->stream, a), false);
+        }
     }
     return CMF_OK;
 }
@@ -276,7 +359,7 @@ static int als_nncg_launches(cmf_ctx *c, const cmfk::AlsCgArgs &a, const std::ve
         pa.partial = pa.state + 5 * nl * (size_t)kp;
         pa.info = (AlsNncgRow *)(pa.state + sfloats);
         pa.passes = na.passes;
-        pa.l2 = a.l2; pa.k = a.k;
+        pa.l2 = a.l2; pa.l2m = a.l2m; pa.k = a.k;
     }
     c->als_nncg_lens.assign(lens.begin(), lens.end());   // (each at most 2^31 - 1: the planner's check)
     c->als_nncg_counted = false;
@@ -293,8 +376,13 @@ static int als_nncg_launches(cmf_ctx *c, const cmfk::AlsCgArgs &a, const std::ve
             if (n <= 0) continue;
             const size_t lds = 4 * (size_t)als_cg_fixed_floats(kp) + (size_t)na.a.cap * als_cg_entry_bytes(kp);
             const dim3 grid((unsigned)n), block(256);
-            ALS_LAUNCH_KP(c, als_nncg_kernel, "the non-negative conjugate-gradient row solve is",
-                          CHK(allow_big_lds(c, (const void *)kern, ALS_CG_LDS_TOTAL)); hipLaunchKernelGGL(kern, grid, block, lds, c->stream, na));
+            if (a.l2m) {   // per-row l2: the LR = true instance
+                ALS_LAUNCH_KP(c, als_nncg_kernel, "the non-negative conjugate-gradient row solve is",
+                              CHK(allow_big_lds(c, (const void *)kern, ALS_CG_LDS_TOTAL)); hipLaunchKernelGGL(kern, grid, block, lds, c->stream, na), true);
+            } else {
+                ALS_LAUNCH_KP(c, als_nncg_kernel, "the non-negative conjugate-gradient row solve is",
+                              CHK(allow_big_lds(c, (const void *)kern, ALS_CG_LDS_TOTAL)); hipLaunchKernelGGL(kern, grid, block, lds, c->stream, na), false);
+            }
         }
         if (nl) {
             const dim3 pgrid((unsigned)npieces), cgrid((unsigned)nl), block(256);
@@ -302,7 +390,11 @@ static int als_nncg_launches(cmf_ctx *c, const cmfk::AlsCgArgs &a, const std::ve
                 pa.stage = s == 0 ? 0 : 2 - (s & 1);
                 pa.last = s == 2 * steps ? 1 : 0;
                 ALS_LAUNCH_KP(c, als_nncg_piece_kernel, "the non-negative conjugate-gradient row solve is", hipLaunchKernelGGL(kern, pgrid, block, 0, c->stream, pa));
-                ALS_LAUNCH_KP(c, als_nncg_combine_kernel, "the non-negative conjugate-gradient row solve is", hipLaunchKernelGGL(kern, cgrid, block, 0, c->stream, pa));
+                if (a.l2m) {
+                    ALS_LAUNCH_KP(c, als_nncg_combine_kernel, "the non-negative conjugate-gradient row solve is", hipLaunchKernelGGL(kern, cgrid, block, 0, c->stream, pa), true);
+                } else {
+                    ALS_LAUNCH_KP(c, als_nncg_combine_kernel, "the non-negative conjugate-gradient row solve is", hipLaunchKernelGGL(kern, cgrid, block, 0, c->stream, pa), false);
+                }
             }
         }
     }
@@ -379,6 +471,7 @@ static int als_cg_rows(cmf_ctx *c, const char *what, const AlsSweep &sw, double 
     a.Fout = Fout;
     a.out_row0 = out_row0;
     a.l2 = (float)l2;
+    a.l2m = als_l2_mult(c, sw.f);
     a.k = c->k;
     a.steps = steps;
     if (nn) return als_nncg_launches(c, a, lens, list, caps, drows, dlongs, dpieces, longs, (int64_t)pieces.size(), nrows);
@@ -394,7 +487,7 @@ static int als_cg_rows(cmf_ctx *c, const char *what, const AlsSweep &sw, double 
         pa.partial = pa.state + 3 * nl * (size_t)kp;
         pa.rr = pa.state + sfloats;
         pa.alive = (int32_t *)(pa.rr + nl);
-        pa.l2 = a.l2; pa.k = a.k;
+        pa.l2 = a.l2; pa.l2m = a.l2m; pa.k = a.k;
     }
     Timed tm(c, CMF_K_ROWHESS, (4.0 * (double)nnz * c->k + (a.S ? 2.0 * (double)nrows * c->k * c->k : 0.0)) * (steps + 1));
     int64_t done = 0;
@@ -427,21 +520,26 @@ static const char *als_dual_why_not(const cmf_ctx *c, const AlsSweep &sw) {
     return nullptr;
 }
 
-template <int KP>
-static int als_dual_launch_class(cmf_ctx *c, const cmfk::AlsDualArgs &a, int np) {
+template <int KP, bool LR>
+static int als_dual_launch_class_lr(cmf_ctx *c, const cmfk::AlsDualArgs &a, int np) {
     using namespace cmfk;
     const dim3 block(256);
     if constexpr (KP > 32) {
-        if (np == 32) hipLaunchKernelGGL((als_dual_gram_kernel<KP, 32>), dim3((unsigned)((a.nrows + 3) / 4)), block, 0, c->stream, a);
+        if (np == 32) hipLaunchKernelGGL((als_dual_gram_kernel<KP, 32, LR>), dim3((unsigned)((a.nrows + 3) / 4)), block, 0, c->stream, a);
     }
     if constexpr (KP > 64) {
-        if (np == 64) hipLaunchKernelGGL((als_dual_gram_kernel<KP, 64>), dim3((unsigned)a.nrows), block, 0, c->stream, a);
+        if (np == 64) hipLaunchKernelGGL((als_dual_gram_kernel<KP, 64, LR>), dim3((unsigned)a.nrows), block, 0, c->stream, a);
     }
     if constexpr (KP > 128) {
-        if (np == 128) hipLaunchKernelGGL((als_dual_gram_kernel<KP, 128>), dim3((unsigned)a.nrows), block, 0, c->stream, a);
+        if (np == 128) hipLaunchKernelGGL((als_dual_gram_kernel<KP, 128, LR>), dim3((unsigned)a.nrows), block, 0, c->stream, a);
     }
     HIPCHK(hipGetLastError());
     return CMF_OK;
+}
+// (per-row l2 bound: the LR = true instances)
+template <int KP>
+static int als_dual_launch_class(cmf_ctx *c, const cmfk::AlsDualArgs &a, int np) {
+    return a.l2m ? als_dual_launch_class_lr<KP, true>(c, a, np) : als_dual_launch_class_lr<KP, false>(c, a, np);
 }
 
 // Rows [r_begin, r_end) of an ELIGIBLE sweep (als_dual_why_not is null, k_pad > 32) under dual_max >= 1: the dual rows class by class
@@ -487,6 +585,7 @@ static int als_dual_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_be
     a.Fout = Fout;
     a.out_row0 = out_row0;
     a.l2 = (float)l2;
+    a.l2m = als_l2_mult(c, sw.f);
     a.k = c->k;
     a.nn = nn ? 1 : 0;
     int64_t done = 0;
@@ -512,7 +611,7 @@ static int als_dual_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_be
                 default: return fail(CMF_EUNSUPPORTED, "the dual ALS rows are built for k_pad 64, 128 and 256 (k_pad = %d)", kp);
                 }
             }
-            CHK(als_solve_rows(c, a.K, a.y, z, nr, np, np, l2));
+            CHK(als_solve_rows(c, a.K, a.y, z, nr, np, np, als_l2_floor(c, sw.f, l2)));
             {
                 Timed tm(c, CMF_K_ELEMWISE);
                 const dim3 grid((unsigned)((nr + 3) / 4)), block(256);
@@ -533,9 +632,9 @@ static int als_dual_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_be
     CHK(ensure_scratch(c, c->als_sol, (size_t)std::min(cnt[ALS_DUAL_FORMED], cap_exact) * kp * sizeof(float)));   // (a chunk's rows)
     return als_chunks(c, sw, l2, pl, cap_exact, [&](const AlsChunk &ch) -> int {
         float *sol = (float *)c->als_sol.p;
-        CHK(als_solve_rows(c, ch.H, ch.g, sol, ch.nr, c->k, kp, l2));
+        CHK(als_solve_rows(c, ch.H, ch.g, sol, ch.nr, c->k, kp, als_l2_floor(c, sw.f, l2)));
         return launch_ew(c, als_dual_scatter_kernel, ch.nr * kp, Fout, out_row0, dformed + ch.slot0, (const float *)sol, ch.nr, c->k, kp, nn ? 1 : 0);
-    });
+    }, dformed);
 }
 
 // ------------------------------------------------------------------ the dispatcher
@@ -572,7 +671,7 @@ static int als_step(cmf_ctx *c, const char *what, double l2, int nn_mask, int ma
         const AlsSweep sw = als_sweep(c, f);
         switch (als_route(als_observed(sw), als_shared_present(c, sw), als_logit_sweep(c, sw), c->kp, nn, o)) {
         case ALS_SHARED_EXACT: CHK(als_sweep_shared(c, what, sw, l2, nn)); break;
-        case ALS_SHARED_HALS: CHK(als_nnls_sweep_shared(c, f, l2, o.nn_sweeps)); break;
+        case ALS_SHARED_HALS: CHK(als_nnls_sweep_shared(c, what, f, l2, o.nn_sweeps)); break;
         case ALS_ROWS_NNLS: CHK(als_rows_nnls(c, sw, l2, o.nn_sweeps)); break;
         case ALS_ROWS_CG: CHK(als_cg_rows(c, what, sw, l2, 0, c->frows[f], o.cg_steps, c->F[f], 0)); break;
         case ALS_ROWS_NNCG: CHK(als_cg_rows(c, what, sw, l2, 0, c->frows[f], o.nn_cg_steps, c->F[f], 0, true)); break;

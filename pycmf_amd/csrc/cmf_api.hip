@@ -108,6 +108,16 @@ struct AlsBias {
     int64_t L = 0;                    // the piece length the lists were built for
 };
 
+// Per-row multipliers of l2 for one factor under the ALS steps (cmf_set_l2_rows): the doubles as given, their float32 image on the
+// device padded with 1.0f to frows_pad, and what the host routes read of that image: its minimum (the threshold of the exact solve)
+// and whether all values are equal (the shared routes have one matrix for all rows).
+struct AlsL2Rows {
+    float *dev = nullptr;             // null: none bound
+    std::vector<double> host;
+    float min = 1.0f, head = 1.0f;    // of the float32 values; head: the first one
+    bool equal = true;
+};
+
 // A captured update step: replayed with hipGraphLaunch while the key (hyper-parameters baked into
 // kernel arguments) and every device pointer it references stay unchanged.
 struct StepGraph {
@@ -179,6 +189,7 @@ struct cmf_ctx {
     bool als_nncg_counted = true;
     int64_t als_dual_last[5] = {0, 0, 0, 0, 0}; // dual ALS rows (cmf_als_dual.hip.h): rows in class 32, 64, 128, rows left to the formed route, rows written as zeros in the last dual sweep
     DevBuf als_dual_ws;                   // ... K, y and z of a chunk of dual rows
+    AlsL2Rows als_l2rows[3];              // per-row multipliers of l2 for U / V / Z under the ALS steps (cmf_set_l2_rows; off: none)
     double wm_bg[2] = {0.0, 0.0};         // background weight c0 of X / Y on the cells outside a CSR pattern (cmf_als_bg.hip.h; 0: none)
     DevBuf als_bg_s, als_bg64;            // ... the shared matrix sum coef Gram of a sweep; float64 Grams of the error's trace term
     int rel_loss[2] = {0, 0};             // loss of X / Y under the ALS steps (cmf_als_logit.hip.h): CMF_LOSS_FROBENIUS | CMF_LOSS_LOGISTIC
@@ -870,6 +881,7 @@ static void release_problem(cmf_ctx *c) {
     c->als_dual_ws = DevBuf(); for (int q = 0; q < 5; ++q) c->als_dual_last[q] = 0;
     c->als_bg_s = DevBuf(); c->als_bg64 = DevBuf();
     c->als_bias_part = DevBuf(); c->als_bias_ws = DevBuf();
+    for (int f = 0; f < 3; ++f) c->als_l2rows[f] = AlsL2Rows();   // (the device images went with c->owned)
     for (int w = 0; w < 2; ++w) {
         c->als_bias[w] = AlsBias();
         c->rel_loss[w] = 0;

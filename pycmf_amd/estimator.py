@@ -13,7 +13,7 @@ from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
 from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_beta, check_beta_extras, check_beta_data, check_entry_weights, check_hals,
-                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_als_nn_cg_steps, check_als_dual_max, check_background_weight, check_biases, check_bias_l2, check_logistic)
+                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_als_nn_cg_steps, check_als_dual_max, check_als_l2_scale, check_background_weight, check_biases, check_bias_l2, check_logistic)
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -43,7 +43,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                     device=0, sg_sampler="numpy", n_gpus=1, _return_solver=False, loss="frobenius",
                                     x_entry_weights=None, y_entry_weights=None, als_nn_sweeps=0, als_cg_steps=0,
                                     x_background_weight=0.0, y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None,
-                                    _x_bias_init=None, _y_bias_init=None, als_nn_cg_steps=0, als_dual_max=0):
+                                    _x_bias_init=None, _y_bias_init=None, als_nn_cg_steps=0, als_dual_max=0, als_l2_scale=0.0):
     """Factorise X ~ f(U V^T) and Y ~ f(V Z^T) with a shared V on an MI355X.
 
     Same contract as the reference function (pycmf/cmf.py:215-456): returns
@@ -113,6 +113,13 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     (K = A A^T + l2 I, f = A^T K^-1 y) instead of its k x k one -- the same exact minimiser, far cheaper when most rows have fewer
     entries than components (``HipALSSolver``).  Every other sweep keeps its route; biases are honoured.
 
+    ``als_l2_scale``: 0 | nu in (0, 1] (``solver='als'`` and ``n_gpus=1`` only; ``ValueError`` otherwise, and for a bool or a value
+    outside [0, 1], before any device is touched).  nu > 0: the frequency-scaled regulariser -- row i of a factor is penalised by
+    l2_reg max(c_i, 1)^nu / 2 |f_i|^2, c_i the stored entries with a positive weight its sweep reads (plus the background weight
+    times the cells of the row; every cell of a relation without weights): ``pycmf_amd.l2_multipliers``.  nu = 1 is ALS-WR's
+    weighted-lambda regulariser.  Composes with every other ALS keyword; the bias blocks keep ``bias_l2`` unscaled
+    (``HipALSSolver``).
+
     ``x_background_weight`` / ``y_background_weight``: 0 | c0 > 0 (``solver='als'`` only) -- implicit feedback.  The relation's
     entry weights must be a SciPy sparse W or ``'observed'`` with every stored weight >= c0; the cells outside that pattern then
     count with weight c0 and target 0 instead of not at all: 1/2 sum_O w (t - a.b)^2 + 1/2 c0 sum_{not O} (a.b)^2, at the cost of
@@ -142,6 +149,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                                                        (Z_non_negative, update_Z)) if upd],
                           n_gpus, loss, bool(x_biases) or bool(y_biases))
     check_als_dual_max(als_dual_max, solver, n_gpus, als_cg_steps)
+    als_l2_scale = check_als_l2_scale(als_l2_scale, solver, n_gpus)
     x_background_weight = check_background_weight(x_background_weight, "x", solver, x_entry_weights)
     y_background_weight = check_background_weight(y_background_weight, "y", solver, y_entry_weights)
     x_biases = check_biases(x_biases, "x", solver, x_entry_weights, x_background_weight)
@@ -204,7 +212,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                      x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, nn_sweeps=als_nn_sweeps, cg_steps=als_cg_steps,
                                      x_background_weight=x_background_weight, y_background_weight=y_background_weight,
                                      x_biases=x_biases, y_biases=y_biases, bias_l2=bias_l2, x_bias_init=_x_bias_init,
-                                     y_bias_init=_y_bias_init, nn_cg_steps=als_nn_cg_steps, dual_max=als_dual_max, **common)
+                                     y_bias_init=_y_bias_init, nn_cg_steps=als_nn_cg_steps, dual_max=als_dual_max, l2_scale=als_l2_scale, **common)
         solver_object.check_weights(X, Y)
     else:
         raise ValueError("No such solver: %s" % solver)
@@ -372,9 +380,15 @@ class CMF(BaseEstimator, TransformerMixin):
     (``collective_matrix_factorization``); ``CMF(solver="als", l2_reg=0.05, als_dual_max=128, U_non_negative=False,
     V_non_negative=False, Z_non_negative=False)``.  ``transform`` honours it: the fold-in of new rows is a sweep over short
     observed rows.  A keyword-only OPTION like ``als_nn_cg_steps``.
+
+    ``als_l2_scale`` (``solver='als'`` only, default 0.0): nu in (0, 1] scales the l2 penalty of every factor row by
+    max(c_i, 1)^nu, c_i the entries its sweep reads in that row (``collective_matrix_factorization``, ``pycmf_amd.l2_multipliers``):
+    ``CMF(solver="als", l2_reg=0.05, als_l2_scale=1.0)`` is ALS-WR's weighted-lambda regulariser.  After a fit ``l2_multipliers_``
+    holds ``(m_U, m_V, m_Z)`` (None with the option off); ``transform`` counts the rows of the X / Y it is given, so a folded-in
+    row gets the penalty of its own length.  A keyword-only OPTION like ``als_nn_cg_steps``.
     """
 
-    _OPTIONS = {"als_nn_cg_steps": 0, "als_dual_max": 0}     # keyword-only options outside get_params(): name -> default
+    _OPTIONS = {"als_nn_cg_steps": 0, "als_dual_max": 0, "als_l2_scale": 0.0}     # keyword-only options outside get_params(): name -> default
 
     def __init__(self, n_components=None, x_init=None, y_init=None, solver='mu', alpha='auto',
                  beta_loss='frobenius', tol=1e-4, max_iter=600,
@@ -441,7 +455,7 @@ class CMF(BaseEstimator, TransformerMixin):
                     hessian_pertubation=self.hessian_pertubation,
                     sg_sample_ratio=self.sg_sample_ratio, device=self.device, sg_sampler=self.sg_sampler,
                     loss=self.loss, als_nn_sweeps=self.als_nn_sweeps, als_cg_steps=self.als_cg_steps,
-                    als_nn_cg_steps=self.als_nn_cg_steps, als_dual_max=self.als_dual_max)
+                    als_nn_cg_steps=self.als_nn_cg_steps, als_dual_max=self.als_dual_max, als_l2_scale=self.als_l2_scale)
 
     def fit_transform(self, X, Y, U=None, V=None, Z=None, x_entry_weights=None, y_entry_weights=None, x_background_weight=0.0,
                       y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None):
@@ -474,6 +488,7 @@ class CMF(BaseEstimator, TransformerMixin):
         self.x_bias_ = _fitted_bias(getattr(solver_object, "x_bias", None))
         self.y_bias_ = _fitted_bias(getattr(solver_object, "y_bias", None))
         self.bias_l2_ = bias_l2
+        self.l2_multipliers_ = getattr(solver_object, "l2_multipliers", None)   # (m_U, m_V, m_Z) under als_l2_scale > 0, else None
         solver_object.release()
         self.n_components_ = U.shape[1]
         self.x_weights = U

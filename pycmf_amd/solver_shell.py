@@ -779,6 +779,87 @@ def check_als_dual_max(als_dual_max, solver="als", n_gpus=1, als_cg_steps=0):
                          "could (signed factors with entry weights): one of the two must be 0" % (als_dual_max, als_cg_steps))
 
 
+def check_als_l2_scale(als_l2_scale, solver="als", n_gpus=1):
+    """``als_l2_scale``: a real number nu in [0, 1] (a bool is refused); non-zero with solver='als' on one GPU only.  It composes with
+    every other ALS keyword.  No device is touched.  Returns nu as a float."""
+    if isinstance(als_l2_scale, (bool, np.bool_)) or not isinstance(als_l2_scale, (numbers.Real, np.integer, np.floating)):
+        raise ValueError("als_l2_scale must be a number in [0, 1], got %r" % (als_l2_scale,))
+    nu = float(als_l2_scale)
+    if not (0.0 <= nu <= 1.0):
+        raise ValueError("als_l2_scale must be a number in [0, 1], got %r" % (als_l2_scale,))
+    if not nu:
+        return 0.0
+    if solver != "als":
+        raise ValueError("als_l2_scale is the frequency-scaled regulariser of solver='als': it must be 0 with solver=%r, got %r" % (solver, als_l2_scale))
+    if n_gpus != 1:
+        raise ValueError("als_l2_scale=%r runs on one GPU: n_gpus must be 1, got %r" % (als_l2_scale, n_gpus))
+    return nu
+
+
+def _relation_counts(shape, W):
+    """(per row, per column) of one relation of ``shape``: the stored entries with a weight > 0 of an observed relation (``W``: a
+    SciPy sparse matrix, a dense array, or resolved ``EntryWeights``), or None, None for a full one (``W`` None)."""
+    if W is None:
+        return None, None
+    if isinstance(W, EntryWeights):
+        if W.kind == "csr":
+            indptr, indices, w = np.asarray(W.indptr, dtype=np.int64), np.asarray(W.indices, dtype=np.int64), np.asarray(W.w, dtype=np.float64)
+        else:
+            return _relation_counts(shape, np.asarray(W.W))
+    elif hasattr(W, "tocsr"):
+        A = _canonical_csr(W)
+        if A.shape != tuple(shape):
+            raise ValueError("weights of shape %s for a relation of shape %s" % (A.shape, tuple(shape)))
+        indptr, indices, w = A.indptr.astype(np.int64), A.indices.astype(np.int64), np.asarray(A.data, dtype=np.float64)
+    else:
+        D = np.asarray(W, dtype=np.float64)
+        if D.shape != tuple(shape):
+            raise ValueError("weights of shape %s for a relation of shape %s" % (D.shape, tuple(shape)))
+        return (D > 0).sum(axis=1).astype(np.float64), (D > 0).sum(axis=0).astype(np.float64)
+    if indptr.size != shape[0] + 1:
+        raise ValueError("a pattern of %d rows for a relation of shape %s" % (indptr.size - 1, tuple(shape)))
+    rows = np.repeat(np.arange(shape[0]), np.diff(indptr))
+    keep = w > 0
+    return (np.bincount(rows[keep], minlength=shape[0]).astype(np.float64),
+            np.bincount(indices[keep], minlength=shape[1]).astype(np.float64))
+
+
+def l2_multipliers(shape_x, shape_y, x_weights, y_weights, x_background_weight=0.0, y_background_weight=0.0, nu=1.0):
+    """``(m_U, m_V, m_Z)``: the per-row multipliers of ``l2`` of the frequency-scaled regulariser (``Context.set_l2_rows``,
+    ``CMF(als_l2_scale=nu)``), NumPy float64, on the host; None for a factor that reads no relation.
+
+        m_F[i] = max(c_F[i], 1) ** nu,      c_F[i] summed over the relations the sweep of F reads (U: X; Z: Y; V: both):
+
+    an OBSERVED relation (``*_weights``: SciPy sparse, a dense array, or resolved ``EntryWeights``) counts the stored entries with a
+    weight > 0 of that row -- of that column on the transposed side --, n; under a background weight c0 it counts n + c0 D, D the
+    cells of the row (Rendle, Krichene, Zhang, Koren: |I_u| + alpha0 |I|); a FULL relation (``*_weights`` None) counts D.
+    ``shape_x`` / ``shape_y``: the shapes of X (m x d) and Y (d x p), None for a relation that is not there.  nu = 1 with observed
+    relations is the weighted-lambda regulariser of ALS-WR (Zhou, Wilkinson, Schreiber, Pan); nu = 0 gives all ones.  The floor at 1
+    keeps lambda_i >= l2: a row without an entry still solves lambda f = 0."""
+    nu = float(nu)
+    if not np.isfinite(nu):
+        raise ValueError("nu must be finite, got %r" % (nu,))
+    if shape_x is not None and shape_y is not None and shape_x[1] != shape_y[0]:
+        raise ValueError("shape_x[1] must equal shape_y[0], got %s and %s" % (tuple(shape_x), tuple(shape_y)))
+    c = [None, None, None]          # U, V, Z
+
+    def add(f, v):
+        c[f] = v if c[f] is None else c[f] + v
+
+    for shape, W, c0, frow, fcol in ((shape_x, x_weights, x_background_weight, 0, 1), (shape_y, y_weights, y_background_weight, 1, 2)):
+        if shape is None:
+            continue
+        r, k = int(shape[0]), int(shape[1])
+        nr, nc = _relation_counts((r, k), W)
+        if nr is None:                          # full: every cell of the row
+            nr, nc = np.full(r, float(k)), np.full(k, float(r))
+        elif c0:
+            nr, nc = nr + float(c0) * k, nc + float(c0) * r
+        add(frow, nr)
+        add(fcol, nc)
+    return tuple(None if v is None else np.maximum(v, 1.0) ** nu for v in c)
+
+
 class HipALSSolver(HipMUSolver):
     """Alternating least squares in MU's sweep order V -> U -> Z (``cmf_als_step`` / ``cmf_als_nnls_step``) on
 
@@ -822,6 +903,15 @@ class HipALSSolver(HipMUSolver):
     instead of a k x k one, when the padded n (32, 64, 128) is below k_pad.  Other rows of such a sweep keep their bits, other
     sweeps their routes; biases are honoured.  Not together with ``cg_steps``.
 
+    ``l2_scale=nu`` (a number in [0, 1]; default 0: off): the FREQUENCY-SCALED regulariser.  Row i of factor F is penalised by
+    l2 m_F[i] / 2 |f_i|^2 with m_F[i] = max(c_F[i], 1)^nu, c_F[i] the stored entries with a positive weight the sweep of F reads in
+    that row (plus c0 times the cells of the row under a background weight; every cell of a relation without weights) --
+    ``l2_multipliers``.  nu = 1 is the weighted-lambda regulariser of ALS-WR, 0 < nu < 1 the form of Rendle et al. for implicit
+    feedback.  The multipliers are computed on the host from the resolved patterns when a problem is bound, set for the factors this
+    solver updates (``cmf_set_l2_rows``) and kept on ``l2_multipliers``; every route above honours them, row by row, and every
+    descent statement above holds for the objective with the scaled regulariser.  The bias blocks keep ``bias_l2`` unscaled.  A
+    factor whose relations are all unweighted has equal counts, hence one l2 for its shared matrix.
+
     ``x_background_weight=c0`` / ``y_background_weight`` (default 0): the implicit-feedback model (Hu, Koren, Volinsky).  The
     relation must have sparse entry weights W (or ``'observed'``) with every stored weight >= c0; the cells outside W's pattern
     then count with weight c0 and target 0,
@@ -859,8 +949,10 @@ class HipALSSolver(HipMUSolver):
 
     def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, cg_steps=0, x_background_weight=0.0,
                  y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None, x_bias_init=None, y_bias_init=None,
-                 loss="frobenius", nn_cg_steps=0, dual_max=0, **kwargs):
+                 loss="frobenius", nn_cg_steps=0, dual_max=0, l2_scale=0.0, **kwargs):
         check_loss(loss, "als")
+        self.l2_scale = check_als_l2_scale(l2_scale)
+        self.l2_multipliers = None           # (m_U, m_V, m_Z) of the bound problem under l2_scale > 0
         check_als(loss=loss)
         check_als_nn_sweeps(nn_sweeps)
         check_als_cg_steps(cg_steps)
@@ -891,7 +983,7 @@ class HipALSSolver(HipMUSolver):
         self.dual_max = int(dual_max)
 
     def _weights_key(self):
-        return super()._weights_key() + (self.x_background_weight, self.y_background_weight, self.x_biases, self.y_biases) + tuple(self._logit)
+        return super()._weights_key() + (self.x_background_weight, self.y_background_weight, self.x_biases, self.y_biases) + tuple(self._logit) + (self.l2_scale,)
 
     def _bias_l2(self):
         return self.bias_l2 if self.bias_l2 is not None else float(self.l2_reg)
@@ -955,6 +1047,14 @@ class HipALSSolver(HipMUSolver):
                     for axis in (0, 1):
                         if start[1 + axis] is not None:
                             ctx.set_bias(which, axis, start[1 + axis])
+            self.l2_multipliers = None
+            if self.l2_scale:   # (set_problem cleared them) the counts of the patterns this call was given: a fold-in counts its own rows
+                wx, wy = self._als_resolved
+                self.l2_multipliers = l2_multipliers(None if X is None else (m, d), None if Y is None else (d, p), wx, wy,
+                                                     self.x_background_weight, self.y_background_weight, self.l2_scale)
+                for which, upd in ((_lib.CMF_U, self.update_U), (_lib.CMF_V, self.update_V), (_lib.CMF_Z, self.update_Z)):
+                    if upd and self.l2_multipliers[which] is not None:
+                        ctx.set_l2_rows(which, self.l2_multipliers[which])
         return ctx
 
     def _device_step(self, l1_reg, l2_reg, alpha):
