@@ -27,18 +27,22 @@
 // Long rows (hot columns): a row with more than L stored entries ("als_cg_piece") leaves that kernel.  Its entries, side 0 then
 // side 1 in stored order, are cut into pieces of L consecutive entries (the last one shorter; a piece may straddle the two sides),
 // and one product H x becomes two plain launches, all long rows of the sweep together:
-//   als_cg_piece_kernel<KP>    one 256-thread workgroup per piece: the inner loop of `pass` over the piece's entries (wave e mod 4
+//   als_cg_piece_kernel<KP>    one 256-thread workgroup per piece: the entry pass over the piece's entries (wave e mod 4
 //                              takes entry e of the piece, four in flight, b_e in registers, the butterfly dot, acc += coef b_e),
 //                              the four wave accumulators added in wave order, the piece's partial [KP] to its own slot.  x comes
 //                              from the row's state (f in the first pass, p afterwards), each lane its KP / 64 floats straight into
 //                              registers.  Pieces always stream; 4 KP floats of static LDS.  A piece of a row that has stopped
-//                              returns at once.
+//                              returns at once.  The non-negative rows (cmf_als_nncg.hip.h) launch this kernel too.
 //   als_cg_combine_kernel<KP>  one workgroup per long row: thread j < KP adds the row's partials in piece order, then (S x)_j for c
 //                              ascending and l2 x_j as `pass` does; the first launch forms r = g - H f (+ N), p = r, r.r, the later
 //                              ones one CG step each with the formulas and the stop rule above; the last one writes f.
 // The sum across workgroups is the kernel boundary: no atomics, no grid barrier, no workgroup waits for another.  The state
 // (f, r, p [KP], r.r and an alive flag per long row) and the partials live in a scratch buffer of their own.  A long row's result
 // depends on that row and on L alone.
+//
+// Shared with cmf_als_nncg.hip.h and cmf_als_dual.hip.h: als_lane_load / als_lane_store (a lane's KP / 64 floats),
+// als_row_pass_accumulate (the entry pass of als_nncg_kernel and of the piece kernel; als_cg_kernel keeps its own copy of the loop,
+// whose code object is the one it had before the fold), als_wg_sum (r.r and p.q here), als_long_row_product (both combine kernels).
 #pragma once
 #include "cmf_kernels.hip.h"
 
@@ -91,6 +95,99 @@ __device__ __forceinline__ float als_cg_wave_sum(float v) {
     return v;
 }
 
+// Sum over the workgroup of va (TWO: and of vb, which goes to *sb), zero in threads >= KP; the same bits in every thread: a butterfly
+// inside each wave, the four wave sums through ws (4 floats, TWO: 8) and added in wave order.  One barrier.  The callers alternate
+// between two such buffers, so that one is rewritten only after a barrier has passed since its last read.
+template <bool TWO = false>
+__device__ __forceinline__ float als_wg_sum(float *ws, int uw, int lane, float va, [[maybe_unused]] float vb = 0.f, [[maybe_unused]] float *sb = nullptr) {
+    va = als_cg_wave_sum(va);
+    if constexpr (TWO) vb = als_cg_wave_sum(vb);
+    if (lane == 0) {
+        ws[uw] = va;
+        if constexpr (TWO) ws[4 + uw] = vb;
+    }
+    __syncthreads();
+    if constexpr (TWO) *sb = ((ws[4] + ws[5]) + ws[6]) + ws[7];
+    return ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
+// the VPL = 4 | 2 | 1 consecutive floats of one lane by one load or store, in global memory or LDS (p aligned to 4 VPL bytes)
+template <int VPL>
+__device__ __forceinline__ void als_lane_load(const float *p, float (&v)[VPL]) {
+    static_assert(VPL == 4 || VPL == 2 || VPL == 1, "k_pad <= 256");
+    if constexpr (VPL == 4) {
+        const f32x4 x4 = *reinterpret_cast<const f32x4 *>(p);
+        v[0] = x4[0]; v[1] = x4[1]; v[2] = x4[2]; v[3] = x4[3];
+    } else if constexpr (VPL == 2) {
+        const float2 x2 = *reinterpret_cast<const float2 *>(p);
+        v[0] = x2.x; v[1] = x2.y;
+    } else {
+        v[0] = p[0];
+    }
+}
+template <int VPL>
+__device__ __forceinline__ void als_lane_store(float *p, const float (&v)[VPL]) {
+    static_assert(VPL == 4 || VPL == 2 || VPL == 1, "k_pad <= 256");
+    if constexpr (VPL == 4) *reinterpret_cast<f32x4 *>(p) = f32x4{v[0], v[1], v[2], v[3]};
+    else if constexpr (VPL == 2) *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1]);
+    else p[0] = v[0];
+}
+
+// The entry pass of als_nncg_kernel (cmf_als_nncg.hip.h) and of als_cg_piece_kernel: acc += sum_e coef_e b_e over entries
+// [e_begin, e_begin + n) of the row (side 0 then side 1 concatenated), wave uw taking every fourth of them, ALS_CG_U in flight:
+// d_e = b_e . x by in-lane FMAs for v ascending and the butterfly, coef_e = w_e d_e, or FIRST: pv_e - w_e d_e.  resident: the
+// gathered rows and weights are kept in res / resw by FIRST and read from there afterwards (written and read by the same wave).
+// The loop of `pass` in als_cg_kernel below is the same loop, kept inline there.
+template <int KP, bool FIRST, int VPL>
+__device__ __forceinline__ void als_row_pass_accumulate(const AlsCgSide s0, const AlsCgSide s1, int64_t b0, int64_t b1, int n0, int e_begin, int n,
+                                                        bool resident, float *res, float *resw, const float (&xr)[VPL], float (&acc)[VPL],
+                                                        int uw, int lane, bool holds) {
+    for (int e0 = uw; e0 < n; e0 += 4 * ALS_CG_U) {
+        float b[ALS_CG_U][VPL], w[ALS_CG_U], pv[ALS_CG_U];
+#pragma unroll
+        for (int u = 0; u < ALS_CG_U; ++u) {
+            const int e = e0 + 4 * u;                    // wave-uniform
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) b[u][v] = 0.f;
+            w[u] = pv[u] = 0.f;
+            if (e >= n) continue;
+            if (FIRST || !resident) {
+                const int ge = e_begin + e;              // entry of the row
+                const bool second = ge >= n0;
+                const int64_t q = second ? b1 + (ge - n0) : b0 + ge;
+                w[u] = (second ? s1.wv : s0.wv)[q];
+                if (FIRST) pv[u] = (second ? s1.pv : s0.pv)[q];
+                if (holds) {
+                    als_lane_load<VPL>((second ? s1.B : s0.B) + (int64_t)(second ? s1.idx : s0.idx)[q] * KP + lane * VPL, b[u]);
+                }
+                if (FIRST && resident) {
+                    if (holds) {
+                        als_lane_store<VPL>(res + (int64_t)e * KP + lane * VPL, b[u]);
+                    }
+                    if (lane == 0) resw[e] = w[u];
+                }
+            } else {                                     // written by this same wave in the first pass
+                w[u] = resw[e];
+                if (holds) {
+                    als_lane_load<VPL>(res + (int64_t)e * KP + lane * VPL, b[u]);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < ALS_CG_U; ++u) {
+            float d = 0.f;
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) d = fmaf(b[u][v], xr[v], d);
+            d = als_cg_wave_sum(d);
+            const float coef = FIRST ? pv[u] - w[u] * d : w[u] * d;
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) acc[v] = fmaf(coef, b[u][v], acc[v]);
+        }
+    }
+}
+
+__device__ __forceinline__ bool als_cg_positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
+
 template <int KP, bool LR>
 __global__ __launch_bounds__(256) void als_cg_kernel(AlsCgArgs g) {
     constexpr int VPL = KP >= 64 ? KP / 64 : 1;     // floats of a gathered row per lane
@@ -136,39 +233,18 @@ __global__ __launch_bounds__(256) void als_cg_kernel(AlsCgArgs g) {
                     w[u] = (second ? g.s1.wv : g.s0.wv)[q];
                     if (first) pv[u] = (second ? g.s1.pv : g.s0.pv)[q];
                     if (holds) {
-                        const float *src = (second ? g.s1.B : g.s0.B) + (int64_t)(second ? g.s1.idx : g.s0.idx)[q] * KP + lane * VPL;
-                        if constexpr (VPL == 4) {
-                            const f32x4 x4 = *reinterpret_cast<const f32x4 *>(src);
-                            b[u][0] = x4[0]; b[u][1] = x4[1]; b[u][2] = x4[2]; b[u][3] = x4[3];
-                        } else if constexpr (VPL == 2) {
-                            const float2 x2 = *reinterpret_cast<const float2 *>(src);
-                            b[u][0] = x2.x; b[u][1] = x2.y;
-                        } else {
-                            b[u][0] = src[0];
-                        }
+                        als_lane_load<VPL>((second ? g.s1.B : g.s0.B) + (int64_t)(second ? g.s1.idx : g.s0.idx)[q] * KP + lane * VPL, b[u]);
                     }
                     if (first && resident) {
                         if (holds) {
-                            float *dst = res + (int64_t)e * KP + lane * VPL;
-                            if constexpr (VPL == 4) *reinterpret_cast<f32x4 *>(dst) = f32x4{b[u][0], b[u][1], b[u][2], b[u][3]};
-                            else if constexpr (VPL == 2) *reinterpret_cast<float2 *>(dst) = make_float2(b[u][0], b[u][1]);
-                            else dst[0] = b[u][0];
+                            als_lane_store<VPL>(res + (int64_t)e * KP + lane * VPL, b[u]);
                         }
                         if (lane == 0) resw[e] = w[u];
                     }
                 } else {                             // written by this same wave in the first pass
                     w[u] = resw[e];
                     if (holds) {
-                        const float *src = res + (int64_t)e * KP + lane * VPL;
-                        if constexpr (VPL == 4) {
-                            const f32x4 x4 = *reinterpret_cast<const f32x4 *>(src);
-                            b[u][0] = x4[0]; b[u][1] = x4[1]; b[u][2] = x4[2]; b[u][3] = x4[3];
-                        } else if constexpr (VPL == 2) {
-                            const float2 x2 = *reinterpret_cast<const float2 *>(src);
-                            b[u][0] = x2.x; b[u][1] = x2.y;
-                        } else {
-                            b[u][0] = src[0];
-                        }
+                        als_lane_load<VPL>(res + (int64_t)e * KP + lane * VPL, b[u]);
                     }
                 }
             }
@@ -203,10 +279,7 @@ __global__ __launch_bounds__(256) void als_cg_kernel(AlsCgArgs g) {
     // sum over the workgroup of v (zero in threads >= KP), the same bits in every thread; `slot` 0 | 1 alternates so that a
     // buffer is rewritten only after a barrier has passed since its last read
     auto dot = [&](float v, int slot) -> float {
-        v = als_cg_wave_sum(v);
-        if (lane == 0) wsum[4 * slot + uw] = v;
-        __syncthreads();
-        return ((wsum[4 * slot] + wsum[4 * slot + 1]) + wsum[4 * slot + 2]) + wsum[4 * slot + 3];
+        return als_wg_sum(wsum + 4 * slot, uw, lane, v);
     };
 
     float f = 0.f, r = 0.f, p = 0.f;
@@ -247,25 +320,23 @@ struct AlsCgLongRow {
     int64_t row;            // of the swept factor
     int32_t first, pieces;  // its partial slots [first, first + pieces)
 };
+// What als_cg_piece_kernel reads, of the signed rows and of the non-negative ones (cmf_als_nncg.hip.h) alike; the combine kernels
+// find the rows, their state and the partials here too.
 struct AlsCgPieceArgs {
     AlsCgSide s0, s1;       // s1.indptr == nullptr: one side
     const AlsCgPiece *pieces;
     const AlsCgLongRow *rows;
-    const float *S, *N, *Fin;
-    float *Fout;
-    int64_t out_row0;
-    float *state;           // [long row][3][KP]: f, r, p
-    float *rr;              // [long row]
-    int32_t *alive;         // [long row]
+    const float *Fin;       // the swept factor: x of the first pass
+    float *state;           // [long row][state_vecs][KP]: f, r, the next vector (x of the later passes), ...
     float *partial;         // [piece][KP]
-    float l2;
-    int k;
-    int phase;              // 0: the first pass / its combine; 1: a step; 2: the last step (f goes to Fout)
-    const float *l2m;       // as AlsCgArgs (the combine finds its row through AlsCgLongRow::row)
+    const int32_t *takes;   // a row takes a later launch's pass when takes[slot * takes_stride] == takes_value (words the combines write)
+    int state_vecs, takes_stride, takes_value;
+    int first;              // the first pass: x = the factor row (clamp: max(., 0) of it), coefficient pv_e - w_e (b_e . x), every row takes it
+    int clamp;
 };
 
-__device__ __forceinline__ bool als_cg_positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
-
+// One 256-thread workgroup per piece: the entry pass over the piece's entries, the four wave accumulators added in wave order, the
+// piece's partial [KP] to its own slot.  Pieces always stream; 4 KP floats of static LDS.
 template <int KP>
 __global__ __launch_bounds__(256) void als_cg_piece_kernel(AlsCgPieceArgs g) {
     constexpr int VPL = KP >= 64 ? KP / 64 : 1;
@@ -274,88 +345,72 @@ __global__ __launch_bounds__(256) void als_cg_piece_kernel(AlsCgPieceArgs g) {
     const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
     const bool holds = lane * VPL < KP;
     const AlsCgPiece pc = g.pieces[blockIdx.x];
-    const bool first = g.phase == 0;
-    if (!first && !g.alive[pc.slot]) return;            // workgroup-uniform
+    const bool first = g.first != 0;
+    if (!first && g.takes[(int64_t)pc.slot * g.takes_stride] != g.takes_value) return;   // workgroup-uniform
     const int64_t row = g.rows[pc.slot].row;
     const int64_t b0 = g.s0.indptr[row], b1 = g.s1.indptr ? g.s1.indptr[row] : 0;
     const int n0 = (int)(g.s0.indptr[row + 1] - b0);
-    const float *x = first ? g.Fin + row * KP : g.state + ((int64_t)pc.slot * 3 + 2) * KP;
+    const float *x = first ? g.Fin + row * KP : g.state + ((int64_t)pc.slot * g.state_vecs + 2) * KP;
     float xr[VPL], acc[VPL];
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
         xr[v] = holds ? x[lane * VPL + v] : 0.f;
+        if (first && g.clamp) xr[v] = fmaxf(xr[v], 0.f);
         acc[v] = 0.f;
     }
-    const int n = pc.count;
-    for (int e0 = uw; e0 < n; e0 += 4 * ALS_CG_U) {
-        float b[ALS_CG_U][VPL], w[ALS_CG_U], pv[ALS_CG_U];
-#pragma unroll
-        for (int u = 0; u < ALS_CG_U; ++u) {
-            const int e = e0 + 4 * u;                    // wave-uniform
-#pragma unroll
-            for (int v = 0; v < VPL; ++v) b[u][v] = 0.f;
-            w[u] = pv[u] = 0.f;
-            if (e >= n) continue;
-            const int ge = pc.first + e;                 // entry of the row
-            const bool second = ge >= n0;
-            const int64_t q = second ? b1 + (ge - n0) : b0 + ge;
-            w[u] = (second ? g.s1.wv : g.s0.wv)[q];
-            if (first) pv[u] = (second ? g.s1.pv : g.s0.pv)[q];
-            if (holds) {
-                const float *src = (second ? g.s1.B : g.s0.B) + (int64_t)(second ? g.s1.idx : g.s0.idx)[q] * KP + lane * VPL;
-                if constexpr (VPL == 4) {
-                    const f32x4 x4 = *reinterpret_cast<const f32x4 *>(src);
-                    b[u][0] = x4[0]; b[u][1] = x4[1]; b[u][2] = x4[2]; b[u][3] = x4[3];
-                } else if constexpr (VPL == 2) {
-                    const float2 x2 = *reinterpret_cast<const float2 *>(src);
-                    b[u][0] = x2.x; b[u][1] = x2.y;
-                } else {
-                    b[u][0] = src[0];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < ALS_CG_U; ++u) {
-            float d = 0.f;
-#pragma unroll
-            for (int v = 0; v < VPL; ++v) d = fmaf(b[u][v], xr[v], d);
-            d = als_cg_wave_sum(d);
-            const float coef = first ? pv[u] - w[u] * d : w[u] * d;
-#pragma unroll
-            for (int v = 0; v < VPL; ++v) acc[v] = fmaf(coef, b[u][v], acc[v]);
-        }
-    }
-    if (holds) {
-#pragma unroll
-        for (int v = 0; v < VPL; ++v) part[uw * KP + lane * VPL + v] = acc[v];
-    }
+    if (first) als_row_pass_accumulate<KP, true, VPL>(g.s0, g.s1, b0, b1, n0, pc.first, pc.count, false, nullptr, nullptr, xr, acc, uw, lane, holds);
+    else als_row_pass_accumulate<KP, false, VPL>(g.s0, g.s1, b0, b1, n0, pc.first, pc.count, false, nullptr, nullptr, xr, acc, uw, lane, holds);
+    if (holds) als_lane_store<VPL>(part + uw * KP + lane * VPL, acc);
     __syncthreads();
     if (t < KP) g.partial[(int64_t)blockIdx.x * KP + t] = ((part[t] + part[KP + t]) + part[2 * KP + t]) + part[3 * KP + t];
 }
 
+// thread t < KP of a combine kernel: the partials of its long row added in piece order, then -+ ((S x)_t + lambda_i x_t) with x in
+// xs (LDS): S x for c ascending, lambda_i x_t on the first k coordinates, as `pass` of the row kernels adds them
 template <int KP, bool LR>
-__global__ __launch_bounds__(256) void als_cg_combine_kernel(AlsCgPieceArgs g) {
+__device__ __forceinline__ float als_long_row_product(const AlsCgPieceArgs &p, const AlsCgLongRow lr, const float *S, const float *xs, int k,
+                                                      float l2, const float *l2m, bool first, int t) {
+    float o = 0.f;
+    const float *pp = p.partial + (int64_t)lr.first * KP + t;
+    for (int q = 0; q < lr.pieces; ++q) o += pp[(int64_t)q * KP];
+    float sx = 0.f;
+    if (S) {
+        for (int c = 0; c < k; ++c) sx = fmaf(S[c * KP + t], xs[c], sx);
+    }
+    if (t < k) sx += als_row_l2<LR>(l2, l2m, lr.row) * xs[t];   // (the row is wave-uniform)
+    return first ? o - sx : o + sx;
+}
+
+struct AlsCgLongArgs {
+    AlsCgPieceArgs p;       // state: [long row][3][KP]: f, r, p; takes: alive
+    const float *S, *N;
+    float *Fout;
+    int64_t out_row0;
+    float *rr;              // [long row]
+    int32_t *alive;         // [long row]; p.takes points at the same words (the piece kernel only reads them): move both together
+    float l2;
+    int k;
+    int phase;              // 0: the first pass / its combine; 1: a step; 2: the last step (f goes to Fout)
+    const float *l2m;       // as AlsCgArgs (the combine finds its row through AlsCgLongRow::row)
+};
+
+template <int KP, bool LR>
+__global__ __launch_bounds__(256) void als_cg_combine_kernel(AlsCgLongArgs g) {
     __shared__ float xs[KP], wsum[8];
     const int t = threadIdx.x, lane = t & 63;
     const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
     const int slot = blockIdx.x, k = g.k;
-    const AlsCgLongRow lr = g.rows[slot];
-    float *st = g.state + (int64_t)slot * 3 * KP;
+    const AlsCgLongRow lr = g.p.rows[slot];
+    float *st = g.p.state + (int64_t)slot * 3 * KP;
     float *out = g.Fout + (lr.row - g.out_row0) * KP;
     const bool first = g.phase == 0, last = g.phase == 2;
     if (!first && !g.alive[slot]) {                      // stopped earlier: the row keeps what it has
         if (last && t < k) out[t] = st[t];
         return;
     }
-    auto dot = [&](float v, int s) -> float {            // as in als_cg_kernel
-        v = als_cg_wave_sum(v);
-        if (lane == 0) wsum[4 * s + uw] = v;
-        __syncthreads();
-        return ((wsum[4 * s] + wsum[4 * s + 1]) + wsum[4 * s + 2]) + wsum[4 * s + 3];
-    };
     float f = 0.f, r = 0.f, p = 0.f, o = 0.f;
     if (t < KP) {
-        f = first ? g.Fin[lr.row * KP + t] : st[t];
+        f = first ? g.p.Fin[lr.row * KP + t] : st[t];
         if (!first) {
             r = st[KP + t];
             p = st[2 * KP + t];
@@ -363,20 +418,11 @@ __global__ __launch_bounds__(256) void als_cg_combine_kernel(AlsCgPieceArgs g) {
         xs[t] = first ? f : p;
     }
     __syncthreads();
-    if (t < KP) {
-        const float *pp = g.partial + (int64_t)lr.first * KP + t;
-        for (int q = 0; q < lr.pieces; ++q) o += pp[(int64_t)q * KP];
-        float sx = 0.f;
-        if (g.S) {
-            for (int c = 0; c < k; ++c) sx = fmaf(g.S[c * KP + t], xs[c], sx);
-        }
-        if (t < k) sx += als_row_l2<LR>(g.l2, g.l2m, lr.row) * xs[t];
-        o = first ? o - sx : o + sx;
-    }
+    if (t < KP) o = als_long_row_product<KP, LR>(g.p, lr, g.S, xs, k, g.l2, g.l2m, first, t);
     if (first) {
         r = o;
         if (t < KP && g.N) r += g.N[lr.row * KP + t];
-        const float rr = dot(r * r, 0);
+        const float rr = als_wg_sum(wsum, uw, lane, r * r);
         if (t < KP) {
             st[t] = f;
             st[KP + t] = r;
@@ -389,7 +435,7 @@ __global__ __launch_bounds__(256) void als_cg_combine_kernel(AlsCgPieceArgs g) {
         return;
     }
     const float rr = g.rr[slot];
-    const float pq = dot(p * o, 1);
+    const float pq = als_wg_sum(wsum + 4, uw, lane, p * o);
     if (!als_cg_positive_finite(pq)) {
         if (t == 0) g.alive[slot] = 0;
         if (last && t < k) out[t] = f;
@@ -398,7 +444,7 @@ __global__ __launch_bounds__(256) void als_cg_combine_kernel(AlsCgPieceArgs g) {
     const float alpha = rr / pq;
     f = fmaf(alpha, p, f);
     r = fmaf(-alpha, o, r);
-    const float rn = dot(r * r, 0);
+    const float rn = als_wg_sum(wsum, uw, lane, r * r);
     const float beta = rn / rr;
     p = fmaf(beta, p, r);
     if (last) {

@@ -202,16 +202,7 @@ __global__ __launch_bounds__(256) void als_dual_back_kernel(AlsDualArgs g, int n
             const bool second = e >= n0;
             const int64_t q = second ? b1 + (e - n0) : b0 + e;
             coef[u] = sqrtf((second ? g.s1.wv : g.s0.wv)[q]) * z[e];
-            const float *src = (second ? g.s1.B : g.s0.B) + (int64_t)(second ? g.s1.idx : g.s0.idx)[q] * KP + lane * VPL;
-            if constexpr (VPL == 4) {
-                const f32x4 x4 = *reinterpret_cast<const f32x4 *>(src);
-                b[u][0] = x4[0]; b[u][1] = x4[1]; b[u][2] = x4[2]; b[u][3] = x4[3];
-            } else if constexpr (VPL == 2) {
-                const float2 x2 = *reinterpret_cast<const float2 *>(src);
-                b[u][0] = x2.x; b[u][1] = x2.y;
-            } else {
-                b[u][0] = src[0];
-            }
+            als_lane_load<VPL>((second ? g.s1.B : g.s0.B) + (int64_t)(second ? g.s1.idx : g.s0.idx)[q] * KP + lane * VPL, b[u]);
         }
 #pragma unroll
         for (int u = 0; u < ALS_CG_U; ++u)

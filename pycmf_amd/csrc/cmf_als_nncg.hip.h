@@ -16,17 +16,17 @@
 // 2 steps + 1 times.
 //
 // als_nncg_kernel<KP>: als_cg_kernel's shape -- one 256-thread workgroup per row, all steps in the one launch, the same pass (wave
-// e mod 4 takes entry e, b_e in registers, butterfly dot, four wave accumulators added in wave order, then S x and l2 x), the same
-// LDS residency classes (a class changes no bit), no atomics, vector stores only, no scratch.  The vector algebra runs in thread
-// j < KP; the decisions every thread must take alike (any t_j < 0, free == free_old, the stop tests) come from values every thread
-// reads the same bits of: sums combined through LDS in wave order, and __syncthreads_or of the flags.  The pass is a COPY of
-// als_cg_kernel's (als_nncg_accumulate, shared by the row kernel and the piece kernel of this file): with the one template in
-// als_cg_kernel too its VGPRs move from 39 / 39 / 41 / 55 to 40 / 40 / 43 / 55, so the CG kernels are untouched.
+// e mod 4 takes entry e, b_e in registers, butterfly dot: als_row_pass_accumulate of cmf_als_cg.hip.h; four wave accumulators added
+// in wave order, then S x and l2 x), the same LDS residency classes (a class changes no bit), no atomics, vector stores only, no
+// scratch.  The vector algebra runs in thread j < KP; the decisions every thread must take alike (any t_j < 0, free == free_old, the
+// stop tests) come from values every thread reads the same bits of: sums combined through LDS in wave order, and __syncthreads_or
+// of the flags.  The kernel's code object is the one it had before the pass was shared.
 //
 // Long rows (more than "als_cg_piece" entries) take the form of cmf_als_cg.hip.h's long rows, a state machine over launches:
-//   als_nncg_piece_kernel<KP>    one workgroup per piece: the partial sum of H x over the piece's entries to its own slot; x is
-//                                max(f, 0) of the factor (stage 0), p (stage 1) or d (stage 2) from the row's state.  A piece of a
-//                                row that does not take this stage's pass (stopped, or a free step in stage 2) returns at once.
+//   als_cg_piece_kernel<KP>      that file's: one workgroup per piece, the partial sum of H x over the piece's entries to its own
+//                                slot; x is max(f, 0) of the factor (stage 0, `clamp`), p (stage 1) or d (stage 2) from the row's
+//                                state.  A piece of a row whose record's mode does not ask for this stage's pass (stopped, or a
+//                                free step in stage 2) returns at once.
 //   als_nncg_combine_kernel<KP>  one workgroup per long row: the partials added in piece order, S x and l2 x, then the algebra of
 //                                the stage: 0 forms r and prepares the first step (free set, rho, p); 1 (A) takes the step if it
 //                                is free and prepares the next, or leaves d as the next vector; 2 (B) finishes a projected step
@@ -51,15 +51,11 @@ struct AlsNncgRow {         // a long row between launches
     int32_t passes, pad;
 };
 struct AlsNncgLongArgs {
-    AlsCgSide s0, s1;
-    const AlsCgPiece *pieces;
-    const AlsCgLongRow *rows;
-    const float *S, *N, *Fin;
+    AlsCgPieceArgs p;       // state: [long row][5][KP]: f, r, the next vector (p | d), f+, free_old (0 | 1); takes: the mode of info
+    const float *S, *N;
     float *Fout;
     int64_t out_row0;
-    float *state;           // [long row][5][KP]: f, r, the next vector (p | d), f+, free_old (0 | 1)
-    AlsNncgRow *info;       // [long row]
-    float *partial;         // [piece][KP]
+    AlsNncgRow *info;       // [long row]; p.takes points at the mode of the first record (the piece kernel only reads it): move both together
     int32_t *passes;        // as AlsNncgArgs
     float l2;
     int k;
@@ -67,78 +63,6 @@ struct AlsNncgLongArgs {
     int last;               // stage 2 of the last step: f and the passes go out
     const float *l2m;       // as AlsCgArgs
 };
-
-// acc += sum_e coef_e b_e over entries [e_begin, e_begin + n) of the row (side 0 then side 1 concatenated), wave uw taking every
-// fourth of them, four in flight: coef_e = w_e (b_e . x), or FIRST: pv_e - w_e (b_e . x).  resident: the gathered rows and weights
-// are kept in res / resw by FIRST and read from there afterwards (written and read by the same wave).  als_cg_kernel's loop.
-template <int KP, bool FIRST, int VPL>
-__device__ __forceinline__ void als_nncg_accumulate(const AlsCgSide s0, const AlsCgSide s1, int64_t b0, int64_t b1, int n0, int e_begin, int n,
-                                                    bool resident, float *res, float *resw, const float (&xr)[VPL], float (&acc)[VPL],
-                                                    int uw, int lane, bool holds) {
-    for (int e0 = uw; e0 < n; e0 += 4 * ALS_CG_U) {
-        float b[ALS_CG_U][VPL], w[ALS_CG_U], pv[ALS_CG_U];
-#pragma unroll
-        for (int u = 0; u < ALS_CG_U; ++u) {
-            const int e = e0 + 4 * u;                    // wave-uniform
-#pragma unroll
-            for (int v = 0; v < VPL; ++v) b[u][v] = 0.f;
-            w[u] = pv[u] = 0.f;
-            if (e >= n) continue;
-            if (FIRST || !resident) {
-                const int ge = e_begin + e;              // entry of the row
-                const bool second = ge >= n0;
-                const int64_t q = second ? b1 + (ge - n0) : b0 + ge;
-                w[u] = (second ? s1.wv : s0.wv)[q];
-                if (FIRST) pv[u] = (second ? s1.pv : s0.pv)[q];
-                if (holds) {
-                    const float *src = (second ? s1.B : s0.B) + (int64_t)(second ? s1.idx : s0.idx)[q] * KP + lane * VPL;
-                    if constexpr (VPL == 4) {
-                        const f32x4 x4 = *reinterpret_cast<const f32x4 *>(src);
-                        b[u][0] = x4[0]; b[u][1] = x4[1]; b[u][2] = x4[2]; b[u][3] = x4[3];
-                    } else if constexpr (VPL == 2) {
-                        const float2 x2 = *reinterpret_cast<const float2 *>(src);
-                        b[u][0] = x2.x; b[u][1] = x2.y;
-                    } else {
-                        b[u][0] = src[0];
-                    }
-                }
-                if (FIRST && resident) {
-                    if (holds) {
-                        float *dst = res + (int64_t)e * KP + lane * VPL;
-                        if constexpr (VPL == 4) *reinterpret_cast<f32x4 *>(dst) = f32x4{b[u][0], b[u][1], b[u][2], b[u][3]};
-                        else if constexpr (VPL == 2) *reinterpret_cast<float2 *>(dst) = make_float2(b[u][0], b[u][1]);
-                        else dst[0] = b[u][0];
-                    }
-                    if (lane == 0) resw[e] = w[u];
-                }
-            } else {                                     // written by this same wave in the first pass
-                w[u] = resw[e];
-                if (holds) {
-                    const float *src = res + (int64_t)e * KP + lane * VPL;
-                    if constexpr (VPL == 4) {
-                        const f32x4 x4 = *reinterpret_cast<const f32x4 *>(src);
-                        b[u][0] = x4[0]; b[u][1] = x4[1]; b[u][2] = x4[2]; b[u][3] = x4[3];
-                    } else if constexpr (VPL == 2) {
-                        const float2 x2 = *reinterpret_cast<const float2 *>(src);
-                        b[u][0] = x2.x; b[u][1] = x2.y;
-                    } else {
-                        b[u][0] = src[0];
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < ALS_CG_U; ++u) {
-            float d = 0.f;
-#pragma unroll
-            for (int v = 0; v < VPL; ++v) d = fmaf(b[u][v], xr[v], d);
-            d = als_cg_wave_sum(d);
-            const float coef = FIRST ? pv[u] - w[u] * d : w[u] * d;
-#pragma unroll
-            for (int v = 0; v < VPL; ++v) acc[v] = fmaf(coef, b[u][v], acc[v]);
-        }
-    }
-}
 
 template <int KP, bool LR>
 __global__ __launch_bounds__(256) void als_nncg_kernel(AlsNncgArgs ga) {
@@ -172,7 +96,7 @@ __global__ __launch_bounds__(256) void als_nncg_kernel(AlsNncgArgs ga) {
             xr[v] = holds ? xs[lane * VPL + v] : 0.f;
             acc[v] = 0.f;
         }
-        als_nncg_accumulate<KP, first, VPL>(g.s0, g.s1, b0, b1, n0, 0, n, resident, res, resw, xr, acc, uw, lane, holds);
+        als_row_pass_accumulate<KP, first, VPL>(g.s0, g.s1, b0, b1, n0, 0, n, resident, res, resw, xr, acc, uw, lane, holds);
         if (holds) {
 #pragma unroll
             for (int v = 0; v < VPL; ++v) part[uw * KP + lane * VPL + v] = acc[v];
@@ -263,46 +187,15 @@ __global__ __launch_bounds__(256) void als_nncg_kernel(AlsNncgArgs ga) {
     if (t == 0) ga.passes[row - g.out_row0] = passes;
 }
 
-// ------------------------------------------------------------------ long rows, cut into pieces
-template <int KP>
-__global__ __launch_bounds__(256) void als_nncg_piece_kernel(AlsNncgLongArgs g) {
-    constexpr int VPL = KP >= 64 ? KP / 64 : 1;
-    __shared__ __attribute__((aligned(16))) float part[4 * KP];
-    const int t = threadIdx.x, lane = t & 63;
-    const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
-    const bool holds = lane * VPL < KP;
-    const AlsCgPiece pc = g.pieces[blockIdx.x];
-    const bool first = g.stage == 0;
-    if (!first && g.info[pc.slot].mode != (g.stage == 1 ? ALS_NNCG_ROW_STEP : ALS_NNCG_ROW_PROJECT)) return;   // workgroup-uniform
-    const int64_t row = g.rows[pc.slot].row;
-    const int64_t b0 = g.s0.indptr[row], b1 = g.s1.indptr ? g.s1.indptr[row] : 0;
-    const int n0 = (int)(g.s0.indptr[row + 1] - b0);
-    const float *x = first ? g.Fin + row * KP : g.state + ((int64_t)pc.slot * 5 + 2) * KP;
-    float xr[VPL], acc[VPL];
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-        xr[v] = holds ? x[lane * VPL + v] : 0.f;
-        if (first) xr[v] = fmaxf(xr[v], 0.f);
-        acc[v] = 0.f;
-    }
-    if (first) als_nncg_accumulate<KP, true, VPL>(g.s0, g.s1, b0, b1, n0, pc.first, pc.count, false, nullptr, nullptr, xr, acc, uw, lane, holds);
-    else als_nncg_accumulate<KP, false, VPL>(g.s0, g.s1, b0, b1, n0, pc.first, pc.count, false, nullptr, nullptr, xr, acc, uw, lane, holds);
-    if (holds) {
-#pragma unroll
-        for (int v = 0; v < VPL; ++v) part[uw * KP + lane * VPL + v] = acc[v];
-    }
-    __syncthreads();
-    if (t < KP) g.partial[(int64_t)blockIdx.x * KP + t] = ((part[t] + part[KP + t]) + part[2 * KP + t]) + part[3 * KP + t];
-}
-
+// ------------------------------------------------------------------ long rows, cut into pieces (the piece kernel: als_cg_piece_kernel)
 template <int KP, bool LR>
 __global__ __launch_bounds__(256) void als_nncg_combine_kernel(AlsNncgLongArgs g) {
     __shared__ float xs[KP], wsum[16];
     const int t = threadIdx.x, lane = t & 63;
     const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
     const int slot = blockIdx.x, k = g.k, stage = g.stage;
-    const AlsCgLongRow lr = g.rows[slot];
-    float *st = g.state + (int64_t)slot * 5 * KP;
+    const AlsCgLongRow lr = g.p.rows[slot];
+    float *st = g.p.state + (int64_t)slot * 5 * KP;
     AlsNncgRow *info = g.info + slot;
     float *out = g.Fout + (lr.row - g.out_row0) * KP;
     AlsNncgRow in = AlsNncgRow{0.f, 0.f, 0, ALS_NNCG_ROW_STEP, 0, 0};
@@ -318,25 +211,11 @@ __global__ __launch_bounds__(256) void als_nncg_combine_kernel(AlsNncgLongArgs g
         if (g.last) finish(t < KP ? st[t] : 0.f, in.passes);
         return;
     }
-    int par = 0;
-    auto dot2 = [&](float va, float vb, float &sb) -> float {    // as in als_nncg_kernel
-        va = als_cg_wave_sum(va);
-        vb = als_cg_wave_sum(vb);
-        float *ws = wsum + 8 * par;
-        par ^= 1;
-        if (lane == 0) {
-            ws[uw] = va;
-            ws[4 + uw] = vb;
-        }
-        __syncthreads();
-        sb = ((ws[4] + ws[5]) + ws[6]) + ws[7];
-        return ((ws[0] + ws[1]) + ws[2]) + ws[3];
-    };
-    float f = 0.f, r = 0.f, x = 0.f, fp = 0.f, o = 0.f, unused;
+    float f = 0.f, r = 0.f, x = 0.f, fp = 0.f, o = 0.f;
     bool free_old = false;
     if (t < KP) {
         if (stage == 0) {
-            f = fmaxf(g.Fin[lr.row * KP + t], 0.f);
+            f = fmaxf(g.p.Fin[lr.row * KP + t], 0.f);
             x = f;
         } else {
             f = st[t];
@@ -348,16 +227,7 @@ __global__ __launch_bounds__(256) void als_nncg_combine_kernel(AlsNncgLongArgs g
         xs[t] = x;
     }
     __syncthreads();
-    if (t < KP) {
-        const float *pp = g.partial + (int64_t)lr.first * KP + t;
-        for (int q = 0; q < lr.pieces; ++q) o += pp[(int64_t)q * KP];
-        float sx = 0.f;
-        if (g.S) {
-            for (int c = 0; c < k; ++c) sx = fmaf(g.S[c * KP + t], xs[c], sx);
-        }
-        if (t < k) sx += als_row_l2<LR>(g.l2, g.l2m, lr.row) * xs[t];
-        o = stage == 0 ? o - sx : o + sx;
-    }
+    if (t < KP) o = als_long_row_product<KP, LR>(g.p, lr, g.S, xs, k, g.l2, g.l2m, stage == 0, t);
     const int passes = in.passes + 1;
     float rho_old = in.rho_old;
     bool conj_ok = in.conj_ok != 0;
@@ -373,7 +243,7 @@ __global__ __launch_bounds__(256) void als_nncg_combine_kernel(AlsNncgLongArgs g
     auto prepare = [&](int mode_alive) {
         const bool fr = t < KP && (f > 0.f || r > 0.f);
         const float z = fr ? r : 0.f;
-        const float rho = dot2(z * z, 0.f, unused);
+        const float rho = als_wg_sum(wsum + 8, uw, lane, z * z);   // (the second half of wsum: a launch's step sum went through the first)
         const bool alive = als_cg_positive_finite(rho);
         const bool conj = !__syncthreads_or(fr != free_old) && conj_ok;
         const float p = conj ? fmaf(rho / rho_old, x, z) : z;
@@ -394,7 +264,7 @@ __global__ __launch_bounds__(256) void als_nncg_combine_kernel(AlsNncgLongArgs g
     }
     if (stage == 1) {                                    // combine A: x = p, o = q
         float pr;
-        const float pq = dot2(x * o, x * r, pr);
+        const float pq = als_wg_sum<true>(wsum, uw, lane, x * o, x * r, &pr);
         if (!als_cg_positive_finite(pq)) return stop();
         const float alpha = pr / pq;
         const float tt = fmaf(alpha, x, f);
@@ -419,7 +289,7 @@ __global__ __launch_bounds__(256) void als_nncg_combine_kernel(AlsNncgLongArgs g
         return;
     }
     float dhd;                                           // combine B: x = d, o = hd
-    const float dr = dot2(x * r, x * o, dhd);
+    const float dr = als_wg_sum<true>(wsum, uw, lane, x * r, x * o, &dhd);
     if (!als_cg_positive_finite(dr) || !als_cg_positive_finite(dhd)) return stop();
     const float theta = dr / dhd;
     if (theta >= 1.f) {

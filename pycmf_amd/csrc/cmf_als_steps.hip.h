@@ -297,13 +297,41 @@ static int64_t als_cg_piece_len(const cmf_ctx *c) {
     return c->opt_als_cg_piece > 0 ? rup(c->opt_als_cg_piece, 16) : (int64_t)ALS_CG_PIECE_DEFAULT;
 }
 
+// What als_cg_piece_kernel reads of the long rows of a sweep, signed or non-negative, and their scratch (als_cg_long):
+// state [vecs][k_pad] per row | partials [k_pad] per piece | row_bytes per row of the route's own words, which start at *own.
+static int als_cg_piece_args(cmf_ctx *c, const cmfk::AlsCgArgs &a, const cmfk::AlsCgLongRow *dlongs, const cmfk::AlsCgPiece *dpieces, size_t nl,
+                             size_t npieces, int vecs, size_t row_bytes, cmfk::AlsCgPieceArgs &p, float **own) {
+    const size_t sfloats = ((size_t)vecs * nl + npieces) * (size_t)c->kp;
+    CHK(ensure_scratch(c, c->als_cg_long, sfloats * sizeof(float) + nl * row_bytes));
+    memset(&p, 0, sizeof p);
+    p.s0 = a.s0; p.s1 = a.s1;
+    p.pieces = dpieces; p.rows = dlongs;
+    p.Fin = a.Fin;
+    p.state = (float *)c->als_cg_long.p;
+    p.state_vecs = vecs;
+    p.partial = p.state + (size_t)vecs * nl * (size_t)c->kp;
+    *own = p.state + sfloats;
+    return CMF_OK;
+}
+
+// one pass over the pieces: the first one (every row, x = the factor row, clamped for the non-negative rows), or a later one of the
+// rows whose word in p.takes holds `takes_value`
+static int als_cg_piece_pass(cmf_ctx *c, cmfk::AlsCgPieceArgs &p, int64_t npieces, bool first, bool clamp, int takes_value) {
+    p.first = first ? 1 : 0;
+    p.clamp = clamp ? 1 : 0;
+    p.takes_value = takes_value;
+    ALS_LAUNCH_KP(c, als_cg_piece_kernel, "the conjugate-gradient row solve is",
+                  hipLaunchKernelGGL(kern, dim3((unsigned)npieces), dim3(256), 0, c->stream, p));
+    return CMF_OK;
+}
+
 // the long rows of a sweep: 2 (steps + 1) launches, pieces then combine, once for r = g - H f and once per step
-static int als_cg_long_rows(cmf_ctx *c, cmfk::AlsCgPieceArgs &a, int64_t nlong, int64_t npieces, int steps) {
+static int als_cg_long_rows(cmf_ctx *c, cmfk::AlsCgLongArgs &a, int64_t nlong, int64_t npieces, int steps) {
     if (nlong <= 0) return CMF_OK;
-    const dim3 pgrid((unsigned)npieces), cgrid((unsigned)nlong), block(256);
+    const dim3 cgrid((unsigned)nlong), block(256);
     for (int s = 0; s <= steps; ++s) {
         a.phase = s == 0 ? 0 : (s == steps ? 2 : 1);
-        ALS_LAUNCH_KP(c, als_cg_piece_kernel, "the conjugate-gradient row solve is", hipLaunchKernelGGL(kern, pgrid, block, 0, c->stream, a));
+        CHK(als_cg_piece_pass(c, a.p, npieces, s == 0, false, 1));   // (later passes: the rows still alive)
         if (a.l2m) {
             ALS_LAUNCH_KP(c, als_cg_combine_kernel, "the conjugate-gradient row solve is", hipLaunchKernelGGL(kern, cgrid, block, 0, c->stream, a), true);
         } else {
@@ -349,15 +377,13 @@ static int als_nncg_launches(cmf_ctx *c, const cmfk::AlsCgArgs &a, const std::ve
     na.passes = (int32_t *)c->als_nncg_passes.p;
     AlsNncgLongArgs pa;
     memset(&pa, 0, sizeof pa);
-    if (nl) {   // scratch of the long rows: state [5][k_pad] per row | partials [k_pad] per piece | a record per row
-        const size_t sfloats = (5 * nl + (size_t)npieces) * (size_t)kp;
-        CHK(ensure_scratch(c, c->als_cg_long, sfloats * sizeof(float) + nl * sizeof(AlsNncgRow)));
-        pa.s0 = a.s0; pa.s1 = a.s1;
-        pa.pieces = dpieces; pa.rows = dlongs;
-        pa.S = a.S; pa.N = a.N; pa.Fin = a.Fin; pa.Fout = a.Fout; pa.out_row0 = a.out_row0;
-        pa.state = (float *)c->als_cg_long.p;
-        pa.partial = pa.state + 5 * nl * (size_t)kp;
-        pa.info = (AlsNncgRow *)(pa.state + sfloats);
+    if (nl) {   // the state of a long row is 5 vectors, its own words a record; a later pass takes the rows whose record's mode asks for it
+        float *own;
+        CHK(als_cg_piece_args(c, a, dlongs, dpieces, nl, (size_t)npieces, 5, sizeof(AlsNncgRow), pa.p, &own));
+        pa.info = (AlsNncgRow *)own;
+        pa.p.takes = &pa.info->mode;
+        pa.p.takes_stride = (int)(sizeof(AlsNncgRow) / sizeof(int32_t));
+        pa.S = a.S; pa.N = a.N; pa.Fout = a.Fout; pa.out_row0 = a.out_row0;
         pa.passes = na.passes;
         pa.l2 = a.l2; pa.l2m = a.l2m; pa.k = a.k;
     }
@@ -385,11 +411,11 @@ static int als_nncg_launches(cmf_ctx *c, const cmfk::AlsCgArgs &a, const std::ve
             }
         }
         if (nl) {
-            const dim3 pgrid((unsigned)npieces), cgrid((unsigned)nl), block(256);
+            const dim3 cgrid((unsigned)nl), block(256);
             for (int s = 0; s <= 2 * steps; ++s) {
                 pa.stage = s == 0 ? 0 : 2 - (s & 1);
                 pa.last = s == 2 * steps ? 1 : 0;
-                ALS_LAUNCH_KP(c, als_nncg_piece_kernel, "the non-negative conjugate-gradient row solve is", hipLaunchKernelGGL(kern, pgrid, block, 0, c->stream, pa));
+                CHK(als_cg_piece_pass(c, pa.p, npieces, s == 0, true, pa.stage == 1 ? ALS_NNCG_ROW_STEP : ALS_NNCG_ROW_PROJECT));
                 if (a.l2m) {
                     ALS_LAUNCH_KP(c, als_nncg_combine_kernel, "the non-negative conjugate-gradient row solve is", hipLaunchKernelGGL(kern, cgrid, block, 0, c->stream, pa), true);
                 } else {
@@ -475,18 +501,15 @@ static int als_cg_rows(cmf_ctx *c, const char *what, const AlsSweep &sw, double 
     a.k = c->k;
     a.steps = steps;
     if (nn) return als_nncg_launches(c, a, lens, list, caps, drows, dlongs, dpieces, longs, (int64_t)pieces.size(), nrows);
-    AlsCgPieceArgs pa;
+    AlsCgLongArgs pa;
     memset(&pa, 0, sizeof pa);
-    if (!longs.empty()) {   // scratch of the long rows: state [3][k_pad] per row | partials [k_pad] per piece | r.r | alive flags
-        const size_t nl = longs.size(), sfloats = (3 * nl + pieces.size()) * (size_t)kp;
-        CHK(ensure_scratch(c, c->als_cg_long, (sfloats + 2 * nl) * sizeof(float)));
-        pa.s0 = a.s0; pa.s1 = a.s1;
-        pa.pieces = dpieces; pa.rows = dlongs;
-        pa.S = a.S; pa.N = a.N; pa.Fin = a.Fin; pa.Fout = Fout; pa.out_row0 = out_row0;
-        pa.state = (float *)c->als_cg_long.p;
-        pa.partial = pa.state + 3 * nl * (size_t)kp;
-        pa.rr = pa.state + sfloats;
+    if (!longs.empty()) {   // the state of a long row is 3 vectors, its own words r.r (all rows) | alive flags (all rows)
+        const size_t nl = longs.size();
+        CHK(als_cg_piece_args(c, a, dlongs, dpieces, nl, pieces.size(), 3, 2 * sizeof(float), pa.p, &pa.rr));
         pa.alive = (int32_t *)(pa.rr + nl);
+        pa.p.takes = pa.alive;
+        pa.p.takes_stride = 1;
+        pa.S = a.S; pa.N = a.N; pa.Fout = Fout; pa.out_row0 = out_row0;
         pa.l2 = a.l2; pa.l2m = a.l2m; pa.k = a.k;
     }
     Timed tm(c, CMF_K_ROWHESS, (4.0 * (double)nnz * c->k + (a.S ? 2.0 * (double)nrows * c->k * c->k : 0.0)) * (steps + 1));

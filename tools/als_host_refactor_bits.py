@@ -1,8 +1,8 @@
 """Bits of every ALS entry point on a fixed list of small cases: one SHA-256 per case over the float32 bytes of U, V and Z (and of
 the bias vectors where biases are bound) after TWO steps from the same start, so that the second step reads the first's output, with
-the counters of cmf_als_cg_last / cmf_als_nncg_last / cmf_als_nncg_passes / cmf_als_dual_last behind it.  Written for the refactor
-of the ALS host code (one options record, one route table, one chunk loop): run on the commit before it and on the commit with it,
-on the same GPU, the two records must be equal entry for entry.
+the counters of cmf_als_cg_last / cmf_als_nncg_last / cmf_als_nncg_passes / cmf_als_dual_last behind it.  For any change that must
+leave the results of the ALS routes as they are (a refactor of the host code or of the kernels): run on the commit before it and on
+the commit with it, on the same GPU, the two records must be equal entry for entry.
 
     python tools/als_host_refactor_bits.py --label parent|branch [--out profiles/als_host_refactor_bits.json]
 
@@ -10,9 +10,12 @@ The record goes under its label into the file --out names, beside the other labe
 tool compares them and fails on the first difference.
 
 The problem is tests/als_dual_cases.py::problem(k): 48 x 160 x 40, both relations observed, row lengths on both sides of 32 / 64 /
-128, empty rows and rows of one entry; k = 3, 40, 200 (k_pad 32, 64, 256); once with als_piece = 32 and als_cg_piece = 16 (rows of
-several pieces, long CG rows) and once with the defaults.  A background weight (0.25 on X) needs every stored weight at or above
-it: those cases bind max(w, 0.25) in place of the weights with stored zeros.  The logistic cases bind the labels Y > 0.
+128, empty rows and rows of one entry; k = 3, 40, 100, 200 (k_pad 32, 64, 128, 256); once with als_piece = 32 and als_cg_piece = 16
+(rows of several pieces, long CG rows) and once with the defaults.  A background weight (0.25 on X) needs every stored weight at or
+above it: those cases bind max(w, 0.25) in place of the weights with stored zeros; they run the matrix-free steps too (the shared
+term S x of every product, on rows with pieces).  The logistic cases bind the labels Y > 0.  The matrix-free row hooks run a second
+time with "als_cg_lds" = 0 (every row streams) and a third time, with one step of each route, under per-row l2 multipliers
+(cmf_set_l2_rows) on all three factors.
 Fails without a GPU."""
 import argparse
 import hashlib
@@ -30,7 +33,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import als_dual_cases as C  # noqa: E402
 
 L2 = C.L2
-KS = (3, 40, 200)
+KS = (3, 40, 100, 200)
 BG = 0.25
 ROWS = (3, 20)              # the row hooks: rows 3 .. 23
 
@@ -106,6 +109,8 @@ def _steps(kind):
                 ("als_bias_step no biases cg 3", lambda c: c.als_bias_step(L2, 5, 7, 3, 2))]
     if kind == "bias":
         out += [("als_bias_step cg 0", lambda c: c.als_bias_step(L2, 0, 7, 0, 0)), ("als_bias_step cg 3", lambda c: c.als_bias_step(L2, 0, 7, 3, 0))]
+    if kind == "bg":
+        out += [("als_cg_step 3 0 nn 0", lambda c: c.als_cg_step(L2, 0, 7, 3, 0)), ("als_nncg_step 0 3 0 nn 7", lambda c: c.als_nncg_step(L2, 7, 7, 0, 3, 0))]
     if kind in ("", "bias", "bg"):
         for name, (dm, ns, ncg) in DUAL:
             if kind == "bias" and ncg:
@@ -124,6 +129,29 @@ def _sha(*arrays):
     for a in arrays:
         h.update(np.ascontiguousarray(a, dtype=np.float32).tobytes())
     return h.hexdigest()
+
+
+def _matrix_free(ctx, F, tag, rec):
+    """The CG and NNCG row hooks with every row streamed, then the hooks and one step of each route under per-row l2 multipliers."""
+    def hooks(label):
+        for w in range(3):
+            for name, hook in (("als_cg_rows", ctx.als_cg_rows), ("als_nncg_rows", ctx.als_nncg_rows)):
+                got = hook(w, ROWS[0], ROWS[1], L2, 3)
+                rec["%s | %s | %s %s" % (tag, label, name, "UVZ"[w])] = dict(_counters(ctx), sha256=_sha(got))
+    ctx.set_option("als_cg_lds", 0)
+    hooks("als_cg_lds 0")
+    ctx.set_option("als_cg_lds", -1)
+    for w, n in enumerate((C.M, C.D, C.P)):
+        ctx.set_l2_rows(w, 0.5 + 0.375 * (np.arange(n) % 7))
+    hooks("l2 rows")
+    for name, call in (("als_cg_step 3 0 nn 0", lambda c: c.als_cg_step(L2, 0, 7, 3, 0)),
+                       ("als_nncg_step 0 3 0 nn 7", lambda c: c.als_nncg_step(L2, 7, 7, 0, 3, 0))):
+        _reset(ctx, F, "")
+        call(ctx)
+        call(ctx)
+        rec["%s | l2 rows | %s" % (tag, name)] = _state(ctx, "")
+    for w in range(3):
+        ctx.set_l2_rows(w, None)
 
 
 def record(lib):
@@ -149,6 +177,7 @@ def record(lib):
                             got = hook()
                             rec["%s | observed | %s %s" % (tag, name, "UVZ"[w])] = dict(
                                 _counters(ctx), sha256=_sha(*got) if isinstance(got, tuple) else _sha(got))
+                    _matrix_free(ctx, F, tag, rec)
                 ctx.close()
             print("%s: done" % tag, flush=True)
     return rec
