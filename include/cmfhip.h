@@ -608,6 +608,40 @@ int cmf_set_relation_loss(cmf_ctx *ctx, int which, int kind);
 int cmf_get_relation_loss(cmf_ctx *ctx, int which, int *kind);
 int cmf_als_logistic_loss(cmf_ctx *ctx, double *lx, double *ly);
 
+/* ---- ALS with a Huber loss on an observed relation (csrc/cmf_als_huber.hip.h) ----
+ * A relation with CSR weights may be fitted under  sum_O w rho_d(t - a . b),  rho_d(r) = r^2 / 2 for |r| <= d and d (|r| - d / 2)
+ * beyond: a stored entry far off the model pulls its row and its column with a bounded force.  The half-quadratic majoriser
+ * rho_d(r) <= rho_d(r0) + omega(r0) (r^2 - r0^2) / 2, omega(r) = min(1, d / |r|), tight at the residual r0 under the CURRENT row,
+ * turns a row's problem into the ALS row problem under the weights w omega on the same targets.  ONE pass (als_huber_pass_kernel)
+ * in front of every sweep writes w omega and w t omega per stored entry of the image the sweep reads, and the sweep's route --
+ * exact, coordinate descent, conjugate gradients signed or projected, dual, and the bias blocks -- reads them where it reads w and
+ * w t, for that sweep only; no row kernel changes.  Every route starts at the current row and never raises its quadratic, so every
+ * sweep lowers the objective (a non-negative factor that is only projected carries no guarantee, as without this block).  An entry
+ * with |r| <= d keeps the bits of w and w t: while no residual exceeds d every entry point gives the bits it gives without a delta.
+ *   cmf_set_huber_delta(ctx, which, delta): `which` 0 = X | 1 = Y; delta > 0 (finite, in float32 too) puts the relation under the
+ *   Huber loss, 0 takes it back.  CMF_EINVAL otherwise.  Cleared by cmf_set_problem; kept when the weights are bound again.
+ *   cmf_get_huber_delta reads it back (the float32 value; CMF_EINVAL for a null output).
+ * HONOURED BY every ALS step (cmf_als_step, _nnls_, _cg_, _nncg_, _bias_, _dual_step), the row entries cmf_als_cg_rows,
+ * cmf_als_nncg_rows, cmf_als_dual_rows, cmf_als_bias_rows and cmf_als_normal (the majoriser's system at the current row).  With no
+ * delta set they launch exactly what they launch without this block.  Each returns CMF_EUNSUPPORTED when a Huber relation it sweeps
+ * has no CSR weights bound (the Huber loss over every cell is not built), a background weight, or a logistic loss; the other
+ * relation may be anything it can be without this block.  NOT HONOURED by the MU, HALS and Newton steps, cmf_weighted_residual_sq,
+ * cmf_als_residual_sq and cmf_als_logistic_loss, which read the relation's weights as bound.  One GPU; cmf_run is not extended.
+ *   cmf_als_huber_loss(ctx, lx, ly): *lx / *ly = sum_O w rho_d(t - a . b) of X / Y with the factors on the device (under biases: the
+ *   adjusted targets), 0 for a relation without a delta; a null pointer skips that side.  CMF_EUNSUPPORTED as above; k_pad > 256.
+ *   cmf_als_huber_weights(ctx, which, t, nnz, w_eff, p_eff) (test entry): w omega and w t omega of image t (0 the pattern, 1 its
+ *   transpose, each in its stored order) at the current factors, nnz floats each; a null pointer skips that array.  CMF_EINVAL for
+ *   a relation without a delta, or when nnz is not the number of stored entries (the size of the caller's buffers, as in
+ *   cmf_als_bias_targets).
+ * The kernel cuts every row into pieces of at most 2048 stored entries, one 256-thread workgroup each: the row in registers, four
+ * gathered rows in flight per lane group, the score in float32 in the fixed order of the lane reduction, omega by a true division.
+ * The loss adds float64 partial sums in piece order behind a kernel boundary.  No atomics: a repeated call from the same state is
+ * bit-identical.  Kernel time: both forms of the pass go to CMF_K_KLMU (2 nnz k_pad flops).                                    */
+int cmf_set_huber_delta(cmf_ctx *ctx, int which, double delta);
+int cmf_get_huber_delta(cmf_ctx *ctx, int which, double *delta);
+int cmf_als_huber_loss(cmf_ctx *ctx, double *lx, double *ly);
+int cmf_als_huber_weights(cmf_ctx *ctx, int which, int t, int64_t nnz, float *w_eff, float *p_eff);
+
 /* sharded form: rank g holds rows of X/U and columns of
  * Y/Z, V replicated.  buf is a DEVICE buffer of cmf_v_buf_elems() floats:
  *   [ X_g^T U_g + Y_g Z_g  (d_pad x k_pad) | U_g^T U_g + Z_g^T Z_g (k_pad x k_pad) ]

@@ -110,6 +110,10 @@ PROTOTYPES = {
     "cmf_set_relation_loss": [_vp, _i32, _i32],
     "cmf_get_relation_loss": [_vp, _i32, C.POINTER(C.c_int)],
     "cmf_als_logistic_loss": [_vp, _pd, _pd],
+    "cmf_set_huber_delta": [_vp, _i32, _dbl],
+    "cmf_get_huber_delta": [_vp, _i32, _pd],
+    "cmf_als_huber_loss": [_vp, _pd, _pd],
+    "cmf_als_huber_weights": [_vp, _i32, _i32, _i64, _pf, _pf],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_data_pass_launches": [_vp, _pi64],
     "cmf_mu_route_launches": [_vp, _pi64],
@@ -808,6 +812,34 @@ class Context:
         lx, ly = C.c_double(0), C.c_double(0)
         check(self._lib.cmf_als_logistic_loss(self._h, C.byref(lx) if want_x else None, C.byref(ly) if want_y else None))
         return lx.value, ly.value
+
+    # ---- ALS with a Huber loss on an observed relation (csrc/cmf_als_huber.hip.h)
+    def set_huber_delta(self, which, delta):
+        """Put relation ``which`` (0 X | 1 Y) under the Huber loss of threshold ``delta`` > 0 for every ALS step and row entry: a
+        reweighting pass runs in front of each sweep that reads it.  0 (or None) takes it back.  Cleared by ``set_problem``."""
+        check(self._lib.cmf_set_huber_delta(self._h, which, float(delta or 0.0)))
+
+    def get_huber_delta(self, which):
+        d = C.c_double(0)
+        check(self._lib.cmf_get_huber_delta(self._h, which, C.byref(d)))
+        return d.value
+
+    def als_huber_loss(self, want_x=True, want_y=True):
+        """(L_x, L_y), L = sum_O w rho_delta(t - s) of the Huber relations with the factors on the device; 0.0 for a relation
+        without a delta and for a side that is not asked for."""
+        lx, ly = C.c_double(0), C.c_double(0)
+        check(self._lib.cmf_als_huber_loss(self._h, C.byref(lx) if want_x else None, C.byref(ly) if want_y else None))
+        return lx.value, ly.value
+
+    def als_huber_weights(self, which, image, nnz):
+        """(w_eff, p_eff) float32[nnz]: w omega and w t omega of the pattern (``image=0``) or its transpose (1) in stored order at the
+        current factors, as a sweep reads them; ``nnz`` must be the stored entries of the pattern.  For the tests."""
+        nnz = int(nnz)
+        if nnz < 0:
+            raise ValueError("als_huber_weights: nnz must be the number of stored entries, got %d" % nnz)
+        hw, hp = np.zeros(nnz, dtype=np.float32), np.zeros(nnz, dtype=np.float32)
+        check(self._lib.cmf_als_huber_weights(self._h, which, image, nnz, hw.ctypes.data_as(_pf), hp.ctypes.data_as(_pf)))
+        return hw, hp
 
     def predict_pairs(self, which, rows, cols, link="linear"):
         """float32[n]: f(offset + r[row] + c[col] + a_row . b_col) of the pairs, a = U, b = V for relation 0 and V, Z for relation 1;

@@ -420,6 +420,15 @@ static int64_t als_piece_len(const cmf_ctx *c) { return c->opt_als_piece > 0 ? r
     default: hipLaunchKernelGGL((cmfk::KERNEL<64>), __VA_ARGS__); break;                                                 \
     }
 
+// ... for a kernel with one more template argument behind GL (TARG)
+#define ALS_LAUNCH_GL_T(c, KERNEL, TARG, ...)                                                                            \
+    switch ((c)->kp) {                                                                                                   \
+    case 32: hipLaunchKernelGGL((cmfk::KERNEL<8, TARG>), __VA_ARGS__); break;                                            \
+    case 64: hipLaunchKernelGGL((cmfk::KERNEL<16, TARG>), __VA_ARGS__); break;                                           \
+    case 128: hipLaunchKernelGGL((cmfk::KERNEL<32, TARG>), __VA_ARGS__); break;                                          \
+    default: hipLaunchKernelGGL((cmfk::KERNEL<64, TARG>), __VA_ARGS__); break;                                           \
+    }
+
 // Rows of `nip` CSR images (ip[s]: the rows' indptr) cut into pieces of at most L stored entries: row by row, within a row image by
 // image, piece(r, s, beg, len) per piece in that order.  The rows are 0 .. nrows, or the listed ones (`rows`, ascending or not).
 // Returns first[i], the pieces before the i-th of those rows ([rows + 1]).

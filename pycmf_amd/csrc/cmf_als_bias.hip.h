@@ -203,10 +203,19 @@ static int als_bias_refresh(cmf_ctx *c, int which) {
     return CMF_OK;
 }
 
-// one bias sweep of relation `which` along `axis` (0 rows, 1 columns) into out (device, rows of that image)
+// (cmf_als_huber.hip.h, which stands below: a relation under a Huber loss, and hw / hp of one of its images from the current state)
+static bool als_huber_rel(const cmf_ctx *c, int which);
+static int als_huber_rel_ok(cmf_ctx *c, const char *what, int which);
+static int als_huber_refresh(cmf_ctx *c, int which, int t);
+
+// one bias sweep of relation `which` along `axis` (0 rows, 1 columns) into out (device, rows of that image).  Under a Huber loss the
+// block is reweighted like a factor's rows: the pass refreshes the image of that axis at the current factors and biases, and the
+// kernel reads w omega where it reads w.
 static int als_bias_sweep(cmf_ctx *c, int which, int axis, float *out) {
     AlsBias &b = c->als_bias[which];
     CHK(als_bias_replan(c, which));
+    const bool huber = als_huber_rel(c, which);
+    if (huber) CHK(als_huber_refresh(c, which, axis));
     const WCsrDev &M = c->wm_sp[which][axis];
     const int fa = which == 0 ? (axis == 0 ? CMF_U : CMF_V) : (axis == 0 ? CMF_V : CMF_Z);
     const int fb = which == 0 ? (axis == 0 ? CMF_V : CMF_U) : (axis == 0 ? CMF_Z : CMF_V);
@@ -214,7 +223,7 @@ static int als_bias_sweep(cmf_ctx *c, int which, int axis, float *out) {
     CHK(ensure_scratch(c, c->als_bias_part, std::max<size_t>(16, (size_t)np * 2 * sizeof(double))));
     cmfk::AlsBiasArgs a;
     a.pieces = b.pieces[axis];
-    a.idx = M.idx; a.tv = M.tv; a.wv = M.wv;
+    a.idx = M.idx; a.tv = M.tv; a.wv = huber ? M.hw : M.wv;
     a.A = c->F[fa]; a.B = c->F[fb];
     a.other = axis == 0 ? b.c : b.r;
     a.mu = (float)b.mu;
@@ -229,6 +238,28 @@ static int als_bias_sweep(cmf_ctx *c, int which, int axis, float *out) {
         hipLaunchKernelGGL(cmfk::als_bias_combine_kernel, dim3((unsigned)((M.rows + 255) / 256)), dim3(256), 0, c->stream, (const double *)a.part,
                            (const int64_t *)b.first[axis], M.rows, b.lb, out);
     HIPCHK(hipGetLastError());
+    return CMF_OK;
+}
+
+// t of relation `which` in the stored order of the transpose: the counting sort of cmf_set_weighted_csr again, from the images on
+// the device
+static int als_transposed_targets(cmf_ctx *c, int which, std::vector<float> &tt) {
+    const WCsrDev &M0 = c->wm_sp[which][0], &M1 = c->wm_sp[which][1];
+    const int64_t nnz = M0.nnz;
+    std::vector<int64_t> ip((size_t)M0.rows + 1), ipt((size_t)M1.rows + 1);
+    std::vector<int32_t> ix((size_t)nnz);
+    std::vector<float> t((size_t)nnz);
+    tt.assign((size_t)nnz, 0.f);
+    HIPCHK(hipMemcpyAsync(ip.data(), M0.indptr, ip.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ipt.data(), M1.indptr, ipt.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (nnz) {
+        HIPCHK(hipMemcpyAsync(ix.data(), M0.idx, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(t.data(), M0.tv, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::vector<int64_t> pos(ipt.begin(), ipt.end() - 1);
+    for (int64_t i = 0; i < M0.rows; ++i)
+        for (int64_t q = ip[(size_t)i]; q < ip[(size_t)i + 1]; ++q) tt[(size_t)pos[(size_t)ix[(size_t)q]]++] = t[(size_t)q];
     return CMF_OK;
 }
 
@@ -259,21 +290,9 @@ extern "C" int cmf_set_biases(cmf_ctx *c, int which, int enable, double mu, doub
     AlsBias &b = c->als_bias[which];
     WCsrDev &M0 = c->wm_sp[which][0], &M1 = c->wm_sp[which][1];
     const int64_t nnz = M0.nnz;
-    // t in the stored order of the transpose: the counting sort of cmf_set_weighted_csr again, from the images on the device
     {
-        std::vector<int64_t> ip((size_t)M0.rows + 1), ipt((size_t)M1.rows + 1);
-        std::vector<int32_t> ix((size_t)nnz);
-        std::vector<float> t((size_t)nnz), tt((size_t)nnz);
-        HIPCHK(hipMemcpyAsync(ip.data(), M0.indptr, ip.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(ipt.data(), M1.indptr, ipt.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        if (nnz) {
-            HIPCHK(hipMemcpyAsync(ix.data(), M0.idx, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(t.data(), M0.tv, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        std::vector<int64_t> pos(ipt.begin(), ipt.end() - 1);
-        for (int64_t i = 0; i < M0.rows; ++i)
-            for (int64_t q = ip[(size_t)i]; q < ip[(size_t)i + 1]; ++q) tt[(size_t)pos[(size_t)ix[(size_t)q]]++] = t[(size_t)q];
+        std::vector<float> tt;
+        CHK(als_transposed_targets(c, which, tt));
         int rc = dev_alloc(c, (void **)&M1.tv, std::max<size_t>(16, (size_t)nnz * sizeof(float)), false);
         if (rc == CMF_OK && nnz) {
             hipError_t he = hipMemcpyAsync(M1.tv, tt.data(), (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, c->stream);
@@ -357,6 +376,7 @@ extern "C" int cmf_als_bias_rows(cmf_ctx *c, int which, int axis, float *host_ou
     NEED_PROBLEM(c);
     float *vec; int64_t n;
     CHK(als_bias_vector(c, "cmf_als_bias_rows", which, axis, &vec, &n));
+    CHK(als_huber_rel_ok(c, "cmf_als_bias_rows", which));   // (a Huber relation: the states every step refuses)
     if (!host_out && n > 0) return fail(CMF_EINVAL, "cmf_als_bias_rows: null output");
     DeviceGuard dg(c->device);
     CHK(ensure_scratch(c, c->als_bias_ws, std::max<size_t>(16, (size_t)n * sizeof(float))));

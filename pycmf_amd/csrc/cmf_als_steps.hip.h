@@ -667,6 +667,8 @@ static int als_dual_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_be
 //   nn_cg_steps > 0  a non-negative factor with an observed relation runs that many projected CG steps per row
 //   dual_max > 0     an exact row sweep without a shared term or a logistic relation solves its rows of 1 .. dual_max entries in dual form
 //   biases           biases are bound: the adjusted targets are refreshed before the sweeps and the bias blocks swept after them
+// A relation under a Huber loss (cmf_als_huber.hip.h) is no option of a step: every sweep that reads one runs the reweighting pass
+// first and its route, whichever it is, reads the effective weights and products for the sweep's duration (AlsHuberGuard).
 struct AlsStepOpts { int nn_sweeps = 0, cg_steps = 0, nn_cg_steps = 0, dual_max = 0; bool biases = false; };
 
 enum AlsRoute { ALS_SHARED_EXACT, ALS_SHARED_HALS, ALS_ROWS_EXACT, ALS_ROWS_NNLS, ALS_ROWS_CG, ALS_ROWS_NNCG, ALS_ROWS_DUAL };
@@ -692,6 +694,8 @@ static int als_step(cmf_ctx *c, const char *what, double l2, int nn_mask, int ma
         if (!(mask & bits[s]) || c->frows[f] <= 0) continue;
         const bool nn = (nn_mask & nnb[s]) != 0;
         const AlsSweep sw = als_sweep(c, f);
+        AlsHuberGuard huber(c);   // the Huber sides of this sweep: refreshed from the current factors, bound until the sweep is over
+        CHK(huber.bind(sw));
         switch (als_route(als_observed(sw), als_shared_present(c, sw), als_logit_sweep(c, sw), c->kp, nn, o)) {
         case ALS_SHARED_EXACT: CHK(als_sweep_shared(c, what, sw, l2, nn)); break;
         case ALS_SHARED_HALS: CHK(als_nnls_sweep_shared(c, what, f, l2, o.nn_sweeps)); break;
@@ -733,6 +737,7 @@ static int als_check(cmf_ctx *c, const char *what, double l2, int mask) {
     if (mask <= 0 || mask > 7) return fail(CMF_EINVAL, "%s: update_mask must name at least one of U, V, Z (got %d)", what, mask);
     if (c->kp > 256) return fail(CMF_EUNSUPPORTED, "%s: n_components <= 256 only (k_pad = %d)", what, c->kp);
     CHK(als_logit_check(c, what, mask));
+    CHK(als_huber_check(c, what, mask));
     if (mask & (CMF_UPD_U | CMF_UPD_V)) CHK(als_relation_ok(c, what, 0));
     if (mask & (CMF_UPD_Z | CMF_UPD_V)) CHK(als_relation_ok(c, what, 1));
     return CMF_OK;
@@ -876,6 +881,8 @@ static int als_rows_entry(cmf_ctx *c, const char *what, int which, int64_t row0,
     const size_t bytes = (size_t)nrows * c->kp * sizeof(float);
     CHK(ensure_scratch(c, c->als_cg_ws, bytes));
     HIPCHK(hipMemsetAsync(c->als_cg_ws.p, 0, bytes, c->stream));
+    AlsHuberGuard huber(c);
+    CHK(huber.bind(sw));
     CHK(run(sw, (float *)c->als_cg_ws.p));
     HIPCHK(hipMemcpyAsync(host_f, c->als_cg_ws.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -978,6 +985,8 @@ extern "C" int cmf_als_normal(cmf_ctx *c, int which, int64_t row0, int64_t nrows
     if (!als_observed(sw)) return fail(CMF_EINVAL, "cmf_als_normal: this sweep has no observed relation: one shared matrix, no per-row systems");
     if (nrows == 0) return CMF_OK;
     DeviceGuard dg(c->device);
+    AlsHuberGuard huber(c);
+    CHK(huber.bind(sw));
     return als_rows_to_host(c, sw, l2, row0, row0 + nrows, host_H, host_g);
 }
 

@@ -92,6 +92,8 @@ struct WCsrDev {
     float *pv = nullptr, *wv = nullptr, *tv = nullptr;
     float *ev = nullptr;   // excess weights w - c0 under a background weight (cmf_als_bg.hip.h), or null
     float *bt = nullptr, *bp = nullptr; // adjusted targets t - mu - r_i - c_j and w times them under biases (cmf_als_bias.hip.h), or null
+    float *hw = nullptr, *hp = nullptr; // effective weights w omega and products under a Huber loss (cmf_als_huber.hip.h), or null; hbound:
+    bool hbound = false;                // ... a sweep has them bound: the row kernels read them (AlsHuberGuard)
     int64_t rows = 0, cols = 0, nnz = 0;
 };
 
@@ -106,6 +108,17 @@ struct AlsBias {
     int64_t *first[2] = {nullptr, nullptr};
     int64_t npieces[2] = {0, 0};
     int64_t L = 0;                    // the piece length the lists were built for
+};
+
+// A Huber loss on a relation with CSR weights (cmf_als_huber.hip.h): delta, and what the reweighting pass needs beyond the images
+// (their hw / hp: WCsrDev) -- t in the stored order of the transpose and the piece lists of both images, built at the first pass
+// over a bound pattern (ready)
+struct AlsHuber {
+    double delta = 0.0;               // 0: none
+    bool ready = false;
+    float *tt1 = nullptr;
+    cmfk::AlsBiasPiece *pieces[2] = {nullptr, nullptr};
+    int64_t npieces[2] = {0, 0};
 };
 
 // Per-row multipliers of l2 for one factor under the ALS steps (cmf_set_l2_rows): the doubles as given, their float32 image on the
@@ -194,6 +207,7 @@ struct cmf_ctx {
     DevBuf als_bg_s, als_bg64;            // ... the shared matrix sum coef Gram of a sweep; float64 Grams of the error's trace term
     int rel_loss[2] = {0, 0};             // loss of X / Y under the ALS steps (cmf_als_logit.hip.h): CMF_LOSS_FROBENIUS | CMF_LOSS_LOGISTIC
     AlsBias als_bias[2];                  // mu and row / column biases of X / Y (cmf_als_bias.hip.h; off: none)
+    AlsHuber als_huber[2];                // Huber loss of X / Y under the ALS steps (cmf_als_huber.hip.h; delta 0: none)
     int opt_als_bias_piece = 0;           // ... stored entries per piece of a row in the bias passes (0: the default, 2048; > 0 rounded up to 16; < 0: every row is one piece)
     DevBuf als_bias_part, als_bias_ws;    // ... (num, wsum) of every piece; cmf_als_bias_rows' result / the pairs and values of cmf_predict_pairs
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
@@ -404,6 +418,21 @@ static void als_bias_free(cmf_ctx *c, int which) {
     dev_free(c, c->wm_sp[which][1].tv);   // t in the stored order of the transpose exists under biases only
     c->wm_sp[which][1].tv = nullptr;
     b = AlsBias();
+}
+// what the Huber pass allocated for a relation's pattern; delta stays (cmf_set_huber_delta)
+static void als_huber_free(cmf_ctx *c, int which) {
+    AlsHuber &h = c->als_huber[which];
+    dev_free(c, h.tt1);
+    for (int t = 0; t < 2; ++t) {
+        dev_free(c, h.pieces[t]);
+        WCsrDev &M = c->wm_sp[which][t];
+        dev_free(c, M.hw); dev_free(c, M.hp);
+        M.hw = M.hp = nullptr;
+        M.hbound = false;
+    }
+    const double delta = h.delta;
+    h = AlsHuber();
+    h.delta = delta;
 }
 static void drop_graph(StepGraph &g) {
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -884,6 +913,7 @@ static void release_problem(cmf_ctx *c) {
     for (int f = 0; f < 3; ++f) c->als_l2rows[f] = AlsL2Rows();   // (the device images went with c->owned)
     for (int w = 0; w < 2; ++w) {
         c->als_bias[w] = AlsBias();
+        c->als_huber[w] = AlsHuber();
         c->rel_loss[w] = 0;
         c->wm_bg[w] = 0.0;
         c->wm_kind[w] = 0; c->wm_w[w] = c->wm_p[w] = nullptr;
@@ -2011,4 +2041,5 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_als_bias.hip.h"    // biases
 #include "cmf_als_bg.hip.h"      // background weights, the shared terms of a sweep
 #include "cmf_als_logit.hip.h"   // relation losses
+#include "cmf_als_huber.hip.h"   // the Huber loss: the reweighting pass in front of a sweep
 #include "cmf_als_steps.hip.h"   // the chunk loop, the routes, als_step and every step entry point

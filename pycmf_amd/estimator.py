@@ -13,7 +13,7 @@ from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
 from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_beta, check_beta_extras, check_beta_data, check_entry_weights, check_hals,
-                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_als_nn_cg_steps, check_als_dual_max, check_als_l2_scale, check_background_weight, check_biases, check_bias_l2, check_logistic)
+                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_als_nn_cg_steps, check_als_dual_max, check_als_l2_scale, check_background_weight, check_huber_delta, check_biases, check_bias_l2, check_logistic)
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -43,7 +43,8 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                     device=0, sg_sampler="numpy", n_gpus=1, _return_solver=False, loss="frobenius",
                                     x_entry_weights=None, y_entry_weights=None, als_nn_sweeps=0, als_cg_steps=0,
                                     x_background_weight=0.0, y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None,
-                                    _x_bias_init=None, _y_bias_init=None, als_nn_cg_steps=0, als_dual_max=0, als_l2_scale=0.0):
+                                    _x_bias_init=None, _y_bias_init=None, als_nn_cg_steps=0, als_dual_max=0, als_l2_scale=0.0,
+                                    x_huber_delta=None, y_huber_delta=None):
     """Factorise X ~ f(U V^T) and Y ~ f(V Z^T) with a shared V on an MI355X.
 
     Same contract as the reference function (pycmf/cmf.py:215-456): returns
@@ -133,6 +134,13 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     sparse W or ``'observed'``, and it must have no background weight.  ``ValueError`` before any device is touched: True with
     another solver, without such entry weights or with a background weight; a ``bias_l2`` that is not None or a finite number >= 0.
     The fitted biases are on the solver object (``x_bias`` / ``y_bias``) and on the estimator (``CMF.x_bias_`` / ``y_bias_``).
+
+    ``x_huber_delta`` / ``y_huber_delta``: None | d > 0 (``solver='als'`` only) -- a robust fit of that relation: its term becomes
+    the Huber loss sum_O w rho_d(t - a.b), quadratic up to |r| = d and linear beyond, so that a few grossly wrong entries (bot
+    accounts, mis-keyed ratings, huge play counts) no longer bend their rows and columns.  Every sweep that reads the relation is
+    preceded by one reweighting pass and then runs the route the other ALS keywords name (``HipALSSolver``).  ``ValueError`` before
+    any device is touched: a bool, a non-finite or non-positive value; another solver; ``n_gpus > 1``; entry weights of that
+    relation that are not a SciPy sparse W or ``'observed'``; a logit link or a background weight on it.
     """
     if n_components is None:
         n_components = max(X.shape[1], Y.shape[1])
@@ -155,6 +163,10 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     x_biases = check_biases(x_biases, "x", solver, x_entry_weights, x_background_weight)
     y_biases = check_biases(y_biases, "y", solver, y_entry_weights, y_background_weight)
     bias_l2 = check_bias_l2(bias_l2)
+    x_huber_delta = check_huber_delta(x_huber_delta, "x", solver, n_gpus, x_entry_weights, x_link, x_background_weight,
+                                      have=X is not None and (update_U or update_V))
+    y_huber_delta = check_huber_delta(y_huber_delta, "y", solver, n_gpus, y_entry_weights, y_link, y_background_weight,
+                                      have=Y is not None and (update_Z or update_V))
     if bias_l2 is not None and solver != "als":
         raise ValueError("bias_l2 is the bias regulariser of solver='als': it must be None with solver=%r" % (solver,))
 
@@ -212,7 +224,8 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                      x_entry_weights=x_entry_weights, y_entry_weights=y_entry_weights, nn_sweeps=als_nn_sweeps, cg_steps=als_cg_steps,
                                      x_background_weight=x_background_weight, y_background_weight=y_background_weight,
                                      x_biases=x_biases, y_biases=y_biases, bias_l2=bias_l2, x_bias_init=_x_bias_init,
-                                     y_bias_init=_y_bias_init, nn_cg_steps=als_nn_cg_steps, dual_max=als_dual_max, l2_scale=als_l2_scale, **common)
+                                     y_bias_init=_y_bias_init, nn_cg_steps=als_nn_cg_steps, dual_max=als_dual_max, l2_scale=als_l2_scale,
+                                     x_huber_delta=x_huber_delta, y_huber_delta=y_huber_delta, **common)
         solver_object.check_weights(X, Y)
     else:
         raise ValueError("No such solver: %s" % solver)
@@ -386,9 +399,18 @@ class CMF(BaseEstimator, TransformerMixin):
     ``CMF(solver="als", l2_reg=0.05, als_l2_scale=1.0)`` is ALS-WR's weighted-lambda regulariser.  After a fit ``l2_multipliers_``
     holds ``(m_U, m_V, m_Z)`` (None with the option off); ``transform`` counts the rows of the X / Y it is given, so a folded-in
     row gets the penalty of its own length.  A keyword-only OPTION like ``als_nn_cg_steps``.
+
+    ``x_huber_delta`` / ``y_huber_delta`` (``solver='als'`` only, default None): d > 0 fits that relation under the Huber loss of
+    threshold d over its observed entries instead of the squared one (``collective_matrix_factorization``):
+    ``CMF(solver="als", l2_reg=0.5, x_huber_delta=1.0, ...).fit(X, Y, x_entry_weights='observed')`` for ratings with gross outliers.
+    ``reconstruction_err_`` and the stopping test take sqrt(2 sum_O w rho_d) from such a relation, ``huber_loss_`` holds the sums
+    ``(L_x, L_y)`` after a fit (None without a delta), and ``transform`` folds new rows in under the same loss.  ``predict``,
+    ``score_entries``, ``top_n``, ``ranks`` and ``evaluate`` read the fitted factors as always.  Keyword-only OPTIONS like
+    ``als_nn_cg_steps``.
     """
 
-    _OPTIONS = {"als_nn_cg_steps": 0, "als_dual_max": 0, "als_l2_scale": 0.0}     # keyword-only options outside get_params(): name -> default
+    # keyword-only options outside get_params(): name -> default
+    _OPTIONS = {"als_nn_cg_steps": 0, "als_dual_max": 0, "als_l2_scale": 0.0, "x_huber_delta": None, "y_huber_delta": None}
 
     def __init__(self, n_components=None, x_init=None, y_init=None, solver='mu', alpha='auto',
                  beta_loss='frobenius', tol=1e-4, max_iter=600,
@@ -455,7 +477,8 @@ class CMF(BaseEstimator, TransformerMixin):
                     hessian_pertubation=self.hessian_pertubation,
                     sg_sample_ratio=self.sg_sample_ratio, device=self.device, sg_sampler=self.sg_sampler,
                     loss=self.loss, als_nn_sweeps=self.als_nn_sweeps, als_cg_steps=self.als_cg_steps,
-                    als_nn_cg_steps=self.als_nn_cg_steps, als_dual_max=self.als_dual_max, als_l2_scale=self.als_l2_scale)
+                    als_nn_cg_steps=self.als_nn_cg_steps, als_dual_max=self.als_dual_max, als_l2_scale=self.als_l2_scale,
+                    x_huber_delta=self.x_huber_delta, y_huber_delta=self.y_huber_delta)
 
     def fit_transform(self, X, Y, U=None, V=None, Z=None, x_entry_weights=None, y_entry_weights=None, x_background_weight=0.0,
                       y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None):
@@ -485,6 +508,7 @@ class CMF(BaseEstimator, TransformerMixin):
         # data and the final factors still live (cmf.py:697-698)
         self.reconstruction_err_ = solver_object.reconstruction_error()
         self.logistic_loss_ = getattr(solver_object, "logistic_loss", None)   # (L_x, L_y) under loss='logistic', else None
+        self.huber_loss_ = getattr(solver_object, "huber_loss", None)         # (L_x, L_y) under a Huber delta, else None
         self.x_bias_ = _fitted_bias(getattr(solver_object, "x_bias", None))
         self.y_bias_ = _fitted_bias(getattr(solver_object, "y_bias", None))
         self.bias_l2_ = bias_l2

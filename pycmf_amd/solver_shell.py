@@ -244,6 +244,36 @@ def check_background_weight(value, name, solver="als", entry_weights="observed")
     return value
 
 
+def check_huber_delta(value, name, solver="als", n_gpus=1, entry_weights="observed", link="linear", background_weight=0.0, have=True):
+    """``x_huber_delta`` / ``y_huber_delta`` (``name`` 'x' | 'y'): None, or a finite number > 0 -- with solver='als' on one GPU only,
+    and (``have``: the relation is part of the call) for a relation with a linear link whose entry weights are a SciPy sparse W or
+    'observed' and that has no background weight.  Returns None or the value as a float; no device is touched."""
+    if value is None:
+        return None
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (numbers.Real, np.integer, np.floating)):
+        raise ValueError("%s_huber_delta must be None or a finite number > 0, got %r" % (name, value))
+    value = float(value)
+    if not np.isfinite(value) or not value > 0 or not np.isfinite(np.float32(value)) or not np.float32(value) > 0:
+        raise ValueError("%s_huber_delta must be None or a finite number > 0, got %r" % (name, value))
+    if solver != "als":
+        raise ValueError("%s_huber_delta is the Huber loss of solver='als': it must be None with solver=%r, got %r" % (name, solver, value))
+    if n_gpus != 1:
+        raise ValueError("%s_huber_delta runs on one GPU: n_gpus must be 1, got %r (the sharded form is not built)" % (name, n_gpus))
+    if not have:
+        return value
+    import scipy.sparse as sp
+    if entry_weights is None or not (isinstance(entry_weights, str) or sp.issparse(entry_weights)):
+        raise ValueError("%s_huber_delta=%r needs %s_entry_weights that name the observed entries: pass a SciPy sparse W or 'observed', got "
+                         "%s; the Huber loss over every cell is not built" % (name, value, name, "None" if entry_weights is None else "a dense array"))
+    if link == "logit":
+        raise ValueError("%s_huber_delta=%r on a relation with %s_link='logit' is not built: the Huber loss is a loss of the linear link"
+                         % (name, value, name))
+    if background_weight:
+        raise ValueError("%s_huber_delta=%r together with %s_background_weight=%r is not built: the Huber loss runs over the stored "
+                         "entries only" % (name, value, name, background_weight))
+    return value
+
+
 def check_biases(flag, name, solver="als", entry_weights="observed", background_weight=0.0):
     """``x_biases`` / ``y_biases`` (``name`` 'x' | 'y'): a bool; True with solver='als' only, for a relation whose entry weights
     resolve to a CSR pattern (a SciPy sparse W or 'observed') and that has no background weight.  Returns the flag as a bool; no
@@ -932,6 +962,16 @@ class HipALSSolver(HipMUSolver):
     zeros).  The bias blocks follow the update flag of the factor on their axis (r_x: U; c_x, r_y: V; c_y: Z), so a fold-in of new
     rows against a fixed V fits their own biases too.  The error of such a relation is the weighted residual of the biased model.
 
+    ``x_huber_delta=d`` / ``y_huber_delta`` (None, or a finite number > 0): the relation -- sparse entry weights or ``'observed'``, a
+    linear link, no background weight -- is fitted under the Huber loss  sum_O w rho_d(t - a.b),  rho_d(r) = r^2 / 2 for |r| <= d and
+    d (|r| - d / 2) beyond, so that a grossly wrong entry pulls its row and its column with a bounded force.  In front of every
+    sweep that reads the relation one pass writes the weights w min(1, d / |r|) at the residuals under the current rows
+    (``cmf_set_huber_delta``), and the sweep -- whichever route the keywords above name, the bias blocks included -- reads them
+    for w: each row then never raises the half-quadratic majoriser of its loss, and the descent statements above hold for the
+    Huber objective.  ``l2_scale`` keeps counting the original weights.  The error metric takes sqrt(2 sum_O w rho_d) from such a
+    relation -- the root of its squared residuals while none exceeds d -- and ``huber_loss`` holds ``(L_x, L_y)`` of the last
+    evaluation (0 for a relation without a delta).
+
     ``loss='logistic'``: the relations whose link is 'logit' (at least one) are fitted as sigmoid(a.b) under the weighted
     cross-entropy over their observed entries,  sum_O w [softplus(a.b) - t a.b],  t in [0, 1]; a relation with a linear link keeps
     its Frobenius term (observed or full), so one V sweep may mix both.  A logistic relation needs a SciPy sparse W or ``'observed'``
@@ -949,7 +989,7 @@ class HipALSSolver(HipMUSolver):
 
     def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, cg_steps=0, x_background_weight=0.0,
                  y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None, x_bias_init=None, y_bias_init=None,
-                 loss="frobenius", nn_cg_steps=0, dual_max=0, l2_scale=0.0, **kwargs):
+                 loss="frobenius", nn_cg_steps=0, dual_max=0, l2_scale=0.0, x_huber_delta=None, y_huber_delta=None, **kwargs):
         check_loss(loss, "als")
         self.l2_scale = check_als_l2_scale(l2_scale)
         self.l2_multipliers = None           # (m_U, m_V, m_Z) of the bound problem under l2_scale > 0
@@ -977,13 +1017,18 @@ class HipALSSolver(HipMUSolver):
             self._logit = check_logistic(self.x_link, self.y_link, x_entry_weights, y_entry_weights, cg_steps, self.x_background_weight,
                                          self.y_background_weight, self.x_biases, self.y_biases, have_x=False, have_y=False)
         self.logistic_loss = None            # (L_x, L_y) of the last error evaluation under loss='logistic'
+        # (the relations that take part in a call are checked again when it resolves its weights: a fold-in binds one of them)
+        self.x_huber_delta = check_huber_delta(x_huber_delta, "x", "als", 1, x_entry_weights, self.x_link, self.x_background_weight, have=False)
+        self.y_huber_delta = check_huber_delta(y_huber_delta, "y", "als", 1, y_entry_weights, self.y_link, self.y_background_weight, have=False)
+        self.huber_loss = None               # (L_x, L_y) of the last error evaluation under a Huber delta
         self.nn_sweeps = int(nn_sweeps)
         self.cg_steps = int(cg_steps)
         self.nn_cg_steps = int(nn_cg_steps)
         self.dual_max = int(dual_max)
 
     def _weights_key(self):
-        return super()._weights_key() + (self.x_background_weight, self.y_background_weight, self.x_biases, self.y_biases) + tuple(self._logit) + (self.l2_scale,)
+        return (super()._weights_key() + (self.x_background_weight, self.y_background_weight, self.x_biases, self.y_biases) + tuple(self._logit)
+                + (self.l2_scale, self.x_huber_delta, self.y_huber_delta))
 
     def _bias_l2(self):
         return self.bias_l2 if self.bias_l2 is not None else float(self.l2_reg)
@@ -1010,6 +1055,8 @@ class HipALSSolver(HipMUSolver):
                 for on, ew, nm in ((self._logit[0], raw[0], "X"), (self._logit[1], raw[1], "Y")):
                     if on and ew is not None:
                         check_logistic_data(ew.t, nm)
+            check_huber_delta(self.x_huber_delta, "x", "als", 1, self.x_entry_weights, self.x_link, self.x_background_weight, have=X is not None)
+            check_huber_delta(self.y_huber_delta, "y", "als", 1, self.y_entry_weights, self.y_link, self.y_background_weight, have=Y is not None)
             self._als_resolved = tuple(_weights_as_pattern(ew) for ew in raw)
             check_background_floor(self._als_resolved[0], self.x_background_weight, "x")
             check_background_floor(self._als_resolved[1], self.y_background_weight, "y")
@@ -1041,6 +1088,9 @@ class HipALSSolver(HipMUSolver):
             for which, M in ((0, X), (1, Y)):
                 if self._logit[which] and M is not None:
                     ctx.set_relation_loss(which, "logistic")
+            for which, M, delta in ((0, X, self.x_huber_delta), (1, Y, self.y_huber_delta)):
+                if delta and M is not None:
+                    ctx.set_huber_delta(which, delta)
             for which, start in enumerate(self._bias_start):
                 if start is not None:
                     ctx.set_biases(which, True, start[0], self._bias_l2())
@@ -1076,7 +1126,12 @@ class HipALSSolver(HipMUSolver):
         X, Y = self._XY
         wx, wy = self.x_entry_weights is not None, self.y_entry_weights is not None
         ex2 = ey2 = 0.0
-        if self.x_background_weight or self.y_background_weight or self.x_biases or self.y_biases:
+        hx, hy = bool(self.x_huber_delta) and X is not None, bool(self.y_huber_delta) and Y is not None
+        if hx or hy:   # (a Huber relation has entry weights, no background, a linear link) its squared residual is never read
+            qx, qy = wx and X is not None and not (hx or self._logit[0]), wy and Y is not None and not (hy or self._logit[1])
+            if qx or qy:
+                ex2, ey2 = self._ctx.als_residual_sq(qx, qy) if self._needs_als_residual() else self._ctx.weighted_residual_sq(qx, qy)
+        elif self._needs_als_residual():
             # (biases: the residual of the biased model, t - mu - r - c - a.b, from the same call)
             # E = sum_O w (t - s)^2 + c0 (<A^T A, B^T B> - sum_O s^2): the error over every cell; a side without a background
             # gets the bits of the weighted residual from the same call
@@ -1095,7 +1150,14 @@ class HipALSSolver(HipMUSolver):
             lx, ly = self._ctx.als_logistic_loss(self._logit[0] and X is not None, self._logit[1] and Y is not None)
             self.logistic_loss = (lx, ly)
             ex, ey = (lx if self._logit[0] and X is not None else ex), (ly if self._logit[1] and Y is not None else ey)
+        if hx or hy:   # a Huber relation contributes sqrt(2 sum w rho): the root of its squared residuals while none exceeds delta
+            lx, ly = self._ctx.als_huber_loss(hx, hy)
+            self.huber_loss = (lx, ly)
+            ex, ey = (np.sqrt(2.0 * lx) if hx else ex), (np.sqrt(2.0 * ly) if hy else ey)
         return ex, ey
+
+    def _needs_als_residual(self):
+        return bool(self.x_background_weight or self.y_background_weight or self.x_biases or self.y_biases)
 
     def _device_step_error(self, l1_reg, l2_reg, alpha):
         return None
