@@ -642,6 +642,36 @@ int cmf_get_huber_delta(cmf_ctx *ctx, int which, double *delta);
 int cmf_als_huber_loss(cmf_ctx *ctx, double *lx, double *ly);
 int cmf_als_huber_weights(cmf_ctx *ctx, int which, int t, int64_t nnz, float *w_eff, float *p_eff);
 
+/* ---- ALS with a logistic loss on every route: the reweighting as a pass of its own (csrc/cmf_als_logit_pass.hip.h) ----
+ * By default a logistic relation (cmf_set_relation_loss) is reweighted inside the normal-equation kernel, so only the routes that
+ * form the k x k systems honour it.  Under this flag the relation is reweighted like a Huber one instead: ONE pass
+ * (als_logit_pass_kernel) in front of every sweep writes  w kappa(xi)  per stored entry of the image the sweep reads, xi the score
+ * under the CURRENT row, next to  w t - w / 2  (written once per bound pattern), and the sweep's route -- exact, coordinate
+ * descent, conjugate gradients signed or projected, dual -- reads them where it reads w and w t, for that sweep only; no row kernel
+ * changes.  Every route starts at the current row and never raises the Jaakkola-Jordan bound, so every sweep lowers the objective
+ * (a non-negative factor that is only projected carries no guarantee, as without this block).
+ *   cmf_set_logit_pass(ctx, which, enable): `which` 0 = X | 1 = Y (CMF_EINVAL otherwise); enable != 0 sets the flag, 0 clears it and
+ *   drops what the pass built.  It may be set before or after cmf_set_relation_loss and acts only while the relation is logistic:
+ *   on a Frobenius relation every entry point gives the bits it gives without it.  Cleared by cmf_set_problem; kept when the
+ *   weights are bound again.  cmf_get_logit_pass reads it back (CMF_EINVAL for a null output).
+ * HONOURED BY every ALS step (cmf_als_step, _nnls_, _cg_, _nncg_, _dual_step) and the row entries cmf_als_cg_rows,
+ * cmf_als_nncg_rows, cmf_als_dual_rows and cmf_als_normal (the majoriser's system at the current row).  For routing such a relation
+ * counts as a Frobenius one: a V sweep may read a passed logistic X, a fused logistic Y and a Frobenius relation in one launch.
+ * With the flag clear every entry point launches and refuses exactly what it does without this block.  Refused with the flag as
+ * without it (CMF_EUNSUPPORTED): a logistic relation without CSR weights, with a background weight, with biases, or with a Huber
+ * delta; k_pad > 256.  cmf_als_logistic_loss, the residuals and every non-ALS step read the relation as bound.  One GPU; cmf_run is
+ * not extended.
+ *   cmf_als_logit_weights(ctx, which, t, nnz, w_eff, p_eff) (test entry): w kappa and w t - w / 2 of image t (0 the pattern, 1 its
+ *   transpose, each in its stored order) at the current factors, nnz floats each; a null pointer skips that array.  CMF_EINVAL for
+ *   a relation that is not logistic or whose flag is clear, or when nnz is not the number of stored entries.
+ * The kernel has the layout of the Huber pass (pieces of at most 2048 stored entries, one 256-thread workgroup each, the row in
+ * registers, four gathered rows in flight per lane group, the score in float32 in the fixed order of the lane reduction), kappa =
+ * |s| < 1e-4 ? 1/4 : tanh(s / 2) / (2 s) by a true division -- the expression of the fused kernel.  No atomics: a repeated call from
+ * the same state is bit-identical.  Kernel time: CMF_K_KLMU (2 nnz k_pad flops).                                                */
+int cmf_set_logit_pass(cmf_ctx *ctx, int which, int enable);
+int cmf_get_logit_pass(cmf_ctx *ctx, int which, int *enabled);
+int cmf_als_logit_weights(cmf_ctx *ctx, int which, int t, int64_t nnz, float *w_eff, float *p_eff);
+
 /* sharded form: rank g holds rows of X/U and columns of
  * Y/Z, V replicated.  buf is a DEVICE buffer of cmf_v_buf_elems() floats:
  *   [ X_g^T U_g + Y_g Z_g  (d_pad x k_pad) | U_g^T U_g + Z_g^T Z_g (k_pad x k_pad) ]

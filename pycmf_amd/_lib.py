@@ -114,6 +114,9 @@ PROTOTYPES = {
     "cmf_get_huber_delta": [_vp, _i32, _pd],
     "cmf_als_huber_loss": [_vp, _pd, _pd],
     "cmf_als_huber_weights": [_vp, _i32, _i32, _i64, _pf, _pf],
+    "cmf_set_logit_pass": [_vp, _i32, _i32],
+    "cmf_get_logit_pass": [_vp, _i32, C.POINTER(C.c_int)],
+    "cmf_als_logit_weights": [_vp, _i32, _i32, _i64, _pf, _pf],
     "cmf_v_buf_elems": [_vp, _pi64],
     "cmf_data_pass_launches": [_vp, _pi64],
     "cmf_mu_route_launches": [_vp, _pi64],
@@ -839,6 +842,28 @@ class Context:
             raise ValueError("als_huber_weights: nnz must be the number of stored entries, got %d" % nnz)
         hw, hp = np.zeros(nnz, dtype=np.float32), np.zeros(nnz, dtype=np.float32)
         check(self._lib.cmf_als_huber_weights(self._h, which, image, nnz, hw.ctypes.data_as(_pf), hp.ctypes.data_as(_pf)))
+        return hw, hp
+
+    # ---- ALS with a logistic loss on every route (csrc/cmf_als_logit_pass.hip.h)
+    def set_logit_pass(self, which, enable=True):
+        """Reweight the logistic relation ``which`` (0 X | 1 Y) by a pass of its own in front of every sweep, so that every ALS route
+        honours its loss (CG, projected CG and dual rows included); False: inside the normal-equation kernel, the default.  It acts
+        only while the relation is logistic.  Cleared by ``set_problem``."""
+        check(self._lib.cmf_set_logit_pass(self._h, which, 1 if enable else 0))
+
+    def get_logit_pass(self, which):
+        on = C.c_int(0)
+        check(self._lib.cmf_get_logit_pass(self._h, which, C.byref(on)))
+        return bool(on.value)
+
+    def als_logit_weights(self, which, image, nnz):
+        """(w_eff, p_eff) float32[nnz]: w kappa and w t - w / 2 of the pattern (``image=0``) or its transpose (1) in stored order at
+        the current factors, as a sweep reads them; ``nnz`` must be the stored entries of the pattern.  For the tests."""
+        nnz = int(nnz)
+        if nnz < 0:
+            raise ValueError("als_logit_weights: nnz must be the number of stored entries, got %d" % nnz)
+        hw, hp = np.zeros(nnz, dtype=np.float32), np.zeros(nnz, dtype=np.float32)
+        check(self._lib.cmf_als_logit_weights(self._h, which, image, nnz, hw.ctypes.data_as(_pf), hp.ctypes.data_as(_pf)))
         return hw, hp
 
     def predict_pairs(self, which, rows, cols, link="linear"):

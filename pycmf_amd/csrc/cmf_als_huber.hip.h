@@ -125,16 +125,20 @@ static int als_huber_check(cmf_ctx *c, const char *what, int mask) {
 }
 
 // What the pass needs beyond the images: hw / hp of both images, t in the stored order of the transpose, and the piece lists of both
-// images -- built once per bound pattern (als_huber_free drops them with the weights), like AlsBias::pieces.
-static int als_huber_build(cmf_ctx *c, int which) {
+// images -- built once per bound pattern (als_huber_free drops them with the weights), like AlsBias::pieces.  logit: for the logistic
+// pass (cmf_als_logit_pass.hip.h), which shares the arrays and the piece lists and reads no targets.
+static int als_huber_build(cmf_ctx *c, int which, bool logit) {
     AlsHuber &h = c->als_huber[which];
     const int64_t nnz = c->wm_sp[which][0].nnz;
     const size_t vbytes = std::max<size_t>(16, (size_t)nnz * sizeof(float));
-    std::vector<float> tt;
-    CHK(als_transposed_targets(c, which, tt));
-    CHK(dev_alloc(c, (void **)&h.tt1, vbytes, false));
-    if (nnz) HIPCHK(hipMemcpyAsync(h.tt1, tt.data(), (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream)); // the host vector may go
+    h.logit = logit;
+    if (!logit) {
+        std::vector<float> tt;
+        CHK(als_transposed_targets(c, which, tt));
+        CHK(dev_alloc(c, (void **)&h.tt1, vbytes, false));
+        if (nnz) HIPCHK(hipMemcpyAsync(h.tt1, tt.data(), (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream)); // the host vector may go
+    }
     for (int t = 0; t < 2; ++t) {
         WCsrDev &M = c->wm_sp[which][t];
         CHK(dev_alloc(c, (void **)&M.hw, vbytes));
@@ -154,9 +158,14 @@ static int als_huber_build(cmf_ctx *c, int which) {
     }
     return CMF_OK;
 }
-static int als_huber_ensure(cmf_ctx *c, int which) {
-    if (c->als_huber[which].ready) return CMF_OK;
-    const int rc = als_huber_build(c, which);
+// (a relation takes a Huber loss or a logistic one, never both at once: what the other loss built for the pattern is dropped first)
+static int als_huber_ensure(cmf_ctx *c, int which, bool logit = false) {
+    if (c->als_huber[which].ready && c->als_huber[which].logit == logit) return CMF_OK;
+    if (c->als_huber[which].ready) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        als_huber_free(c, which);
+    }
+    const int rc = als_huber_build(c, which, logit);
     if (rc != CMF_OK) {
         (void)hipStreamSynchronize(c->stream);
         als_huber_free(c, which);
@@ -222,9 +231,13 @@ static int als_huber_loss_side(cmf_ctx *c, int which, double *out) {
     return CMF_OK;
 }
 
+// (cmf_als_logit_pass.hip.h, which stands below: hw of one image of a passed logistic relation from the current factors)
+static int als_logit_pass_refresh(cmf_ctx *c, int which, int t);
+
 // The Huber sides of one sweep, bound for its duration: bind() refreshes hw / hp of every Huber image the sweep reads, in the
 // sweep's orientation, from the current factors, and als_side_weights / als_side_targets return them until the scope ends.  Nothing
-// outside a sweep ever sees them: the residual, the bias targets and the losses read the images as they were bound.
+// outside a sweep ever sees them: the residual, the bias targets and the losses read the images as they were bound.  A logistic
+// relation under cmf_set_logit_pass is bound in the same way, behind its own pass.
 struct AlsHuberGuard {
     cmf_ctx *const c;
     WCsrDev *bound[2] = {nullptr, nullptr};
@@ -232,8 +245,10 @@ struct AlsHuberGuard {
     int bind(const AlsSweep &sw) {
         for (int s = 0; s < sw.nrel; ++s) {
             const AlsRel &r = sw.rel[s];
-            if (!sw.observed[s] || !als_huber_rel(c, r.which)) continue;
-            CHK(als_huber_refresh(c, r.which, r.t));
+            if (!sw.observed[s]) continue;
+            if (als_huber_rel(c, r.which)) CHK(als_huber_refresh(c, r.which, r.t));
+            else if (als_logit_passed(c, r.which)) CHK(als_logit_pass_refresh(c, r.which, r.t));
+            else continue;
             bound[s] = &c->wm_sp[r.which][r.t];
             bound[s]->hbound = true;
         }

@@ -76,11 +76,17 @@ __global__ void als_logit_sum_kernel(const double *part, int64_t n, double *out)
 enum { ALS_LOGIT_LOSS_PIECE = 2048 };
 
 static bool als_logit_rel(const cmf_ctx *c, int which) { return c->rel_loss[which] == CMF_LOSS_LOGISTIC; }
+// A logistic relation is reweighted in one of two places: inside als_normal_kernel<KP, true> (FUSED, the default: the formed routes
+// only), or by a pass of its own in front of every sweep (PASSED, cmf_set_logit_pass, cmf_als_logit_pass.hip.h), after which every
+// route reads it as a Frobenius relation under w kappa and w (t - 1/2).  For routing and for the refusals of the routes without
+// formed systems a passed relation is therefore not a logistic one.
+static bool als_logit_passed(const cmf_ctx *c, int which) { return als_logit_rel(c, which) && c->als_logit_pass[which]; }
+static bool als_logit_fused(const cmf_ctx *c, int which) { return als_logit_rel(c, which) && !c->als_logit_pass[which]; }
 
-// does the sweep of factor f read a logistic relation?
+// does the sweep of factor f read a fused logistic relation?
 static bool als_logit_sweep(const cmf_ctx *c, const AlsSweep &sw) {
     for (int s = 0; s < sw.nrel; ++s)
-        if (als_logit_rel(c, sw.rel[s].which)) return true;
+        if (als_logit_fused(c, sw.rel[s].which)) return true;
     return false;
 }
 
@@ -90,7 +96,8 @@ static bool als_logit_swept(const cmf_ctx *c, int mask) {
 }
 
 // What a step that sweeps a logistic relation cannot do: the relation must be observed (CSR weights), without a background weight and
-// without biases.  cg: the entry point asked for the conjugate-gradient route, which has no reweighting pass.
+// without biases, fused or passed.  cg: the entry point asked for the conjugate-gradient route, which has no reweighting pass of its
+// own: a fused relation is refused there.
 static int als_logit_check(cmf_ctx *c, const char *what, int mask, bool cg = false) {
     for (int w = 0; w < 2; ++w) {
         const bool swept = w == 0 ? (mask & (CMF_UPD_U | CMF_UPD_V)) != 0 : (mask & (CMF_UPD_Z | CMF_UPD_V)) != 0;
@@ -102,7 +109,7 @@ static int als_logit_check(cmf_ctx *c, const char *what, int mask, bool cg = fal
         if (c->wm_bg[w] > 0.0)
             return fail(CMF_EUNSUPPORTED, "%s: %s has a logistic loss and a background weight; the logistic loss over the cells outside the pattern is not built", what, nm);
         if (c->als_bias[w].on) return fail(CMF_EUNSUPPORTED, "%s: %s has a logistic loss and biases; biases under a logit link are not built", what, nm);
-        if (cg)
+        if (cg && als_logit_fused(c, w))
             return fail(CMF_EUNSUPPORTED, "%s: %s has a logistic loss; the conjugate-gradient rows have no reweighting pass: use cmf_als_step or cmf_als_nnls_step", what, nm);
     }
     return CMF_OK;

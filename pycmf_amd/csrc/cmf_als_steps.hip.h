@@ -121,7 +121,7 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, AlsPlan &pl, in
     using namespace cmfk;
     const int kp = c->kp;
     const int64_t kk = (int64_t)kp * kp, nslots = (int64_t)pl.first.size() - 1;
-    const bool lg = als_logit_sweep(c, sw);   // a sweep that reads a logistic relation: the LG = true instance of als_normal_kernel
+    const bool lg = als_logit_sweep(c, sw);   // a sweep that reads a fused logistic relation: the LG = true instance of als_normal_kernel
     int64_t max_rows = 0, max_pieces = 0;
     std::vector<int64_t> cuts{0};
     for (int64_t r = 0; r < nslots;) {
@@ -147,7 +147,7 @@ static int als_chunks(cmf_ctx *c, const AlsSweep &sw, double l2, AlsPlan &pl, in
     if (lg) {
         a.F = c->F[sw.f];
         for (int s = 0, o = 0; s < sw.nrel; ++s)
-            if (sw.observed[s]) (o++ == 0 ? a.logit0 : a.logit1) = als_logit_rel(c, sw.rel[s].which) ? 1 : 0;
+            if (sw.observed[s]) (o++ == 0 ? a.logit0 : a.logit1) = als_logit_fused(c, sw.rel[s].which) ? 1 : 0;
     }
     for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
         const int64_t c0 = cuts[ci], c1 = cuts[ci + 1], nr = c1 - c0, row0 = pl.row0 + c0;
@@ -668,7 +668,8 @@ static int als_dual_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_be
 //   dual_max > 0     an exact row sweep without a shared term or a logistic relation solves its rows of 1 .. dual_max entries in dual form
 //   biases           biases are bound: the adjusted targets are refreshed before the sweeps and the bias blocks swept after them
 // A relation under a Huber loss (cmf_als_huber.hip.h) is no option of a step: every sweep that reads one runs the reweighting pass
-// first and its route, whichever it is, reads the effective weights and products for the sweep's duration (AlsHuberGuard).
+// first and its route, whichever it is, reads the effective weights and products for the sweep's duration (AlsHuberGuard).  So does a
+// logistic relation under cmf_set_logit_pass (cmf_als_logit_pass.hip.h), which the routes then take for a Frobenius one.
 struct AlsStepOpts { int nn_sweeps = 0, cg_steps = 0, nn_cg_steps = 0, dual_max = 0; bool biases = false; };
 
 enum AlsRoute { ALS_SHARED_EXACT, ALS_SHARED_HALS, ALS_ROWS_EXACT, ALS_ROWS_NNLS, ALS_ROWS_CG, ALS_ROWS_NNCG, ALS_ROWS_DUAL };
@@ -694,7 +695,7 @@ static int als_step(cmf_ctx *c, const char *what, double l2, int nn_mask, int ma
         if (!(mask & bits[s]) || c->frows[f] <= 0) continue;
         const bool nn = (nn_mask & nnb[s]) != 0;
         const AlsSweep sw = als_sweep(c, f);
-        AlsHuberGuard huber(c);   // the Huber sides of this sweep: refreshed from the current factors, bound until the sweep is over
+        AlsHuberGuard huber(c);   // the Huber and passed-logistic sides of this sweep: refreshed from the current factors, bound until it is over
         CHK(huber.bind(sw));
         switch (als_route(als_observed(sw), als_shared_present(c, sw), als_logit_sweep(c, sw), c->kp, nn, o)) {
         case ALS_SHARED_EXACT: CHK(als_sweep_shared(c, what, sw, l2, nn)); break;
@@ -754,12 +755,12 @@ static int als_dual_max_ok(const char *what, int dual_max) {
     return CMF_OK;
 }
 
-// What the non-negative CG rows cannot sweep: a logistic relation (no reweighting pass) and a relation with biases bound
+// What the non-negative CG rows cannot sweep: a fused logistic relation (no reweighting pass) and a relation with biases bound
 static int als_nncg_sweep_ok(cmf_ctx *c, const char *what, const AlsSweep &sw) {
     for (int s = 0; s < sw.nrel; ++s) {
         const int w = sw.rel[s].which;
         const char *nm = w == 0 ? "X" : "Y";
-        if (als_logit_rel(c, w))
+        if (als_logit_fused(c, w))
             return fail(CMF_EUNSUPPORTED, "%s: %s has a logistic loss; the non-negative conjugate-gradient rows have no reweighting pass: use cmf_als_nnls_step", what, nm);
         if (c->als_bias[w].on)
             return fail(CMF_EUNSUPPORTED, "%s: %s has biases bound; the non-negative conjugate-gradient rows under biases are not built: use cmf_als_bias_step", what, nm);

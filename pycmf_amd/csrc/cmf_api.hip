@@ -92,7 +92,8 @@ struct WCsrDev {
     float *pv = nullptr, *wv = nullptr, *tv = nullptr;
     float *ev = nullptr;   // excess weights w - c0 under a background weight (cmf_als_bg.hip.h), or null
     float *bt = nullptr, *bp = nullptr; // adjusted targets t - mu - r_i - c_j and w times them under biases (cmf_als_bias.hip.h), or null
-    float *hw = nullptr, *hp = nullptr; // effective weights w omega and products under a Huber loss (cmf_als_huber.hip.h), or null; hbound:
+    float *hw = nullptr, *hp = nullptr; // effective weights w omega and products under a Huber loss (cmf_als_huber.hip.h), or w kappa and
+                                        // w t - w / 2 under the logistic pass (cmf_als_logit_pass.hip.h), or null; hbound:
     bool hbound = false;                // ... a sweep has them bound: the row kernels read them (AlsHuberGuard)
     int64_t rows = 0, cols = 0, nnz = 0;
 };
@@ -116,6 +117,7 @@ struct AlsBias {
 struct AlsHuber {
     double delta = 0.0;               // 0: none
     bool ready = false;
+    bool logit = false;               // built for the logistic pass (cmf_als_logit_pass.hip.h): no tt1, hp written once at the build
     float *tt1 = nullptr;
     cmfk::AlsBiasPiece *pieces[2] = {nullptr, nullptr};
     int64_t npieces[2] = {0, 0};
@@ -206,6 +208,7 @@ struct cmf_ctx {
     double wm_bg[2] = {0.0, 0.0};         // background weight c0 of X / Y on the cells outside a CSR pattern (cmf_als_bg.hip.h; 0: none)
     DevBuf als_bg_s, als_bg64;            // ... the shared matrix sum coef Gram of a sweep; float64 Grams of the error's trace term
     int rel_loss[2] = {0, 0};             // loss of X / Y under the ALS steps (cmf_als_logit.hip.h): CMF_LOSS_FROBENIUS | CMF_LOSS_LOGISTIC
+    bool als_logit_pass[2] = {false, false}; // a logistic X / Y is reweighted by a pass in front of every sweep (cmf_set_logit_pass), not in als_normal_kernel
     AlsBias als_bias[2];                  // mu and row / column biases of X / Y (cmf_als_bias.hip.h; off: none)
     AlsHuber als_huber[2];                // Huber loss of X / Y under the ALS steps (cmf_als_huber.hip.h; delta 0: none)
     int opt_als_bias_piece = 0;           // ... stored entries per piece of a row in the bias passes (0: the default, 2048; > 0 rounded up to 16; < 0: every row is one piece)
@@ -915,6 +918,7 @@ static void release_problem(cmf_ctx *c) {
         c->als_bias[w] = AlsBias();
         c->als_huber[w] = AlsHuber();
         c->rel_loss[w] = 0;
+        c->als_logit_pass[w] = false;
         c->wm_bg[w] = 0.0;
         c->wm_kind[w] = 0; c->wm_w[w] = c->wm_p[w] = nullptr;
         c->wm_sp[w][0] = WCsrDev(); c->wm_sp[w][1] = WCsrDev();
@@ -2042,4 +2046,5 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_als_bg.hip.h"      // background weights, the shared terms of a sweep
 #include "cmf_als_logit.hip.h"   // relation losses
 #include "cmf_als_huber.hip.h"   // the Huber loss: the reweighting pass in front of a sweep
+#include "cmf_als_logit_pass.hip.h"   // the logistic loss by such a pass (cmf_set_logit_pass): every route
 #include "cmf_als_steps.hip.h"   // the chunk loop, the routes, als_step and every step entry point

@@ -13,7 +13,7 @@ from sklearn.utils import check_array
 
 from .factor_init import initialize_mf, init_custom, DeviceOperand, DEVICE_SVD_MIN_CELLS
 from .solver_shell import (HipMUSolver, HipNewtonSolver, HipHALSSolver, HipALSSolver, check_loss, check_kl_data, check_beta, check_beta_extras, check_beta_data, check_entry_weights, check_hals,
-                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_als_nn_cg_steps, check_als_dual_max, check_als_l2_scale, check_background_weight, check_huber_delta, check_biases, check_bias_l2, check_logistic)
+                           check_als, check_als_nn_sweeps, check_als_cg_steps, check_als_nn_cg_steps, check_als_dual_max, check_als_l2_scale, check_als_logit_pass, check_background_weight, check_huber_delta, check_biases, check_bias_l2, check_logistic)
 from .topic_terms import print_topic_terms_from_matrix, print_topic_terms_with_importances
 
 _BETA_NAMES = {'frobenius': 2, 'kullback-leibler': 1, 'itakura-saito': 0}
@@ -44,7 +44,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                     x_entry_weights=None, y_entry_weights=None, als_nn_sweeps=0, als_cg_steps=0,
                                     x_background_weight=0.0, y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None,
                                     _x_bias_init=None, _y_bias_init=None, als_nn_cg_steps=0, als_dual_max=0, als_l2_scale=0.0,
-                                    x_huber_delta=None, y_huber_delta=None):
+                                    x_huber_delta=None, y_huber_delta=None, als_logit_pass=False):
     """Factorise X ~ f(U V^T) and Y ~ f(V Z^T) with a shared V on an MI355X.
 
     Same contract as the reference function (pycmf/cmf.py:215-456): returns
@@ -141,11 +141,18 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
     preceded by one reweighting pass and then runs the route the other ALS keywords name (``HipALSSolver``).  ``ValueError`` before
     any device is touched: a bool, a non-finite or non-positive value; another solver; ``n_gpus > 1``; entry weights of that
     relation that are not a SciPy sparse W or ``'observed'``; a logit link or a background weight on it.
+
+    ``als_logit_pass``: False | True (``solver='als'``, ``loss='logistic'`` and ``n_gpus=1`` only; ``ValueError`` otherwise) -- the
+    logistic relations are reweighted by a pass of their own in front of every sweep instead of inside the normal-equation kernel,
+    so that ``als_cg_steps``, ``als_nn_cg_steps`` and ``als_dual_max`` honour the logistic loss too (``HipALSSolver``): the
+    matrix-free routes for logistic factorisation at large k.  Without it those keywords are refused under ``loss='logistic'`` (or,
+    ``als_dual_max``, leave the logistic sweeps to the exact rows) as before.
     """
     if n_components is None:
         n_components = max(X.shape[1], Y.shape[1])
     _check_beta_loss(beta_loss)
     check_loss(loss, solver, n_gpus)
+    als_logit_pass = check_als_logit_pass(als_logit_pass, solver, n_gpus, loss)
     if loss == "beta-divergence":
         beta = check_beta(beta_loss)
         check_beta_extras(x_entry_weights, y_entry_weights, x_background_weight, y_background_weight, x_biases, y_biases)
@@ -155,7 +162,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                                                  (Z_non_negative, update_Z)) if upd])
     check_als_nn_cg_steps(als_nn_cg_steps, solver, [nn for nn, upd in ((U_non_negative, update_U), (V_non_negative, update_V),
                                                                        (Z_non_negative, update_Z)) if upd],
-                          n_gpus, loss, bool(x_biases) or bool(y_biases))
+                          n_gpus, loss, bool(x_biases) or bool(y_biases), als_logit_pass)
     check_als_dual_max(als_dual_max, solver, n_gpus, als_cg_steps)
     als_l2_scale = check_als_l2_scale(als_l2_scale, solver, n_gpus)
     x_background_weight = check_background_weight(x_background_weight, "x", solver, x_entry_weights)
@@ -188,7 +195,8 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
         raise ValueError("No such link %s for y_link" % y_link)
     if loss == "logistic":
         check_logistic(x_link, y_link, x_entry_weights, y_entry_weights, als_cg_steps, x_background_weight, y_background_weight, x_biases,
-                       y_biases, have_x=X is not None and (update_U or update_V), have_y=Y is not None and (update_Z or update_V))
+                       y_biases, have_x=X is not None and (update_U or update_V), have_y=Y is not None and (update_Z or update_V),
+                       logit_pass=als_logit_pass)
 
     # ---- solver dispatch (cmf.py:433-453)
     common = dict(max_iter=max_iter, tol=tol, verbose=verbose, update_U=update_U, update_V=update_V,
@@ -225,7 +233,7 @@ def collective_matrix_factorization(X, Y, U=None, V=None, Z=None,
                                      x_background_weight=x_background_weight, y_background_weight=y_background_weight,
                                      x_biases=x_biases, y_biases=y_biases, bias_l2=bias_l2, x_bias_init=_x_bias_init,
                                      y_bias_init=_y_bias_init, nn_cg_steps=als_nn_cg_steps, dual_max=als_dual_max, l2_scale=als_l2_scale,
-                                     x_huber_delta=x_huber_delta, y_huber_delta=y_huber_delta, **common)
+                                     x_huber_delta=x_huber_delta, y_huber_delta=y_huber_delta, logit_pass=als_logit_pass, **common)
         solver_object.check_weights(X, Y)
     else:
         raise ValueError("No such solver: %s" % solver)
@@ -407,10 +415,17 @@ class CMF(BaseEstimator, TransformerMixin):
     ``(L_x, L_y)`` after a fit (None without a delta), and ``transform`` folds new rows in under the same loss.  ``predict``,
     ``score_entries``, ``top_n``, ``ranks`` and ``evaluate`` read the fitted factors as always.  Keyword-only OPTIONS like
     ``als_nn_cg_steps``.
+
+    ``als_logit_pass`` (``solver='als'`` with ``loss='logistic'`` only, default False): True reweights the logistic relations by a
+    pass in front of every sweep, so that ``als_cg_steps``, ``als_nn_cg_steps`` and ``als_dual_max`` fit them too
+    (``collective_matrix_factorization``): ``CMF(solver="als", loss="logistic", x_link="logit", l2_reg=0.5, als_logit_pass=True,
+    als_cg_steps=6, U_non_negative=False, V_non_negative=False, Z_non_negative=False)``.  ``transform`` honours it;
+    ``logistic_loss_``, ``reconstruction_err_`` and the stopping test are unchanged.  A keyword-only OPTION like ``als_nn_cg_steps``.
     """
 
     # keyword-only options outside get_params(): name -> default
-    _OPTIONS = {"als_nn_cg_steps": 0, "als_dual_max": 0, "als_l2_scale": 0.0, "x_huber_delta": None, "y_huber_delta": None}
+    _OPTIONS = {"als_nn_cg_steps": 0, "als_dual_max": 0, "als_l2_scale": 0.0, "x_huber_delta": None, "y_huber_delta": None,
+                "als_logit_pass": False}
 
     def __init__(self, n_components=None, x_init=None, y_init=None, solver='mu', alpha='auto',
                  beta_loss='frobenius', tol=1e-4, max_iter=600,
@@ -478,7 +493,7 @@ class CMF(BaseEstimator, TransformerMixin):
                     sg_sample_ratio=self.sg_sample_ratio, device=self.device, sg_sampler=self.sg_sampler,
                     loss=self.loss, als_nn_sweeps=self.als_nn_sweeps, als_cg_steps=self.als_cg_steps,
                     als_nn_cg_steps=self.als_nn_cg_steps, als_dual_max=self.als_dual_max, als_l2_scale=self.als_l2_scale,
-                    x_huber_delta=self.x_huber_delta, y_huber_delta=self.y_huber_delta)
+                    x_huber_delta=self.x_huber_delta, y_huber_delta=self.y_huber_delta, als_logit_pass=self.als_logit_pass)
 
     def fit_transform(self, X, Y, U=None, V=None, Z=None, x_entry_weights=None, y_entry_weights=None, x_background_weight=0.0,
                       y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None):

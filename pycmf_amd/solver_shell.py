@@ -66,17 +66,19 @@ def check_kl_data(X, Y):
 
 
 def check_logistic(x_link="linear", y_link="linear", x_entry_weights="observed", y_entry_weights="observed", als_cg_steps=0,
-                   x_background_weight=0.0, y_background_weight=0.0, x_biases=False, y_biases=False, have_x=True, have_y=True):
+                   x_background_weight=0.0, y_background_weight=0.0, x_biases=False, y_biases=False, have_x=True, have_y=True,
+                   logit_pass=False):
     """What ``loss='logistic'`` (solver='als') cannot do, refused before any device is touched.  The relations whose link is 'logit'
     are the logistic ones: at least one must be; each needs entry weights that resolve to a CSR pattern (a SciPy sparse W or
-    'observed' -- ``have_x`` / ``have_y``: the relation is part of the call), and takes no conjugate-gradient rows, no background
-    weight and no biases.  Returns (x is logistic, y is logistic)."""
+    'observed' -- ``have_x`` / ``have_y``: the relation is part of the call), and takes no conjugate-gradient rows (unless
+    ``logit_pass``: the reweighting pass in front of every sweep, ``als_logit_pass``), no background weight and no biases.  Returns
+    (x is logistic, y is logistic)."""
     import scipy.sparse as sp
     logit = (x_link == "logit", y_link == "logit")
     if not any(logit):
         raise ValueError("loss='logistic' fits the relations whose link is 'logit': x_link or y_link must be 'logit', got x_link=%r, "
                          "y_link=%r" % (x_link, y_link))
-    if als_cg_steps:
+    if als_cg_steps and not logit_pass:
         raise ValueError("als_cg_steps=%r with loss='logistic' is not built (the conjugate-gradient rows have no reweighting pass): "
                          "als_cg_steps must be 0; use the exact rows or als_nn_sweeps" % (als_cg_steps,))
     for name, on, have, W, c0, biases in (("x", logit[0], have_x, x_entry_weights, x_background_weight, x_biases),
@@ -765,10 +767,11 @@ def check_als_cg_steps(als_cg_steps, solver="als", updated_non_negative=None):
                          "(U/V/Z_non_negative=True is the default): pass *_non_negative=False, or use als_nn_sweeps" % (als_cg_steps,))
 
 
-def check_als_nn_cg_steps(als_nn_cg_steps, solver="als", updated_non_negative=None, n_gpus=1, loss="frobenius", biases=False):
+def check_als_nn_cg_steps(als_nn_cg_steps, solver="als", updated_non_negative=None, n_gpus=1, loss="frobenius", biases=False,
+                          logit_pass=False):
     """``als_nn_cg_steps``: an integer 0 .. 1024; non-zero with solver='als' on one GPU only, only when some updated factor is
-    non-negative (``updated_non_negative`` as in ``check_als_cg_steps``), and not with ``loss='logistic'`` or biases.  No device is
-    touched."""
+    non-negative (``updated_non_negative`` as in ``check_als_cg_steps``), and not with ``loss='logistic'`` (unless ``logit_pass``:
+    ``als_logit_pass``) or biases.  No device is touched."""
     if isinstance(als_nn_cg_steps, (bool, np.bool_)) or not isinstance(als_nn_cg_steps, (numbers.Integral, np.integer)):
         raise ValueError("als_nn_cg_steps must be an integer 0 .. 1024, got %r" % (als_nn_cg_steps,))
     if als_nn_cg_steps < 0 or als_nn_cg_steps > 1024:
@@ -783,7 +786,7 @@ def check_als_nn_cg_steps(als_nn_cg_steps, solver="als", updated_non_negative=No
     if updated_non_negative is not None and not any(updated_non_negative):
         raise ValueError("als_nn_cg_steps=%r acts on non-negative factors only, and every factor this call updates is signed: "
                          "pass *_non_negative=True, or use als_cg_steps" % (als_nn_cg_steps,))
-    if loss == "logistic":
+    if loss == "logistic" and not logit_pass:
         raise ValueError("als_nn_cg_steps=%r with loss='logistic' is not built (the conjugate-gradient rows have no reweighting pass): "
                          "als_nn_cg_steps must be 0; use als_nn_sweeps" % (als_nn_cg_steps,))
     if biases:
@@ -807,6 +810,22 @@ def check_als_dual_max(als_dual_max, solver="als", n_gpus=1, als_cg_steps=0):
     if als_cg_steps:
         raise ValueError("als_dual_max=%r together with als_cg_steps=%r: conjugate gradients already take every sweep the dual rows "
                          "could (signed factors with entry weights): one of the two must be 0" % (als_dual_max, als_cg_steps))
+
+
+def check_als_logit_pass(als_logit_pass, solver="als", n_gpus=1, loss="logistic"):
+    """``als_logit_pass``: a bool; True with solver='als', loss='logistic' and one GPU only.  No device is touched.  Returns the bool."""
+    if not isinstance(als_logit_pass, (bool, np.bool_)):
+        raise ValueError("als_logit_pass must be True or False, got %r" % (als_logit_pass,))
+    if not als_logit_pass:
+        return False
+    if solver != "als":
+        raise ValueError("als_logit_pass is the reweighting pass of solver='als' under loss='logistic': it must be False with solver=%r" % (solver,))
+    if loss != "logistic":
+        raise ValueError("als_logit_pass=True reweights the logistic relations in front of every sweep: it needs loss='logistic', got "
+                         "loss=%r" % (loss,))
+    if n_gpus != 1:
+        raise ValueError("als_logit_pass=True runs on one GPU: n_gpus must be 1, got %r (the sharded form is not built)" % (n_gpus,))
+    return True
 
 
 def check_als_l2_scale(als_l2_scale, solver="als", n_gpus=1):
@@ -980,7 +999,10 @@ class HipALSSolver(HipMUSolver):
     with signed factors, and with non-negative ones under ``nn_sweeps > 0``.  The error metric -- the stopping test and
     ``reconstruction_error`` -- then takes from a logistic relation its cross-entropy SUM (not a root) and from a Frobenius
     relation what it takes without this keyword; ``logistic_loss`` holds ``(L_x, L_y)`` of the last evaluation (0 for a Frobenius
-    relation).
+    relation).  ``logit_pass=True`` moves the reweighting out of the normal-equation kernel into a pass of its own in front of every
+    sweep that reads a logistic relation (``cmf_set_logit_pass``): ``cg_steps``, ``nn_cg_steps`` and ``dual_max`` are then accepted
+    and honour the loss, with the same descent statements (conjugate gradients, projected or not, start at the current row and never
+    raise the bound; the dual rows are exact).  ``l2_scale`` keeps counting the original weights.  The error metric is unchanged.
 
     Under ``loss='frobenius'`` it ignores alpha and the links, like MU.  The error metric is the one of a weighted MU fit,
     sqrt(sum wx e^2) + sqrt(sum wy e^2); the loop stays on the host (``cmf_run`` knows the MU and Newton steps only)."""
@@ -989,14 +1011,16 @@ class HipALSSolver(HipMUSolver):
 
     def __init__(self, *args, x_entry_weights=None, y_entry_weights=None, nn_sweeps=0, cg_steps=0, x_background_weight=0.0,
                  y_background_weight=0.0, x_biases=False, y_biases=False, bias_l2=None, x_bias_init=None, y_bias_init=None,
-                 loss="frobenius", nn_cg_steps=0, dual_max=0, l2_scale=0.0, x_huber_delta=None, y_huber_delta=None, **kwargs):
+                 loss="frobenius", nn_cg_steps=0, dual_max=0, l2_scale=0.0, x_huber_delta=None, y_huber_delta=None, logit_pass=False,
+                 **kwargs):
         check_loss(loss, "als")
+        self.logit_pass = check_als_logit_pass(logit_pass, "als", 1, loss)
         self.l2_scale = check_als_l2_scale(l2_scale)
         self.l2_multipliers = None           # (m_U, m_V, m_Z) of the bound problem under l2_scale > 0
         check_als(loss=loss)
         check_als_nn_sweeps(nn_sweeps)
         check_als_cg_steps(cg_steps)
-        check_als_nn_cg_steps(nn_cg_steps, loss=loss, biases=bool(x_biases) or bool(y_biases))
+        check_als_nn_cg_steps(nn_cg_steps, loss=loss, biases=bool(x_biases) or bool(y_biases), logit_pass=self.logit_pass)
         check_als_dual_max(dual_max, als_cg_steps=cg_steps)
         self.x_background_weight = check_background_weight(x_background_weight, "x", "als", x_entry_weights)
         self.y_background_weight = check_background_weight(y_background_weight, "y", "als", y_entry_weights)
@@ -1015,7 +1039,8 @@ class HipALSSolver(HipMUSolver):
         self._logit = (False, False)
         if loss == "logistic":
             self._logit = check_logistic(self.x_link, self.y_link, x_entry_weights, y_entry_weights, cg_steps, self.x_background_weight,
-                                         self.y_background_weight, self.x_biases, self.y_biases, have_x=False, have_y=False)
+                                         self.y_background_weight, self.x_biases, self.y_biases, have_x=False, have_y=False,
+                                         logit_pass=self.logit_pass)
         self.logistic_loss = None            # (L_x, L_y) of the last error evaluation under loss='logistic'
         # (the relations that take part in a call are checked again when it resolves its weights: a fold-in binds one of them)
         self.x_huber_delta = check_huber_delta(x_huber_delta, "x", "als", 1, x_entry_weights, self.x_link, self.x_background_weight, have=False)
@@ -1028,7 +1053,7 @@ class HipALSSolver(HipMUSolver):
 
     def _weights_key(self):
         return (super()._weights_key() + (self.x_background_weight, self.y_background_weight, self.x_biases, self.y_biases) + tuple(self._logit)
-                + (self.l2_scale, self.x_huber_delta, self.y_huber_delta))
+                + (self.l2_scale, self.x_huber_delta, self.y_huber_delta, self.logit_pass))
 
     def _bias_l2(self):
         return self.bias_l2 if self.bias_l2 is not None else float(self.l2_reg)
@@ -1051,7 +1076,8 @@ class HipALSSolver(HipMUSolver):
             raw = super()._resolve_weights(X, Y)
             if any(self._logit):   # a logistic relation that is part of the call: sparse weights, targets in [0, 1]
                 check_logistic(self.x_link, self.y_link, self.x_entry_weights, self.y_entry_weights, self.cg_steps, self.x_background_weight,
-                               self.y_background_weight, self.x_biases, self.y_biases, have_x=X is not None, have_y=Y is not None)
+                               self.y_background_weight, self.x_biases, self.y_biases, have_x=X is not None, have_y=Y is not None,
+                               logit_pass=self.logit_pass)
                 for on, ew, nm in ((self._logit[0], raw[0], "X"), (self._logit[1], raw[1], "Y")):
                     if on and ew is not None:
                         check_logistic_data(ew.t, nm)
@@ -1088,6 +1114,8 @@ class HipALSSolver(HipMUSolver):
             for which, M in ((0, X), (1, Y)):
                 if self._logit[which] and M is not None:
                     ctx.set_relation_loss(which, "logistic")
+                    if self.logit_pass:   # every route of the step then honours the loss (cmf_set_logit_pass)
+                        ctx.set_logit_pass(which, True)
             for which, M, delta in ((0, X, self.x_huber_delta), (1, Y, self.y_huber_delta)):
                 if delta and M is not None:
                     ctx.set_huber_delta(which, delta)
@@ -1111,7 +1139,7 @@ class HipALSSolver(HipMUSolver):
         check_als(l1_reg, l2_reg)
         if self.dual_max:      # (never with cg_steps: check_als_dual_max; the bias blocks follow inside the call)
             self._ctx.als_dual_step(l2_reg, self._nn_mask(), self._update_mask(), self.dual_max, self.nn_sweeps, self.nn_cg_steps)
-        elif self.nn_cg_steps:   # (never with biases or a logistic relation: check_als_nn_cg_steps)
+        elif self.nn_cg_steps:   # (never with biases, or a logistic relation without logit_pass: check_als_nn_cg_steps)
             self._ctx.als_nncg_step(l2_reg, self._nn_mask(), self._update_mask(), self.cg_steps, self.nn_cg_steps, self.nn_sweeps)
         elif self.x_biases or self.y_biases:
             self._ctx.als_bias_step(l2_reg, self._nn_mask(), self._update_mask(), self.cg_steps, self.nn_sweeps)
