@@ -608,7 +608,7 @@ int cmf_set_relation_loss(cmf_ctx *ctx, int which, int kind);
 int cmf_get_relation_loss(cmf_ctx *ctx, int which, int *kind);
 int cmf_als_logistic_loss(cmf_ctx *ctx, double *lx, double *ly);
 
-/* ---- ALS with a Huber loss on an observed relation (csrc/cmf_als_huber.hip.h) ----
+/* ---- ALS with a Huber loss on an observed relation (csrc/cmf_als_reweight.hip.h) ----
  * A relation with CSR weights may be fitted under  sum_O w rho_d(t - a . b),  rho_d(r) = r^2 / 2 for |r| <= d and d (|r| - d / 2)
  * beyond: a stored entry far off the model pulls its row and its column with a bounded force.  The half-quadratic majoriser
  * rho_d(r) <= rho_d(r0) + omega(r0) (r^2 - r0^2) / 2, omega(r) = min(1, d / |r|), tight at the residual r0 under the CURRENT row,
@@ -642,7 +642,7 @@ int cmf_get_huber_delta(cmf_ctx *ctx, int which, double *delta);
 int cmf_als_huber_loss(cmf_ctx *ctx, double *lx, double *ly);
 int cmf_als_huber_weights(cmf_ctx *ctx, int which, int t, int64_t nnz, float *w_eff, float *p_eff);
 
-/* ---- ALS with a logistic loss on every route: the reweighting as a pass of its own (csrc/cmf_als_logit_pass.hip.h) ----
+/* ---- ALS with a logistic loss on every route: the reweighting as a pass of its own (csrc/cmf_als_reweight.hip.h) ----
  * By default a logistic relation (cmf_set_relation_loss) is reweighted inside the normal-equation kernel, so only the routes that
  * form the k x k systems honour it.  Under this flag the relation is reweighted like a Huber one instead: ONE pass
  * (als_logit_pass_kernel) in front of every sweep writes  w kappa(xi)  per stored entry of the image the sweep reads, xi the score

@@ -93,10 +93,10 @@ __global__ __launch_bounds__(256) void als_bg_dot64_kernel(const double *a, cons
 #ifdef CMF_ALS_HOST
 
 // the weights the row kernels read for an observed side: the excess w - c0 under a background, w itself otherwise -- or, while a
-// sweep has the Huber arrays of the image bound (AlsHuberGuard, cmf_als_huber.hip.h), w omega
+// sweep has the reweighted arrays of the image bound (AlsReweightGuard, cmf_als_reweight.hip.h), the effective weights hw
 static const float *als_side_weights(const WCsrDev &M) { return M.hbound ? M.hw : (M.ev ? M.ev : M.wv); }
-// the products w t they read: w times the adjusted targets under biases (cmf_als_bias.hip.h), p = w t otherwise -- or, bound, those
-// times omega
+// the products w t they read: w times the adjusted targets under biases (cmf_als_bias.hip.h), p = w t otherwise -- or, bound, the
+// effective products hp
 static const float *als_side_targets(const WCsrDev &M) { return M.hbound ? M.hp : (M.bp ? M.bp : M.pv); }
 
 // does the sweep have a shared term (als_shared_terms sets S): a full relation, or an observed one under a background weight

@@ -6,11 +6,10 @@
 // minimiser of its block:   r_i = sum_{j in O_i} w (t - mu - c_j - a_i . b_j) / (sum_{j in O_i} w + lb),   0 for a row without
 // stored entries or with a zero denominator.  What this file adds:
 //   als_bias_piece_kernel<GL>   one 256-thread workgroup per PIECE (at most L consecutive stored entries of one row of a CSR image;
-//                          option "als_bias_piece").  GL = k_pad / 4 lanes gather one row of B, a float4 per lane (the lane layout of
-//                          wmu_res_csr_kernel); the 256 / GL lane groups deal the piece's entries among themselves round-robin, two
-//                          gathers in flight per group.  Per entry the term w (t - mu - other[idx] - a . b) in float32; every group
-//                          sums its terms and its weights in float64; the groups are added in group order and the workgroup writes
-//                          one (num, wsum) pair of doubles.  No group ever walks a whole long row.  512 bytes of static LDS
+//                          option "als_bias_piece"), the walk of cmf_als_entries.hip.h with two gathers in flight per group.  Per
+//                          entry the term w (t - mu - other[idx] - a . b) in float32; every group sums its terms and its weights in
+//                          float64; the groups are added in group order and the workgroup writes one (num, wsum) pair of doubles.
+//                          At most 512 bytes of static LDS
 //   als_bias_combine_kernel  per row: its pieces added in piece order, bias = (float)(num / (wsum + lb)), or 0
 //   als_bias_targets_kernel  bt = ((t - mu) - rowbias[row]) - colbias[idx] and bp = w bt of one image, each operation rounded once in
 //                          float32; one wave per piece (on the transposed image the roles of r and c are swapped by the caller)
@@ -19,75 +18,46 @@
 // Every cross-workgroup sum is a kernel boundary; no atomics, no grid-wide barrier, vector stores only: a repeated call from the
 // same state is bit-identical, and a row's bias depends on the row and on L alone.
 #pragma once
-#include "cmf_kernels.hip.h"
+#include "cmf_als_entries.hip.h"
 
 namespace cmfk {
 
-struct AlsBiasPiece {
-    int64_t beg;   // first stored entry
-    int32_t len;   // 1 .. L
-    int32_t row;   // of the image
-};
-
-struct AlsBiasArgs {
-    const AlsBiasPiece *pieces;
-    const int32_t *idx;
+struct AlsBiasArgs : AlsEntryArgs {
     const float *tv, *wv;
-    const float *A, *B;      // the factor of the image's rows, the gathered factor; pitch kp
     const float *other;      // the bias of the image's columns
     float mu;
-    int kp;
     double *part;            // [pieces][2]: num, wsum
+};
+
+enum { ALS_BIAS_FLIGHT = 2 };   // gathered rows in flight per lane group
+
+// the term w (t - mu - other[idx] - a . b) in float32; sum[0] its sum, sum[1] the weights', in float64 per lane group
+struct AlsBiasBody {
+    const AlsBiasArgs &g;
+    const float *tv, *wv;    // of the piece
+    float t[ALS_BIAS_FLIGHT], w[ALS_BIAS_FLIGHT], o[ALS_BIAS_FLIGHT];
+    double sum[2] = {0.0, 0.0};
+    __device__ __forceinline__ void begin(int64_t beg) { tv = g.tv + beg, wv = g.wv + beg; }
+    __device__ __forceinline__ void load(int j, int q, int32_t col) {
+        t[j] = tv[q];
+        w[j] = wv[q];
+        o[j] = g.other[col];
+    }
+    __device__ __forceinline__ void use(int j, float d, int, bool real) {
+#pragma clang fp contract(off)
+        const float x = w[j] * (((t[j] - g.mu) - o[j]) - d);
+        if (real) {
+            sum[0] += (double)x;
+            sum[1] += (double)w[j];
+        }
+    }
 };
 
 template <int GL>
 __global__ __launch_bounds__(256) void als_bias_piece_kernel(AlsBiasArgs g) {
-#pragma clang fp contract(off)
-    constexpr int NG = 256 / GL;
-    const AlsBiasPiece pc = g.pieces[blockIdx.x];
-    const int gl = threadIdx.x % GL, grp = threadIdx.x / GL;
-    const f32x4 a = *reinterpret_cast<const f32x4 *>(g.A + (int64_t)pc.row * g.kp + 4 * gl);
-    const int32_t *idx = g.idx + pc.beg;
-    const float *tv = g.tv + pc.beg, *wv = g.wv + pc.beg;
-    double num = 0.0, ws = 0.0;
-    // every group runs the same number of rounds (a round past the piece's end reads its last entry again and adds nothing): the
-    // lanes of a wave stay together through group_sum
-    for (int base = 0; base < pc.len; base += 2 * NG) {
-        const int e0 = base + grp, e1 = e0 + NG;
-        const int q0 = min(e0, pc.len - 1), q1 = min(e1, pc.len - 1);
-        const int32_t j0 = idx[q0], j1 = idx[q1];
-        const f32x4 b0 = *reinterpret_cast<const f32x4 *>(g.B + (int64_t)j0 * g.kp + 4 * gl);
-        const f32x4 b1 = *reinterpret_cast<const f32x4 *>(g.B + (int64_t)j1 * g.kp + 4 * gl);
-        const float t0 = tv[q0], t1 = tv[q1], w0 = wv[q0], w1 = wv[q1], o0 = g.other[j0], o1 = g.other[j1];
-        float d0 = a[0] * b0[0] + a[1] * b0[1] + a[2] * b0[2] + a[3] * b0[3];
-        float d1 = a[0] * b1[0] + a[1] * b1[1] + a[2] * b1[2] + a[3] * b1[3];
-        d0 = group_sum<GL>(d0);
-        d1 = group_sum<GL>(d1);
-        const float x0 = w0 * (((t0 - g.mu) - o0) - d0), x1 = w1 * (((t1 - g.mu) - o1) - d1);
-        if (e0 < pc.len) {
-            num += (double)x0;
-            ws += (double)w0;
-        }
-        if (e1 < pc.len) {
-            num += (double)x1;
-            ws += (double)w1;
-        }
-    }
-    __shared__ double red[2][NG];
-    if (gl == 0) {
-        red[0][grp] = num;
-        red[1][grp] = ws;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double n = red[0][0], w = red[1][0];
-        for (int q = 1; q < NG; ++q) {
-            n += red[0][q];
-            w += red[1][q];
-        }
-        g.part[2 * (int64_t)blockIdx.x] = n;
-        g.part[2 * (int64_t)blockIdx.x + 1] = w;
-    }
+    AlsBiasBody body{g};
+    als_entry_walk<GL, ALS_BIAS_FLIGHT>(g, body);
+    als_group_reduce<GL>(body.sum, g.part + 2 * (int64_t)blockIdx.x);
 }
 
 // first[row] .. first[row + 1]: the pieces of the row
@@ -104,12 +74,12 @@ __global__ __launch_bounds__(256) void als_bias_combine_kernel(const double *par
     bias[row] = (p1 > p0 && den > 0.0) ? (float)(n / den) : 0.f;
 }
 
-__global__ __launch_bounds__(256) void als_bias_targets_kernel(const AlsBiasPiece *pieces, int64_t npieces, const int32_t *idx, const float *tv, const float *wv,
+__global__ __launch_bounds__(256) void als_bias_targets_kernel(const AlsEntryPiece *pieces, int64_t npieces, const int32_t *idx, const float *tv, const float *wv,
                                                                const float *rowbias, const float *colbias, float mu, float *bt, float *bp) {
 #pragma clang fp contract(off)
     const int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (p >= npieces) return;
-    const AlsBiasPiece pc = pieces[p];
+    const AlsEntryPiece pc = pieces[p];
     const float rb = rowbias[pc.row];
     for (int e = threadIdx.x & 63; e < pc.len; e += 64) {
         const int64_t q = pc.beg + e;
@@ -142,8 +112,9 @@ __global__ __launch_bounds__(256) void predict_pairs_kernel(const int64_t *rows,
 
 } // namespace cmfk
 
-// ------------------------------------------------------------------ host side (included by cmf_api.hip behind cmf_als.hip.h; the step
-// that sweeps the biases is als_step, cmf_als_steps.hip.h)
+// ------------------------------------------------------------------ host side (included by cmf_api.hip behind cmf_als_entries.hip.h;
+// the bias sweep itself, which under a Huber loss runs the reweighting pass first, stands behind that pass: als_bias_sweep,
+// cmf_als_steps.hip.h)
 #ifdef CMF_ALS_HOST
 
 enum { ALS_BIAS_PIECE_DEFAULT = 2048 };
@@ -160,23 +131,9 @@ static int als_bias_plan(cmf_ctx *c, int which) {
     AlsBias &b = c->als_bias[which];
     const int64_t L = als_bias_piece_len(c);
     for (int t = 0; t < 2; ++t) {
-        const WCsrDev &M = c->wm_sp[which][t];
-        std::vector<int64_t> ip((size_t)M.rows + 1, 0);
-        HIPCHK(hipMemcpyAsync(ip.data(), M.indptr, ip.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        std::vector<cmfk::AlsBiasPiece> pieces;
-        const std::vector<int64_t> first = als_cut_rows(&ip, 1, M.rows, L, [&](int64_t r, int, int64_t beg, int32_t len) {
-            pieces.push_back(cmfk::AlsBiasPiece{beg, len, (int32_t)r});
-        });
-        if ((int64_t)pieces.size() > INT32_MAX) return fail(CMF_EUNSUPPORTED, "cmf_set_biases: more than 2^31 - 1 pieces (als_bias_piece too small)");
         dev_free(c, b.pieces[t]); dev_free(c, b.first[t]);
         b.pieces[t] = nullptr; b.first[t] = nullptr;
-        CHK(dev_alloc(c, (void **)&b.pieces[t], std::max<size_t>(16, pieces.size() * sizeof(cmfk::AlsBiasPiece)), false));
-        CHK(dev_alloc(c, (void **)&b.first[t], first.size() * sizeof(int64_t), false));
-        if (!pieces.empty()) HIPCHK(hipMemcpyAsync(b.pieces[t], pieces.data(), pieces.size() * sizeof(cmfk::AlsBiasPiece), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(b.first[t], first.data(), first.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream)); // the host vectors may go
-        b.npieces[t] = (int64_t)pieces.size();
+        CHK(als_image_pieces(c, c->wm_sp[which][t], L, "cmf_set_biases", &b.pieces[t], &b.npieces[t], &b.first[t]));
     }
     b.L = L;
     return CMF_OK;
@@ -195,49 +152,11 @@ static int als_bias_refresh(cmf_ctx *c, int which) {
         if (b.npieces[t] == 0) continue;
         Timed tm(c, CMF_K_ELEMWISE);
         hipLaunchKernelGGL(cmfk::als_bias_targets_kernel, dim3((unsigned)((b.npieces[t] + 3) / 4)), dim3(256), 0, c->stream,
-                           (const cmfk::AlsBiasPiece *)b.pieces[t], b.npieces[t], (const int32_t *)M.idx, (const float *)M.tv, (const float *)M.wv,
+                           (const cmfk::AlsEntryPiece *)b.pieces[t], b.npieces[t], (const int32_t *)M.idx, (const float *)M.tv, (const float *)M.wv,
                            (const float *)(t == 0 ? b.r : b.c), (const float *)(t == 0 ? b.c : b.r), (float)b.mu, M.bt, M.bp);
         HIPCHK(hipGetLastError());
     }
     b.dirty = false;
-    return CMF_OK;
-}
-
-// (cmf_als_huber.hip.h, which stands below: a relation under a Huber loss, and hw / hp of one of its images from the current state)
-static bool als_huber_rel(const cmf_ctx *c, int which);
-static int als_huber_rel_ok(cmf_ctx *c, const char *what, int which);
-static int als_huber_refresh(cmf_ctx *c, int which, int t);
-
-// one bias sweep of relation `which` along `axis` (0 rows, 1 columns) into out (device, rows of that image).  Under a Huber loss the
-// block is reweighted like a factor's rows: the pass refreshes the image of that axis at the current factors and biases, and the
-// kernel reads w omega where it reads w.
-static int als_bias_sweep(cmf_ctx *c, int which, int axis, float *out) {
-    AlsBias &b = c->als_bias[which];
-    CHK(als_bias_replan(c, which));
-    const bool huber = als_huber_rel(c, which);
-    if (huber) CHK(als_huber_refresh(c, which, axis));
-    const WCsrDev &M = c->wm_sp[which][axis];
-    const int fa = which == 0 ? (axis == 0 ? CMF_U : CMF_V) : (axis == 0 ? CMF_V : CMF_Z);
-    const int fb = which == 0 ? (axis == 0 ? CMF_V : CMF_U) : (axis == 0 ? CMF_Z : CMF_V);
-    const int64_t np = b.npieces[axis];
-    CHK(ensure_scratch(c, c->als_bias_part, std::max<size_t>(16, (size_t)np * 2 * sizeof(double))));
-    cmfk::AlsBiasArgs a;
-    a.pieces = b.pieces[axis];
-    a.idx = M.idx; a.tv = M.tv; a.wv = huber ? M.hw : M.wv;
-    a.A = c->F[fa]; a.B = c->F[fb];
-    a.other = axis == 0 ? b.c : b.r;
-    a.mu = (float)b.mu;
-    a.kp = c->kp;
-    a.part = (double *)c->als_bias_part.p;
-    Timed tm(c, CMF_K_KLMU, 2.0 * (double)M.nnz * (double)c->kp);
-    if (np > 0) {
-        const dim3 grid((unsigned)np), block(256);
-        ALS_LAUNCH_GL(c, als_bias_piece_kernel, grid, block, 0, c->stream, a);
-    }
-    if (M.rows > 0)
-        hipLaunchKernelGGL(cmfk::als_bias_combine_kernel, dim3((unsigned)((M.rows + 255) / 256)), dim3(256), 0, c->stream, (const double *)a.part,
-                           (const int64_t *)b.first[axis], M.rows, b.lb, out);
-    HIPCHK(hipGetLastError());
     return CMF_OK;
 }
 
@@ -372,21 +291,7 @@ extern "C" int cmf_get_bias_f64(cmf_ctx *c, int which, int axis, double *v) {
     return CMF_OK;
 }
 
-extern "C" int cmf_als_bias_rows(cmf_ctx *c, int which, int axis, float *host_out) {
-    NEED_PROBLEM(c);
-    float *vec; int64_t n;
-    CHK(als_bias_vector(c, "cmf_als_bias_rows", which, axis, &vec, &n));
-    CHK(als_huber_rel_ok(c, "cmf_als_bias_rows", which));   // (a Huber relation: the states every step refuses)
-    if (!host_out && n > 0) return fail(CMF_EINVAL, "cmf_als_bias_rows: null output");
-    DeviceGuard dg(c->device);
-    CHK(ensure_scratch(c, c->als_bias_ws, std::max<size_t>(16, (size_t)n * sizeof(float))));
-    CHK(als_bias_sweep(c, which, axis, (float *)c->als_bias_ws.p));
-    if (n) HIPCHK(hipMemcpyAsync(host_out, c->als_bias_ws.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return CMF_OK;
-}
-
-// test entry beside it: the adjusted targets bt and bp = w bt of one image (0 the pattern, 1 its transpose); nnz: the entries the
+// test entry: the adjusted targets bt and bp = w bt of one image (0 the pattern, 1 its transpose); nnz: the entries the
 // caller's buffers hold, which must be the stored entries of the pattern
 extern "C" int cmf_als_bias_targets(cmf_ctx *c, int which, int image, int64_t nnz, float *host_bt, float *host_bp) {
     NEED_PROBLEM(c);

@@ -14,70 +14,51 @@
 //                          w kappa, w (t - 1/2) where a staged tile leaves them.  A sweep without a logistic relation launches the
 //                          LG = false instance, which carries none of it.
 //   als_logit_loss_kernel<GL>     sum_O w [max(s, 0) + log1p(exp(-|s|)) - t s]: one 256-thread workgroup per piece of at most 2048
-//                          stored entries of one row (AlsBiasPiece, the lane layout of als_bias_piece_kernel), s in float32, the
+//                          stored entries of one row (the walk of cmf_als_entries.hip.h, one gather in flight), s in float32, the
 //                          terms added in float64 per lane group, the groups in group order; the pieces are added in piece order
-//                          behind the kernel boundary (als_logit_sum_kernel, one thread).
+//                          behind the kernel boundary (als_piece_sum_kernel, one thread).
 // No atomics anywhere, vector stores only: a repeated call from the same state is bit-identical.
 #pragma once
-#include "cmf_kernels.hip.h"   // (AlsBiasPiece: cmf_als_bias.hip.h, which cmf_api.hip includes before this file)
+#include "cmf_als_entries.hip.h"
 
 namespace cmfk {
 
-struct AlsLogitLossArgs {
-    const AlsBiasPiece *pieces;
-    const int32_t *idx;
+struct AlsLogitLossArgs : AlsEntryArgs {
     const float *tv, *wv;
-    const float *A, *B;      // the factor of the image's rows, the gathered factor; pitch kp
-    int kp;
     double *part;            // [pieces]
+};
+
+struct AlsLogitLossBody {
+    const AlsLogitLossArgs &g;
+    const float *tv, *wv;    // of the piece
+    float t[1], w[1];
+    double sum[1] = {0.0};
+    __device__ __forceinline__ void begin(int64_t beg) { tv = g.tv + beg, wv = g.wv + beg; }
+    __device__ __forceinline__ void load(int j, int q, int32_t) {
+        t[j] = tv[q];
+        w[j] = wv[q];
+    }
+    __device__ __forceinline__ void use(int j, float s, int, bool real) {
+#pragma clang fp contract(off)
+        const float term = w[j] * ((fmaxf(s, 0.f) + log1pf(expf(-fabsf(s)))) - t[j] * s);
+        if (real) sum[0] += (double)term;
+    }
 };
 
 template <int GL>
 __global__ __launch_bounds__(256) void als_logit_loss_kernel(AlsLogitLossArgs g) {
-#pragma clang fp contract(off)
-    constexpr int NG = 256 / GL;
-    const AlsBiasPiece pc = g.pieces[blockIdx.x];
-    const int gl = threadIdx.x % GL, grp = threadIdx.x / GL;
-    const f32x4 a = *reinterpret_cast<const f32x4 *>(g.A + (int64_t)pc.row * g.kp + 4 * gl);
-    const int32_t *idx = g.idx + pc.beg;
-    const float *tv = g.tv + pc.beg, *wv = g.wv + pc.beg;
-    double sum = 0.0;
-    // every group runs the same number of rounds (a round past the piece's end reads its last entry again and adds nothing)
-    for (int base = 0; base < pc.len; base += NG) {
-        const int e = base + grp, q = min(e, pc.len - 1);
-        const f32x4 b = *reinterpret_cast<const f32x4 *>(g.B + (int64_t)idx[q] * g.kp + 4 * gl);
-        float s = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
-        s = group_sum<GL>(s);
-        const float term = wv[q] * ((fmaxf(s, 0.f) + log1pf(expf(-fabsf(s)))) - tv[q] * s);
-        if (e < pc.len) sum += (double)term;
-    }
-    __shared__ double red[NG];
-    if (gl == 0) red[grp] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double v = red[0];
-        for (int q = 1; q < NG; ++q) v += red[q];
-        g.part[blockIdx.x] = v;
-    }
-}
-
-// the pieces in piece order
-__global__ void als_logit_sum_kernel(const double *part, int64_t n, double *out) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    double v = 0.0;
-    for (int64_t p = 0; p < n; ++p) v += part[p];
-    *out = v;
+    AlsLogitLossBody body{g};
+    als_entry_walk<GL, 1>(g, body);
+    als_group_reduce<GL>(body.sum, g.part + blockIdx.x);
 }
 
 } // namespace cmfk
 
 // ------------------------------------------------------------------ host side (included by cmf_api.hip behind cmf_als_bg.hip.h)
 #ifdef CMF_ALS_HOST
-enum { ALS_LOGIT_LOSS_PIECE = 2048 };
-
 static bool als_logit_rel(const cmf_ctx *c, int which) { return c->rel_loss[which] == CMF_LOSS_LOGISTIC; }
 // A logistic relation is reweighted in one of two places: inside als_normal_kernel<KP, true> (FUSED, the default: the formed routes
-// only), or by a pass of its own in front of every sweep (PASSED, cmf_set_logit_pass, cmf_als_logit_pass.hip.h), after which every
+// only), or by a pass of its own in front of every sweep (PASSED, cmf_set_logit_pass, cmf_als_reweight.hip.h), after which every
 // route reads it as a Frobenius relation under w kappa and w (t - 1/2).  For routing and for the refusals of the routes without
 // formed systems a passed relation is therefore not a logistic one.
 static bool als_logit_passed(const cmf_ctx *c, int which) { return als_logit_rel(c, which) && c->als_logit_pass[which]; }
@@ -136,37 +117,16 @@ static int als_logit_loss_side(cmf_ctx *c, int which, double *out) {
     const WCsrDev &M = c->wm_sp[which][0];
     *out = 0.0;
     if (M.nnz <= 0) return CMF_OK;
-    std::vector<int64_t> ip((size_t)M.rows + 1, 0);
-    HIPCHK(hipMemcpyAsync(ip.data(), M.indptr, ip.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    std::vector<cmfk::AlsBiasPiece> pieces;
-    als_cut_rows(&ip, 1, M.rows, ALS_LOGIT_LOSS_PIECE, [&](int64_t r, int, int64_t beg, int32_t len) {
-        pieces.push_back(cmfk::AlsBiasPiece{beg, len, (int32_t)r});
-    });
-    if ((int64_t)pieces.size() > INT32_MAX) return fail(CMF_EUNSUPPORTED, "cmf_als_logistic_loss: more than 2^31 - 1 pieces");
-    const size_t pbytes = rup((int64_t)(pieces.size() * sizeof(cmfk::AlsBiasPiece)), 16);
-    CHK(ensure_scratch(c, c->als_desc, pbytes));
-    CHK(ensure_scratch(c, c->als_bias_part, (pieces.size() + 1) * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(c->als_desc.p, pieces.data(), pieces.size() * sizeof(cmfk::AlsBiasPiece), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream)); // the host vector may go
-    cmfk::AlsLogitLossArgs a;
-    a.pieces = (const cmfk::AlsBiasPiece *)c->als_desc.p;
-    a.idx = M.idx; a.tv = M.tv; a.wv = M.wv;
-    a.A = c->F[which == 0 ? CMF_U : CMF_V];
-    a.B = c->F[which == 0 ? CMF_V : CMF_Z];
-    a.kp = c->kp;
-    a.part = (double *)c->als_bias_part.p;
-    double *sum = a.part + pieces.size();
-    {
-        Timed tm(c, CMF_K_KLMU, 2.0 * (double)M.nnz * (double)c->kp);
-        const dim3 grid((unsigned)pieces.size()), block(256);
+    CHK(als_entry_pieces(c, which, 0, "cmf_als_logistic_loss"));
+    const AlsReweight &h = c->als_reweight[which];
+    cmfk::AlsLogitLossArgs a{};
+    als_entry_args(c, which, 0, h.pieces[0], a);
+    a.tv = M.tv; a.wv = M.wv;
+    return als_pieces_loss(c, h.npieces[0], M.nnz, [&](double *part) {
+        a.part = part;
+        const dim3 grid((unsigned)h.npieces[0]), block(256);
         ALS_LAUNCH_GL(c, als_logit_loss_kernel, grid, block, 0, c->stream, a);
-        hipLaunchKernelGGL(cmfk::als_logit_sum_kernel, dim3(1), dim3(64), 0, c->stream, (const double *)a.part, (int64_t)pieces.size(), sum);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(out, sum, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return CMF_OK;
+    }, out);
 }
 
 extern "C" int cmf_als_logistic_loss(cmf_ctx *c, double *lx, double *ly) {

@@ -1,6 +1,7 @@
 // cmf_als_steps.hip.h -- the host side of the ALS sweeps behind everything it calls (cmf_als.hip.h: the routes and the kernels; the
-// sweep descriptor, the ladders and the piece plan; cmf_als_bias / _bg / _logit.hip.h): the chunk loop of the formed systems, the
-// planners of the matrix-free and the dual rows, als_route, als_step -- the one place that sweeps -- and the entry points.
+// sweep descriptor, the ladders and the piece plan; cmf_als_entries / _bias / _bg / _logit / _reweight.hip.h): the chunk loop of the
+// formed systems, the planners of the matrix-free and the dual rows, the bias sweep, als_route, als_step -- the one place that
+// sweeps -- and the entry points.
 #pragma once
 #ifdef CMF_ALS_HOST
 
@@ -667,9 +668,9 @@ static int als_dual_rows(cmf_ctx *c, const AlsSweep &sw, double l2, int64_t r_be
 //   nn_cg_steps > 0  a non-negative factor with an observed relation runs that many projected CG steps per row
 //   dual_max > 0     an exact row sweep without a shared term or a logistic relation solves its rows of 1 .. dual_max entries in dual form
 //   biases           biases are bound: the adjusted targets are refreshed before the sweeps and the bias blocks swept after them
-// A relation under a Huber loss (cmf_als_huber.hip.h) is no option of a step: every sweep that reads one runs the reweighting pass
-// first and its route, whichever it is, reads the effective weights and products for the sweep's duration (AlsHuberGuard).  So does a
-// logistic relation under cmf_set_logit_pass (cmf_als_logit_pass.hip.h), which the routes then take for a Frobenius one.
+// A relation under a Huber loss (cmf_als_reweight.hip.h) is no option of a step: every sweep that reads one runs the reweighting pass
+// first and its route, whichever it is, reads the effective weights and products for the sweep's duration (AlsReweightGuard).  So does
+// a logistic relation under cmf_set_logit_pass, which the routes then take for a Frobenius one.
 struct AlsStepOpts { int nn_sweeps = 0, cg_steps = 0, nn_cg_steps = 0, dual_max = 0; bool biases = false; };
 
 enum AlsRoute { ALS_SHARED_EXACT, ALS_SHARED_HALS, ALS_ROWS_EXACT, ALS_ROWS_NNLS, ALS_ROWS_CG, ALS_ROWS_NNCG, ALS_ROWS_DUAL };
@@ -681,6 +682,35 @@ static AlsRoute als_route(bool observed, bool shared, bool logit, int kp, bool n
     if (!observed) return ALS_SHARED_EXACT;
     if (!nn && o.cg_steps) return ALS_ROWS_CG;
     return o.dual_max > 0 && !shared && !logit && kp > 32 ? ALS_ROWS_DUAL : ALS_ROWS_EXACT;   // (k_pad = 32: no class is below it)
+}
+
+// One bias sweep of relation `which` along `axis` (0 rows, 1 columns) into out (device, rows of that image): als_bias_piece_kernel
+// over the piece lists of cmf_als_bias.hip.h.  Under a Huber loss the block is reweighted like a factor's rows: the pass refreshes the
+// image of that axis at the current factors and biases, and the kernel reads w omega where it reads w.
+static int als_bias_sweep(cmf_ctx *c, int which, int axis, float *out) {
+    AlsBias &b = c->als_bias[which];
+    CHK(als_bias_replan(c, which));
+    const bool huber = als_huber_rel(c, which);
+    if (huber) CHK(als_huber_refresh(c, which, axis));
+    const WCsrDev &M = c->wm_sp[which][axis];
+    const int64_t np = b.npieces[axis];
+    CHK(ensure_scratch(c, c->als_bias_part, std::max<size_t>(16, (size_t)np * 2 * sizeof(double))));
+    cmfk::AlsBiasArgs a{};
+    als_entry_args(c, which, axis, b.pieces[axis], a);
+    a.tv = M.tv; a.wv = huber ? M.hw : M.wv;
+    a.other = axis == 0 ? b.c : b.r;
+    a.mu = (float)b.mu;
+    a.part = (double *)c->als_bias_part.p;
+    Timed tm(c, CMF_K_KLMU, 2.0 * (double)M.nnz * (double)c->kp);
+    if (np > 0) {
+        const dim3 grid((unsigned)np), block(256);
+        ALS_LAUNCH_GL(c, als_bias_piece_kernel, grid, block, 0, c->stream, a);
+    }
+    if (M.rows > 0)
+        hipLaunchKernelGGL(cmfk::als_bias_combine_kernel, dim3((unsigned)((M.rows + 255) / 256)), dim3(256), 0, c->stream, (const double *)a.part,
+                           (const int64_t *)b.first[axis], M.rows, b.lb, out);
+    HIPCHK(hipGetLastError());
+    return CMF_OK;
 }
 
 // The only place that sweeps: V, U, Z (cmf_solvers.py:248-263), each by its route; under biases the bias blocks after them.
@@ -695,8 +725,8 @@ static int als_step(cmf_ctx *c, const char *what, double l2, int nn_mask, int ma
         if (!(mask & bits[s]) || c->frows[f] <= 0) continue;
         const bool nn = (nn_mask & nnb[s]) != 0;
         const AlsSweep sw = als_sweep(c, f);
-        AlsHuberGuard huber(c);   // the Huber and passed-logistic sides of this sweep: refreshed from the current factors, bound until it is over
-        CHK(huber.bind(sw));
+        AlsReweightGuard reweighted(c);   // the Huber and passed-logistic sides of this sweep: refreshed from the current factors, bound until it is over
+        CHK(reweighted.bind(sw));
         switch (als_route(als_observed(sw), als_shared_present(c, sw), als_logit_sweep(c, sw), c->kp, nn, o)) {
         case ALS_SHARED_EXACT: CHK(als_sweep_shared(c, what, sw, l2, nn)); break;
         case ALS_SHARED_HALS: CHK(als_nnls_sweep_shared(c, what, f, l2, o.nn_sweeps)); break;
@@ -864,6 +894,21 @@ extern "C" int cmf_als_dual_step(cmf_ctx *c, double l2, int nn_mask, int mask, i
 }
 
 // ------------------------------------------------------------------ test entries
+// the bias block a step would write along `axis` of relation `which`, the biases left alone
+extern "C" int cmf_als_bias_rows(cmf_ctx *c, int which, int axis, float *host_out) {
+    NEED_PROBLEM(c);
+    float *vec; int64_t n;
+    CHK(als_bias_vector(c, "cmf_als_bias_rows", which, axis, &vec, &n));
+    CHK(als_huber_rel_ok(c, "cmf_als_bias_rows", which));   // (a Huber relation: the states every step refuses)
+    if (!host_out && n > 0) return fail(CMF_EINVAL, "cmf_als_bias_rows: null output");
+    DeviceGuard dg(c->device);
+    CHK(ensure_scratch(c, c->als_bias_ws, std::max<size_t>(16, (size_t)n * sizeof(float))));
+    CHK(als_bias_sweep(c, which, axis, (float *)c->als_bias_ws.p));
+    if (n) HIPCHK(hipMemcpyAsync(host_out, c->als_bias_ws.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CMF_OK;
+}
+
 // The row test entries: the rows a route would write for rows [row0, row0 + nrows) of sweep `which`, the factors left alone.
 // check(sw): the route's own refusals, of its arguments (sw == null: before the range check) and of the sweep (after it); run(sw,
 // out): the rows into out, where row r goes to out + (r - row0) k_pad.
@@ -882,8 +927,8 @@ static int als_rows_entry(cmf_ctx *c, const char *what, int which, int64_t row0,
     const size_t bytes = (size_t)nrows * c->kp * sizeof(float);
     CHK(ensure_scratch(c, c->als_cg_ws, bytes));
     HIPCHK(hipMemsetAsync(c->als_cg_ws.p, 0, bytes, c->stream));
-    AlsHuberGuard huber(c);
-    CHK(huber.bind(sw));
+    AlsReweightGuard reweighted(c);
+    CHK(reweighted.bind(sw));
     CHK(run(sw, (float *)c->als_cg_ws.p));
     HIPCHK(hipMemcpyAsync(host_f, c->als_cg_ws.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -986,8 +1031,8 @@ extern "C" int cmf_als_normal(cmf_ctx *c, int which, int64_t row0, int64_t nrows
     if (!als_observed(sw)) return fail(CMF_EINVAL, "cmf_als_normal: this sweep has no observed relation: one shared matrix, no per-row systems");
     if (nrows == 0) return CMF_OK;
     DeviceGuard dg(c->device);
-    AlsHuberGuard huber(c);
-    CHK(huber.bind(sw));
+    AlsReweightGuard reweighted(c);
+    CHK(reweighted.bind(sw));
     return als_rows_to_host(c, sw, l2, row0, row0 + nrows, host_H, host_g);
 }
 

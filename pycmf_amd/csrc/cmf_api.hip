@@ -92,34 +92,35 @@ struct WCsrDev {
     float *pv = nullptr, *wv = nullptr, *tv = nullptr;
     float *ev = nullptr;   // excess weights w - c0 under a background weight (cmf_als_bg.hip.h), or null
     float *bt = nullptr, *bp = nullptr; // adjusted targets t - mu - r_i - c_j and w times them under biases (cmf_als_bias.hip.h), or null
-    float *hw = nullptr, *hp = nullptr; // effective weights w omega and products under a Huber loss (cmf_als_huber.hip.h), or w kappa and
-                                        // w t - w / 2 under the logistic pass (cmf_als_logit_pass.hip.h), or null; hbound:
-    bool hbound = false;                // ... a sweep has them bound: the row kernels read them (AlsHuberGuard)
+    float *hw = nullptr, *hp = nullptr; // effective weights and products of a reweighting pass (cmf_als_reweight.hip.h): w omega and
+                                        // w t omega under a Huber loss, w kappa and w t - w / 2 under the logistic pass, or null; hbound:
+    bool hbound = false;                // ... a sweep has them bound: the row kernels read them (AlsReweightGuard)
     int64_t rows = 0, cols = 0, nnz = 0;
 };
 
 // Biases of a relation with CSR weights (cmf_als_bias.hip.h): mu, lb, the row and column biases and the piece lists of both images;
 // the adjusted targets live in the images (WCsrDev::bt / bp), t of the transposed image in its tv
-namespace cmfk { struct AlsBiasPiece; }
+namespace cmfk { struct AlsEntryPiece; }   // (cmf_als_entries.hip.h)
 struct AlsBias {
     bool on = false, dirty = false;   // dirty: the biases changed since bt / bp were written
     double mu = 0.0, lb = 0.0;
     float *r = nullptr, *c = nullptr;
-    cmfk::AlsBiasPiece *pieces[2] = {nullptr, nullptr};
+    cmfk::AlsEntryPiece *pieces[2] = {nullptr, nullptr};
     int64_t *first[2] = {nullptr, nullptr};
     int64_t npieces[2] = {0, 0};
     int64_t L = 0;                    // the piece length the lists were built for
 };
 
-// A Huber loss on a relation with CSR weights (cmf_als_huber.hip.h): delta, and what the reweighting pass needs beyond the images
-// (their hw / hp: WCsrDev) -- t in the stored order of the transpose and the piece lists of both images, built at the first pass
-// over a bound pattern (ready)
-struct AlsHuber {
-    double delta = 0.0;               // 0: none
-    bool ready = false;
-    bool logit = false;               // built for the logistic pass (cmf_als_logit_pass.hip.h): no tt1, hp written once at the build
+// What the entry passes over a relation with CSR weights keep (cmf_als_reweight.hip.h): the Huber delta; which reweighting pass the
+// images' hw / hp (WCsrDev) were built for, and with them t in the stored order of the transpose (HUBER) or hp written once (LOGIT);
+// the piece lists of both images, which the passes and the losses walk (als_entry_pieces), each built at its first use over a bound
+// pattern
+enum AlsReweightKind { ALS_REWEIGHT_NONE, ALS_REWEIGHT_HUBER, ALS_REWEIGHT_LOGIT };
+struct AlsReweight {
+    double delta = 0.0;               // of the Huber loss; 0: none
+    AlsReweightKind kind = ALS_REWEIGHT_NONE;
     float *tt1 = nullptr;
-    cmfk::AlsBiasPiece *pieces[2] = {nullptr, nullptr};
+    cmfk::AlsEntryPiece *pieces[2] = {nullptr, nullptr};
     int64_t npieces[2] = {0, 0};
 };
 
@@ -210,7 +211,7 @@ struct cmf_ctx {
     int rel_loss[2] = {0, 0};             // loss of X / Y under the ALS steps (cmf_als_logit.hip.h): CMF_LOSS_FROBENIUS | CMF_LOSS_LOGISTIC
     bool als_logit_pass[2] = {false, false}; // a logistic X / Y is reweighted by a pass in front of every sweep (cmf_set_logit_pass), not in als_normal_kernel
     AlsBias als_bias[2];                  // mu and row / column biases of X / Y (cmf_als_bias.hip.h; off: none)
-    AlsHuber als_huber[2];                // Huber loss of X / Y under the ALS steps (cmf_als_huber.hip.h; delta 0: none)
+    AlsReweight als_reweight[2];          // the reweighting passes over X / Y under the ALS steps (cmf_als_reweight.hip.h): the Huber delta, their state
     int opt_als_bias_piece = 0;           // ... stored entries per piece of a row in the bias passes (0: the default, 2048; > 0 rounded up to 16; < 0: every row is one piece)
     DevBuf als_bias_part, als_bias_ws;    // ... (num, wsum) of every piece; cmf_als_bias_rows' result / the pairs and values of cmf_predict_pairs
     int opt_choldiag = 0;  // timing diagnostics of chol_solve_kernel (wrong results)
@@ -422,9 +423,9 @@ static void als_bias_free(cmf_ctx *c, int which) {
     c->wm_sp[which][1].tv = nullptr;
     b = AlsBias();
 }
-// what the Huber pass allocated for a relation's pattern; delta stays (cmf_set_huber_delta)
-static void als_huber_free(cmf_ctx *c, int which) {
-    AlsHuber &h = c->als_huber[which];
+// what the entry passes allocated for a relation's pattern; delta stays (cmf_set_huber_delta)
+static void als_reweight_free(cmf_ctx *c, int which) {
+    AlsReweight &h = c->als_reweight[which];
     dev_free(c, h.tt1);
     for (int t = 0; t < 2; ++t) {
         dev_free(c, h.pieces[t]);
@@ -434,7 +435,7 @@ static void als_huber_free(cmf_ctx *c, int which) {
         M.hbound = false;
     }
     const double delta = h.delta;
-    h = AlsHuber();
+    h = AlsReweight();
     h.delta = delta;
 }
 static void drop_graph(StepGraph &g) {
@@ -916,7 +917,7 @@ static void release_problem(cmf_ctx *c) {
     for (int f = 0; f < 3; ++f) c->als_l2rows[f] = AlsL2Rows();   // (the device images went with c->owned)
     for (int w = 0; w < 2; ++w) {
         c->als_bias[w] = AlsBias();
-        c->als_huber[w] = AlsHuber();
+        c->als_reweight[w] = AlsReweight();
         c->rel_loss[w] = 0;
         c->als_logit_pass[w] = false;
         c->wm_bg[w] = 0.0;
@@ -2042,9 +2043,9 @@ extern "C" int cmf_rowhess_samples(cmf_ctx *c, double *credited, double *gathere
 #include "cmf_hals.hip.h"
 #define CMF_ALS_HOST   // the ALS headers, each once, in this order: a host part calls only what stands above it
 #include "cmf_als.hip.h"         // every row kernel; the sweep descriptor, the launch ladders, the piece plan
+#include "cmf_als_entries.hip.h" // the walk over the stored entries of a row piece; the piece lists and the loss tail behind it
 #include "cmf_als_bias.hip.h"    // biases
 #include "cmf_als_bg.hip.h"      // background weights, the shared terms of a sweep
 #include "cmf_als_logit.hip.h"   // relation losses
-#include "cmf_als_huber.hip.h"   // the Huber loss: the reweighting pass in front of a sweep
-#include "cmf_als_logit_pass.hip.h"   // the logistic loss by such a pass (cmf_set_logit_pass): every route
+#include "cmf_als_reweight.hip.h" // the Huber loss and the logistic loss on every route: a reweighting pass in front of a sweep
 #include "cmf_als_steps.hip.h"   // the chunk loop, the routes, als_step and every step entry point

@@ -131,7 +131,7 @@ static float *wm_data(const cmf_ctx *c, int which) { return which == 0 ? c->X : 
 
 static void wm_free_side(cmf_ctx *c, int which) {
     als_bias_free(c, which);   // biases (cmf_als_bias.hip.h) go with the weights they were set on, as a background weight does
-    als_huber_free(c, which);  // ... and what the Huber pass built for their pattern (cmf_als_huber.hip.h; the delta stays)
+    als_reweight_free(c, which);  // ... and what the entry passes built for their pattern (cmf_als_reweight.hip.h; the delta stays)
     dev_free(c, c->wm_w[which]); dev_free(c, c->wm_p[which]);
     c->wm_w[which] = c->wm_p[which] = nullptr;
     for (int t = 0; t < 2; ++t) {
